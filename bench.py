@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the relightable-3DGS hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one training iteration of the hot path on one synthetic 800x800 view over a ~300k-Gaussian scene
@@ -10,6 +10,10 @@ channels) -> pixel loss -> rasterize backward -> shading backward -> fused Adam 
 Views are sharded over ranks (one camera per rank per step, weak scaling); per-Gaussian gradients are summed with
 one RCCL all-reduce per step.  value = iterations/s summed over all ranks.  Inputs are resident in HBM before the
 timed region.  rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the --steps iterations, writes --dump-outputs and prints the line.  --full adds
+everything else the benchmark measures: per-kernel event timing and the roofline, the repeated blocks, the one-stream pass,
+relight, the data-parallel attribution, the other BASELINE configurations and the CPU baseline.
 """
 import argparse
 import os
@@ -75,6 +79,13 @@ def parse():
                          "flags given after it still override): " + "; ".join("%s = %s" % (k, v[0]) for k, v in sorted(CONFIG_PRESETS.items())))
     ap.add_argument("--plumbing-only", action="store_true",
                     help="launch/rendezvous/reduction path only, no kernels (CPU test of the --gpus N launcher)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (per-kernel timing + roofline, repeated blocks, relight, data-parallel "
+                         "attribution, other configurations, CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write one step of the timed path from the run's inputs (initial parameters, the "
+                         "last timed view) as DIR/<name>.npy: rasterizer outputs, loss, parameters after Adam (float32 / float64; "
+                         "fixed seeded samples of per-Gaussian rows and pixels, under 64 MB in all)")
     args = ap.parse_args()
     if args.config:
         # a preset fills in every flag the command line left at its default

@@ -671,7 +671,7 @@ def dp_path_one_rank(args, timeout_s=180, fake_comm_gbs=None, steps=None):
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps or args.steps), "--warmup",
            str(args.warmup), "--points", str(args.points), "--res", str(args.res), "--width", str(getattr(args, "width", 0)), "--height",
            str(getattr(args, "height", 0)), "--objective", getattr(args, "objective", "nerf"), "--sample-num", str(args.sample_num),
-           "--no-cpu-baseline", "--no-other-configs", "--relight-frames", "0", "--repeats", "0"]
+           "--no-cpu-baseline", "--no-other-configs", "--relight-frames", "0", "--repeats", "0", "--full"]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s, env=env, stdin=subprocess.DEVNULL)
         line = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -1070,6 +1070,83 @@ def emit(result):
     close_stdout()
 
 
+DUMP_LIMIT = 64 << 20     # bytes: everything --dump-outputs writes
+DUMP_ROWS = 16384          # per-Gaussian arrays of a larger scene: this many rows, a fixed seeded sample
+DUMP_PIXELS = 262144       # per-pixel arrays of a larger image: this many pixels, a fixed seeded sample
+_OUT_NAMES = ("num_rendered", "n_contrib", "image", "opacity_image", "depth", "feature", "pseudo_normal", "surface_xyz",
+              "weights", "radii")
+
+
+def _param_names(stage2):
+    """GaussianParams' trained tensors (the unfused path; the fused step objects list theirs in `_opt_order`)."""
+    names = ["xyz", "normal", "scaling", "rotation", "opacity", "features_dc", "features_rest"]
+    return names + (["base_color", "roughness", "incidents_dc", "incidents_rest", "env"] if stage2 else [])
+
+
+def step_outputs(make_step, step_fn, scene, dev, stage2, fused, cam, bg, gt, process_group=None):
+    """(name, array) pairs of one step of the timed path, through the same call as the timed steps: the rasterizer's outputs,
+    the loss and every trained parameter after the step's Adam update.  The step starts from the run's inputs -- a step object
+    built like the timed one (`make_step`) over the initial parameters, on the last timed view, its bounded forward armed with
+    the capacity the timed steps learned -- so that two runs give the same arrays up to the order of the float atomics.  The
+    timed steps' own state is no such function of the inputs: Adam's first updates are about lr * sign(gradient), so a
+    gradient at rounding level moves its parameter a whole learning rate either way, and over the warmup and timed steps that
+    reaches the rasterizer's discrete decisions (contributor counts, pixels at Gaussian edges)."""
+    p = GaussianParams(scene, dev, stage2)
+    step = make_step(p, process_group)
+    if fused:
+        if getattr(step_fn, "_capacity", None) is not None:
+            step._capacity = step_fn._capacity             # (the timed steps past the first run the bounded forward)
+        step(cam, bg, gt)                                  # forward + loss + backward + Adam, as one_step calls it
+        step.flush()
+        if step.poll_overflow():
+            raise RuntimeError("bench: the dumped step was dropped by the bounded forward")
+        outs = list(step.last_outs)
+        outs[0] = step.rendered_counts(1)[0]               # (a bounded forward returns its capacity in that slot)
+        loss, model, names = step.loss(), step, step._opt_order
+    else:
+        opt = torch.optim.Adam(p.parameters(), lr=1e-4, eps=1e-15, fused=True)      # (as run() builds it)
+        if stage2:
+            loss, outs = step(cam, bg, gt)
+        else:
+            outs = render_stage1(p, cam, bg)
+            loss = loss_stage1(outs, gt)
+        loss.backward()
+        opt.step()
+        model, names = p, _param_names(stage2)
+    torch.cuda.synchronize()
+    return [(n, t) for n, t in zip(_OUT_NAMES, outs) if t is not None] + [("loss", loss)] + \
+        [("param_" + n, getattr(model, n)) for n in names]
+
+
+def dump_outputs(out_dir, pairs, P, H, W):
+    """--dump-outputs: every array as out_dir/<name>.npy, float32 (float64 for integer data).  Arrays with one row per
+    Gaussian keep the rows of a fixed seeded sample when the scene has more than DUMP_ROWS, arrays over the image the pixels of
+    a fixed seeded sample when it has more than DUMP_PIXELS; the sample indices are written as gaussian_index / pixel_index."""
+    import numpy as np
+    g = np.random.default_rng(0)
+    rows = np.sort(g.choice(P, DUMP_ROWS, replace=False)) if P > DUMP_ROWS else None
+    pix = np.sort(g.choice(H * W, DUMP_PIXELS, replace=False)) if H * W > DUMP_PIXELS else None
+    arrays = {}
+    for name, t in pairs:
+        t = torch.as_tensor(t).detach()
+        if rows is not None and t.dim() >= 1 and t.shape[0] == P:
+            t = t[torch.from_numpy(rows).to(t.device)]
+        elif pix is not None and t.dim() >= 2 and tuple(t.shape[-2:]) == (H, W):
+            t = t.reshape(t.shape[:-2] + (H * W,))[..., torch.from_numpy(pix).to(t.device)]
+        a = t.cpu().numpy()
+        arrays[name] = a.astype(np.float32 if a.dtype.kind == "f" and a.itemsize <= 4 else np.float64)
+    if rows is not None:
+        arrays["gaussian_index"] = rows.astype(np.float64)
+    if pix is not None:
+        arrays["pixel_index"] = pix.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError("bench: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _plumbing_only(args, world, rank, backend):
     """The launcher / rendezvous / max-over-ranks reduction / rank-0 print path of run() with no kernels: what a CPU box
     can check of `bench.py --gpus N` (tests/test_dp_cpu.py).  value is null: nothing was measured."""
@@ -1097,6 +1174,7 @@ def run(args):
     # the host driver only supports dmabuf IPC: must be in the environment before the first HIP call initialises the runtime
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     t_start = time.perf_counter()
+    full = bool(getattr(args, "full", False))      # the side measurements (bench.py --full); a plain run times the headline
 
     def side_budget(want_s):
         """Seconds a side measurement in a child process may still take: the default run is meant to finish within minutes,
@@ -1150,32 +1228,34 @@ def run(args):
     params = GaussianParams(scene, dev, stage2)
     fused = not getattr(args, "unfused", False)
     opt = None if fused else torch.optim.Adam(params.parameters(), lr=1e-4, eps=1e-15, fused=True)
-    if fused and not stage2:
-        from . import fused_step
-        step_fn = fused_step.FusedStage1Step(params, lr=1e-4)
-        S = 5
-    elif fused:
-        # the whole iteration through the fused glue kernels + one-launch Adam (fused_step.py); gradients are averaged
-        # over ranks inside (three buckets of one flat slab; see fused_step.py and DESIGN.md section 5)
-        from . import fused_step
-        syn4 = getattr(args, "objective", "nerf") == "syn4"
-        from . import train_step as _ts
-        step_fn = fused_step.FusedStage2Step(params, args.sample_num, lr=1e-4, lrs=SYN4_LRS if syn4 else None,
-                                             loss_weights=_ts.STAGE2_WEIGHTS_SYN4 if syn4 else None,
-                                             bounded=os.environ.get("R3DG_BOUNDED", "1") != "0")      # (A/B experiments)
-        S = 16
-    elif stage2:
-        from . import train_step
-        step_fn = train_step.Stage2Step(params, scene, dev, args.sample_num)
-        S = 16
-    else:
-        step_fn = None
-        S = 5
+    syn4 = getattr(args, "objective", "nerf") == "syn4"
+
+    def make_step(p, process_group=None):
+        """The timed step object over the parameters `p` (--dump-outputs builds a second one over a fresh copy)."""
+        if fused and not stage2:
+            from . import fused_step
+            return fused_step.FusedStage1Step(p, lr=1e-4, process_group=process_group)
+        if fused:
+            # the whole iteration through the fused glue kernels + one-launch Adam (fused_step.py); gradients are averaged
+            # over ranks inside (three buckets of one flat slab; see fused_step.py and DESIGN.md section 5)
+            from . import fused_step
+            from . import train_step as _ts
+            return fused_step.FusedStage2Step(p, args.sample_num, lr=1e-4, lrs=SYN4_LRS if syn4 else None,
+                                              loss_weights=_ts.STAGE2_WEIGHTS_SYN4 if syn4 else None, process_group=process_group,
+                                              bounded=os.environ.get("R3DG_BOUNDED", "1") != "0")      # (A/B experiments)
+        if stage2:
+            from . import train_step
+            return train_step.Stage2Step(p, scene, dev, args.sample_num)
+        return None
+    step_fn = make_step(params)
+    S = 16 if stage2 else 5
 
     # ground-truth images: renders of a perturbed "teacher" copy, resident in HBM before timing
     with torch.no_grad():
         teacher = GaussianParams(syn.make_scene(P=args.points, seed=0, stage2=False), dev, False)
-        teacher.features_dc.add_(0.05 * torch.randn_like(teacher.features_dc))
+        # (a seeded generator of its own: the process's default device generator gave other images in every run)
+        noise = torch.randn(teacher.features_dc.shape, generator=torch.Generator().manual_seed(1))
+        teacher.features_dc.add_(0.05 * noise.to(dev))
         my_views = list(range(rank, 100, world))
         gts = {}
         for v in my_views[: max(4, (args.steps + args.warmup))]:
@@ -1218,16 +1298,20 @@ def run(args):
     torch.cuda.synchronize()
     if dp:
         dist.barrier()
-    L.r3dg_profile_enable(0 if os.environ.get("R3DG_BENCH_NOPROFILE") else 1)
-    if dp and fused and hasattr(step_fn, "measure_comm"):
+    # (--full) per-kernel HIP-event timing and the data-parallel attribution ride along in the timed region; a plain run
+    # times the iterations alone
+    profile = full and not os.environ.get("R3DG_BENCH_NOPROFILE")
+    L.r3dg_profile_enable(1 if profile else 0)
+    if full and dp and fused and hasattr(step_fn, "measure_comm"):
         step_fn.measure_comm = True          # (two event records per waited bucket: what the compute stream stalls on)
     torch.cuda.synchronize()
-    quota0 = host_cpu_quota()
+    quota0 = host_cpu_quota() if full else {}
     t0 = time.perf_counter()
     # per-kernel HIP-event timing is live inside the timed region but sampled (every EVENT_EVERY-th step): each event pair costs
     # ~2 us of host time, ~40 pairs per step, and the events themselves sit between the kernels on the stream
     for i in range(args.steps):
-        L.r3dg_profile_pause(0 if (i % EVENT_EVERY == 0 and not os.environ.get("R3DG_BENCH_NOPROFILE")) else 1)
+        if profile:
+            L.r3dg_profile_pause(0 if i % EVENT_EVERY == 0 else 1)
         one_step(args.warmup + i)
     if fused:
         step_fn.flush()                  # (world > 1) the last iteration's deferred incident-light update
@@ -1236,27 +1320,29 @@ def run(args):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    quota1 = host_cpu_quota()
+    quota1 = host_cpu_quota() if full else {}
     host_cpu = dict(quota_cores=quota1.get("quota_cores"),
                     throttled_periods_in_timed_region=quota1.get("nr_throttled", 0) - quota0.get("nr_throttled", 0),
                     throttled_ms_in_timed_region=round(1e-3 * (quota1.get("throttled_usec", 0) - quota0.get("throttled_usec", 0)), 1),
                     throttled_periods_before=quota0.get("nr_throttled"),
                     what="cgroup cpu.max / cpu.stat around the timed region: periods in which the container's CPU quota "
                          "stalled its threads (a host effect; 0 = the timed steps were not held up by it)") if quota1 else None
-    prof = _lib.profile_read()
+    prof = _lib.profile_read() if full else None
     L.r3dg_profile_enable(0)
     # the shader clock this box sustains under VALU load, measured on the device right behind the timed region (boxes of the pool
     # differed by 8 % on identical code): what `roofline.valu_bound` and a comparison between two bench lines should be read with
-    try:
-        ghz, nwaves = _lib.shader_clock_ghz(dev)
-        device_clock = dict(shader_clock_ghz_under_valu_load=round(ghz, 3), waves=nwaves,
-                            what="r3dg_clock_probe behind the timed region: shader-clock cycles per wall-clock tick over a "
-                                 "device-filling grid of FMA-only waves")
-    except Exception as e:                         # (never the reason a bench line is missing)
-        device_clock = dict(error=str(e)[:120])
+    device_clock = None
+    if full:
+        try:
+            ghz, nwaves = _lib.shader_clock_ghz(dev)
+            device_clock = dict(shader_clock_ghz_under_valu_load=round(ghz, 3), waves=nwaves,
+                                what="r3dg_clock_probe behind the timed region: shader-clock cycles per wall-clock tick over a "
+                                     "device-filling grid of FMA-only waves")
+        except Exception as e:                     # (never the reason a bench line is missing)
+            device_clock = dict(error=str(e)[:120])
     exposed_comm = None
     exposed_by_bucket = {}
-    if dp and fused and hasattr(step_fn, "exposed_comm_ms"):
+    if full and dp and fused and hasattr(step_fn, "exposed_comm_ms"):
         exposed_comm, exposed_by_bucket = step_fn.exposed_comm_ms(split=True)
         step_fn.measure_comm = False
     if fused and hasattr(step_fn, "rendered_counts"):
@@ -1268,10 +1354,18 @@ def run(args):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if getattr(args, "dump_outputs", None) and args.steps > 0:
+        # under data parallelism rank 0 runs the step alone, in a one-rank group (every rank takes part in creating it)
+        group = dist.new_group([0]) if world > 1 else None
+        if rank == 0:
+            v = gt_views[(args.warmup + args.steps - 1) % len(gt_views)]
+            dump_outputs(args.dump_outputs, step_outputs(make_step, step_fn, scene, dev, stage2, fused, cams[v], bg, gts[v], group),
+                         args.points, H_img, W_img)
+            torch.cuda.empty_cache()
 
     # spread of the headline number: the same block of --steps iterations repeated (N=1; event timing off)
     blocks = [world * args.steps / elapsed]
-    if world == 1 and getattr(args, "repeats", 0) > 0:
+    if full and world == 1 and getattr(args, "repeats", 0) > 0:
         L.r3dg_profile_pause(1)
         for r in range(args.repeats):
             torch.cuda.synchronize()
@@ -1291,7 +1385,8 @@ def run(args):
     # a few more iterations with every launch on ONE stream (FusedStage2Step.serial_streams): each stage's time with nothing
     # beside it, for the choice of the dominant kernel (kernel_table `alone`, roofline_of)
     alone = None
-    if fused and stage2 and world == 1 and not dp and hasattr(step_fn, "serial_streams") and not os.environ.get("R3DG_BENCH_NOPROFILE") \
+    if full and fused and stage2 and world == 1 and not dp and hasattr(step_fn, "serial_streams") \
+            and not os.environ.get("R3DG_BENCH_NOPROFILE") \
             and not os.environ.get("R3DG_BENCH_NO_ALONE"):          # (rocprofv3 runs: keep the trace to the pipelined iterations)
         try:
             step_fn.serial_streams = True
@@ -1312,9 +1407,9 @@ def run(args):
 
     relight = None
     comm_buckets = exposed_split = None
-    if dp and fused and hasattr(step_fn, "comm_table"):
+    if full and dp and fused and hasattr(step_fn, "comm_table"):
         comm_buckets = step_fn.comm_table()
-    if stage2 and args.relight_frames > 0:
+    if full and stage2 and args.relight_frames > 0:
         step_fn.visibility = step_fn.incident_dirs = step_fn.incident_areas = None   # free the K=train caches
         if hasattr(step_fn, "_taps"):
             step_fn._taps = step_fn._taps_src = None
@@ -1329,25 +1424,27 @@ def run(args):
     if rank == 0:
         P, N = args.points, W_img * H_img
         R_mean = float(sum(R_seen[-args.steps:])) / max(1, args.steps)
-        n_sampled = max(1, sum(1 for i in range(args.steps) if i % EVENT_EVERY == 0))     # steps whose launches were timed
-        # feature channels the timed backward launch carried (FusedStage2Step: 3 of 16 under the run_nerf.sh objective)
-        S_bwd = getattr(step_fn, "last_active_features", None)
-        S_bwd = None if S_bwd is None else len(S_bwd)
-        general = fused and stage2 and getattr(step_fn, "_frs", None) is None
-        kernels = kernel_table(prof, n_sampled, P, R_mean, N, S, args.sample_num, S_bwd=S_bwd,
-                               rename={"shade_forward": "shade_forward_general", "shade_backward": "shade_backward_general"}
-                               if general else None, alone=alone,
-                               # (whole single-GPU iterations run the incident-light chain as one kernel: fused_step.py)
-                               chain_kernel=bool(fused and stage2 and getattr(step_fn, "_chain_kernel", False) and
-                                                 getattr(step_fn, "_pre_rotated", None) is not None and not dp))
-        if not kernels:                   # experiments with the in-library event timing switched off
-            kernels = {"none": dict(avg_ms=0.0, launches=0, ms_per_iteration=0.0, algorithmic_MB=None, achieved_GBs=None)}
-        roofline = roofline_of(kernels, "achieved = algorithmic bytes of the TIMED launch (SURVEY.md 8(d) per-unit figures with "
-                               "the %s feature channels this launch carries) / HIP-event kernel time inside the iteration; "
-                               "`bound` = what the SQ counters of the same launch configuration say (`valu_bound`: wave "
-                               "instructions x 4 cycles / 1024 SIMDs); the HBM fraction is reported as the contract requires" % (
-                                   "S" if S_bwd is None else str(S_bwd)))
-        roofline["feature_channels_in_backward"] = S_bwd
+        kernels = roofline = None
+        if full:
+            n_sampled = max(1, sum(1 for i in range(args.steps) if i % EVENT_EVERY == 0))     # steps whose launches were timed
+            # feature channels the timed backward launch carried (FusedStage2Step: 3 of 16 under the run_nerf.sh objective)
+            S_bwd = getattr(step_fn, "last_active_features", None)
+            S_bwd = None if S_bwd is None else len(S_bwd)
+            general = fused and stage2 and getattr(step_fn, "_frs", None) is None
+            kernels = kernel_table(prof, n_sampled, P, R_mean, N, S, args.sample_num, S_bwd=S_bwd,
+                                   rename={"shade_forward": "shade_forward_general", "shade_backward": "shade_backward_general"}
+                                   if general else None, alone=alone,
+                                   # (whole single-GPU iterations run the incident-light chain as one kernel: fused_step.py)
+                                   chain_kernel=bool(fused and stage2 and getattr(step_fn, "_chain_kernel", False) and
+                                                     getattr(step_fn, "_pre_rotated", None) is not None and not dp))
+            if not kernels:                   # experiments with the in-library event timing switched off
+                kernels = {"none": dict(avg_ms=0.0, launches=0, ms_per_iteration=0.0, algorithmic_MB=None, achieved_GBs=None)}
+            roofline = roofline_of(kernels, "achieved = algorithmic bytes of the TIMED launch (SURVEY.md 8(d) per-unit figures with "
+                                   "the %s feature channels this launch carries) / HIP-event kernel time inside the iteration; "
+                                   "`bound` = what the SQ counters of the same launch configuration say (`valu_bound`: wave "
+                                   "instructions x 4 cycles / 1024 SIMDs); the HBM fraction is reported as the contract requires" % (
+                                       "S" if S_bwd is None else str(S_bwd)))
+            roofline["feature_channels_in_backward"] = S_bwd
         iters_s = world * args.steps / elapsed
         result = {
             "metric": "train iters/s, synthetic lego-like %dx%d, %d Gaussians (stage-%d hot path)" % (
@@ -1363,10 +1460,11 @@ def run(args):
                                        "shading fwd/bwd (K=%d) + " % args.sample_num if stage2 else "", S,
                                        P, W_img, H_img, R_mean),
                        "parallelism": "dp%d (views sharded over ranks; bucketed async RCCL all-reduce of per-Gaussian grads)" % world},
-            "roofline": roofline, "kernels": kernels, "spread_iters_per_s": spread, "host_cpu": host_cpu,
-            "device_clock": device_clock,
         }
-        if dp:
+        if full:
+            result.update({"roofline": roofline, "kernels": kernels, "spread_iters_per_s": spread, "host_cpu": host_cpu,
+                           "device_clock": device_clock})
+        if dp and full:
             # rank 0's compute stream: mean time per iteration it stood waiting for gradient all-reduce buckets (C, then the
             # deferred B in front of the next shading forward; A is waited for on a side stream, under the shading backward)
             result["exposed_comm_ms"] = None if exposed_comm is None else round(exposed_comm, 4)
@@ -1376,6 +1474,7 @@ def run(args):
             # size (R3DG_DP_BUCKETS=1 against the default 3) and schedule (exposed_comm_ms_by_bucket high at a good bus_GBs)
             result["exposed_comm_ms_by_bucket"] = {k: round(v, 4) for k, v in sorted(exposed_by_bucket.items())}
             result["comm_buckets"] = comm_buckets
+        if dp:
             result["dp_buckets"] = 1 if getattr(step_fn, "_single_bucket", False) else 3
             with step_fn._ctx:                   # (the step's own option context: the process default stays 0)
                 result["reserved_cus_for_comm"] = _lib.get_option("RESERVE_CUS")
@@ -1383,7 +1482,7 @@ def run(args):
             result["roofline_relight"] = relight.pop("roofline_relight")
         if relight is not None:
             result["relight"] = relight
-        if stage2 and world == 1 and not getattr(args, "no_other_configs", False):
+        if full and stage2 and world == 1 and not getattr(args, "no_other_configs", False):
             # the other single-GPU BASELINE configurations on the same scene (short runs; the headline stays `value`)
             try:
                 del step_fn, params
@@ -1436,7 +1535,7 @@ def run(args):
                             "bandwidth; exposed_comm_ms = what the compute stream waits for buckets C and B")
             except Exception as e:
                 result["other_configs"] = {"failed": repr(e)}
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             try:
                 result["cpu_baseline"] = cpu_baseline(scene, cams_cpu, S, args.cpu_baseline_seconds, args.points, W_img, H_img)
             except Exception as e:  # the oracle is only a reported baseline; never fail the bench on it

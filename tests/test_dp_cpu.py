@@ -214,3 +214,51 @@ def test_bench_config_presets_fill_in_what_the_command_line_left_open(monkeypatc
     monkeypatch.setattr(sys, "argv", ["bench.py"])
     a = bench.parse()
     assert a.config is None and (a.points, a.res, a.sample_num, a.stage) == (300_000, 800, 64, 2)
+
+
+def test_bench_full_and_dump_outputs_flags(monkeypatch):
+    """A plain run leaves the side measurements out (`--full` is off by default); `--dump-outputs DIR` names the directory."""
+    import importlib.util
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out/dir"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out/dir"
+
+
+def test_bench_dump_outputs_writes_fixed_samples(tmp_path):
+    """bench_core.dump_outputs: float32 / float64 files; per-Gaussian rows and image pixels of a large step reduced to the same
+    seeded samples on every call (their indices are written too); small arrays whole; never more than DUMP_LIMIT bytes."""
+    import numpy as np
+    from relightable3dgaussian_amd import bench_core as bc
+    P, H, W = bc.DUMP_ROWS + 1000, 600, 500                 # 300 000 pixels: more than DUMP_PIXELS
+    g = torch.Generator().manual_seed(0)
+    pairs = [("num_rendered", 1234), ("n_contrib", torch.randint(0, 9, (H, W), dtype=torch.int32, generator=g)),
+             ("image", torch.rand(3, H, W, generator=g)), ("radii", torch.randint(0, 5, (P,), dtype=torch.int32, generator=g)),
+             ("loss", torch.tensor(0.25, dtype=torch.float64)), ("grad_xyz", torch.rand(P, 3, generator=g)),
+             ("grad_env", torch.rand(4, 8, 3, generator=g))]
+    for d in ("a", "b"):
+        bc.dump_outputs(str(tmp_path / d), pairs, P, H, W)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted([n + ".npy" for n, _ in pairs] + ["gaussian_index.npy", "pixel_index.npy"])
+    z = {n[:-4]: np.load(os.path.join(tmp_path, "a", n)) for n in names}
+    for n in names:
+        assert np.array_equal(z[n[:-4]], np.load(os.path.join(tmp_path, "b", n)))
+    rows, pix = z["gaussian_index"].astype(np.int64), z["pixel_index"].astype(np.int64)
+    assert len(rows) == bc.DUMP_ROWS and len(set(rows)) == bc.DUMP_ROWS and rows.max() < P
+    assert len(pix) == bc.DUMP_PIXELS and len(set(pix)) == bc.DUMP_PIXELS and pix.max() < H * W
+    assert z["image"].dtype == np.float32 and z["image"].shape == (3, bc.DUMP_PIXELS)
+    assert np.array_equal(z["image"], pairs[2][1].reshape(3, -1).numpy()[:, pix])
+    assert z["n_contrib"].dtype == np.float64 and np.array_equal(z["n_contrib"], pairs[1][1].reshape(-1).numpy()[pix])
+    assert z["grad_xyz"].dtype == np.float32 and np.array_equal(z["grad_xyz"], pairs[5][1].numpy()[rows])
+    assert np.array_equal(z["radii"], pairs[3][1].numpy()[rows].astype(np.float64))
+    assert z["grad_env"].shape == (4, 8, 3) and z["loss"].dtype == np.float64 and float(z["loss"]) == 0.25
+    assert float(z["num_rendered"]) == 1234
+    with pytest.raises(RuntimeError):
+        bc.dump_outputs(str(tmp_path / "c"), [("big", torch.zeros(bc.DUMP_LIMIT // 4 + 1))], P, H, W)

@@ -166,8 +166,9 @@ def _bench(extra, env, timeout=420):
     return r, (json.loads(lines[-1]) if lines else None)
 
 
+# (--full: these tests read the relight rows and the per-bucket all-reduce attribution, which a plain run leaves out)
 SMALL = ["--steps", "3", "--warmup", "1", "--points", "20000", "--res", "160", "--sample-num", "16", "--no-cpu-baseline",
-         "--relight-frames", "0", "--no-other-configs", "--repeats", "0"]
+         "--relight-frames", "0", "--no-other-configs", "--repeats", "0", "--full"]
 
 
 def _with_relight(flags, frames="3", samples="32"):
@@ -264,6 +265,55 @@ def test_sharded_relight_frames_equal_single_rank_frames(tmp_path):
             for k in ("pbr_env", "render_env", "render", "feature", "num_contrib"):
                 assert torch.equal(frame[k], single[f][k]), "frame %d of rank %d: %s differs from the single-process frame" % (f, rank, k)
     assert seen == set(range(6))
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_outputs(tmp_path):
+    """A plain `bench.py` run at the headline size (no --full): the --steps it was given, one JSON line whose value and
+    ms_per_step agree and that carries none of the side rows.  --dump-outputs writes one step of the timed path on the run's
+    inputs: sampled Gaussians and pixels, float32 / float64, under 64 MB.  A second run writes the same arrays: the forward
+    bit for bit, the loss and the parameters after Adam up to the order of the float atomics."""
+    import numpy as np
+    from relightable3dgaussian_amd import bench_core as bc
+    dumps = []
+    for run in ("a", "b"):
+        out = str(tmp_path / run)
+        r, doc = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", out], {})
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert sum(1 for x in r.stdout.splitlines() if x.startswith("{")) == 1
+        assert doc["n_gpus"] == 1 and doc["steps"] == 3 and doc["warmup"] == 1 and doc["value"] > 0
+        assert abs(doc["value"] * doc["ms_per_step"] / 1e3 - 1.0) < 1e-2
+        for k in ("roofline", "relight", "relight_fps", "cpu_baseline", "other_configs_iters_per_s", "spread_iters_per_s"):
+            assert doc.get(k) is None, k
+        dumps.append({n[:-4]: np.load(os.path.join(out, n)) for n in os.listdir(out)})
+    a, b = dumps
+    assert {"image", "feature", "radii", "n_contrib", "loss", "param_xyz", "param_incidents", "param_env",
+            "gaussian_index", "pixel_index"} <= set(a), sorted(a)
+    assert sorted(a) == sorted(b)
+    total = 0
+    for n, x in a.items():
+        assert x.dtype in (np.float32, np.float64) and np.isfinite(x).all(), n
+        total += x.nbytes
+    assert total <= bc.DUMP_LIMIT
+    assert a["image"].shape == (3, bc.DUMP_PIXELS) and a["param_xyz"].shape == (bc.DUMP_ROWS, 3)
+    for n in a:
+        d = np.abs(a[n].astype(np.float64) - b[n])
+        if n == "loss":
+            assert d <= 1e-5 * abs(float(a[n])), n
+        elif n.startswith("param_"):
+            assert d.max() <= 1e-5 * np.abs(a[n]).max(), (n, d.max())
+        else:
+            assert np.array_equal(a[n], b[n]), n
+
+
+def test_bench_gpus_2_plain_run_dumps_outputs(tmp_path):
+    """`--gpus 2 --dump-outputs` without --full: one line without the data-parallel attribution rows, and rank 0 writes the
+    dumped step (run in a one-rank group of its own)."""
+    out = str(tmp_path / "dump")
+    r, doc = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--points", "20000", "--res", "160", "--sample-num", "16",
+                     "--dump-outputs", out], {"R3DG_DIST_BACKEND": "gloo"})
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert doc["n_gpus"] == 2 and doc["value"] > 0 and "comm_buckets" not in doc and "relight_fps" not in doc
+    assert {"image.npy", "loss.npy", "param_xyz.npy", "param_incidents.npy"} <= set(os.listdir(out))
 
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="RCCL needs one device per rank")

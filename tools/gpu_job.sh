@@ -55,18 +55,18 @@ run_task() {
     tests)
       timeout 2400 python -m pytest "$@" -m gpu -q -p no:cacheprovider < /dev/null > $O/${RD}_tests_$n.txt 2>&1; tail -30 $O/${RD}_tests_$n.txt ;;
     bench)
-      timeout 1200 python bench.py "$@" < /dev/null > $O/${RD}_bench_$n.out 2> $O/${RD}_bench_$n.err
+      timeout 1200 python bench.py --full "$@" < /dev/null > $O/${RD}_bench_$n.out 2> $O/${RD}_bench_$n.err
       tail -1 $O/${RD}_bench_$n.out > $O/${RD}_bench_${n}_compact.json; cp $O/bench_full.json $O/${RD}_bench_$n.json 2>/dev/null
       cut -c1-1500 $O/${RD}_bench_${n}_compact.json; tail -3 $O/${RD}_bench_$n.err | cut -c1-300 ;;
     short)
-      timeout 600 python bench.py --steps 40 --warmup 8 --repeats 2 $SHORT "$@" < /dev/null 2> $O/${RD}_short_$n.err | tail -1 > /dev/null
+      timeout 600 python bench.py --full --steps 40 --warmup 8 --repeats 2 $SHORT "$@" < /dev/null 2> $O/${RD}_short_$n.err | tail -1 > /dev/null
       cp $O/bench_full.json $O/${RD}_short_$n.json; show_bench "short $*" $O/${RD}_short_$n.json ;;
     ab)
       steps=$1; shift
       for spec in "$@"; do
         label="${spec%%=*}"; envs="${spec#*=}"
         for rep in 1 2; do
-          env $envs timeout 600 python bench.py --steps $steps --warmup 8 --repeats 2 $SHORT $AB_ARGS < /dev/null > /dev/null 2> $O/${RD}_ab.err
+          env $envs timeout 600 python bench.py --full --steps $steps --warmup 8 --repeats 2 $SHORT $AB_ARGS < /dev/null > /dev/null 2> $O/${RD}_ab.err
           show_bench "$label" $O/bench_full.json | tee -a $O/${RD}_ab_$n.txt
         done
       done ;;
@@ -74,9 +74,9 @@ run_task() {
       tag=$1; shift
       args="$*"; [ -z "$args" ] && args="--steps 20 --warmup 5 --repeats 0 $SHORT"
       rm -rf /tmp/prof_$n
-      (cd /tmp && R3DG_BENCH_NO_ALONE=1 timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_$n -o bench -- python $R/bench.py $args < /dev/null > $O/${RD}_${tag}_prof.log 2>&1)
+      (cd /tmp && R3DG_BENCH_NO_ALONE=1 timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_$n -o bench -- python $R/bench.py --full $args < /dev/null > $O/${RD}_${tag}_prof.log 2>&1)
       f=$(find /tmp/prof_$n -name "*.db" | head -1)
-      python tools/rocpd_summary.py "$f" $O/${RD}_${tag}_kernel_stats.md "R3DG_BENCH_NO_ALONE=1 rocprofv3 --kernel-trace --stats -- python bench.py $args" < /dev/null
+      python tools/rocpd_summary.py "$f" $O/${RD}_${tag}_kernel_stats.md "R3DG_BENCH_NO_ALONE=1 rocprofv3 --kernel-trace --stats -- python bench.py --full $args" < /dev/null
       python tools/rocpd_timeline.py "$f" 15 < /dev/null > $O/${RD}_${tag}_timeline.txt 2>&1
       python tools/rocpd_timeline.py "$f" seq < /dev/null > $O/${RD}_${tag}_sequence.txt 2>&1
       head -40 $O/${RD}_${tag}_kernel_stats.md | cut -c1-200 ;;

@@ -19,22 +19,22 @@ if [ "$1" != quick ]; then
 fi
 # ---- kernel stats + timeline of the training iteration (the one-stream "alone" pass of bench.py is left out of the trace)
 cd /tmp
-CMD="python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --relight-frames 0 --no-other-configs --repeats 0"
+CMD="python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --relight-frames 0 --no-other-configs --repeats 0"
 rm -rf /tmp/prof
 R3DG_BENCH_NO_ALONE=1 timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof -o bench -- $CMD < /dev/null > $O/prof_bench.log 2>&1
 f=$(find /tmp/prof -name "*.db" | head -1)
 cd $R
-python tools/rocpd_summary.py "$f" $O/${RD}_stage2_fused_bench_kernel_stats.md "R3DG_BENCH_NO_ALONE=1 rocprofv3 --kernel-trace --stats -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --relight-frames 0 --no-other-configs --repeats 0" < /dev/null
+python tools/rocpd_summary.py "$f" $O/${RD}_stage2_fused_bench_kernel_stats.md "R3DG_BENCH_NO_ALONE=1 rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --relight-frames 0 --no-other-configs --repeats 0" < /dev/null
 python tools/rocpd_timeline.py "$f" 15 < /dev/null > $O/${RD}_stage2_fused_step_timeline.txt 2>&1
 python tools/rocpd_timeline.py "$f" seq < /dev/null > $O/${RD}_stage2_fused_step_sequence.txt 2>&1
 # ---- the relight frame
 cd /tmp
-CMD2="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --relight-frames 40 --no-other-configs --repeats 0"
+CMD2="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --relight-frames 40 --no-other-configs --repeats 0"
 rm -rf /tmp/prof2
 R3DG_BENCH_NO_ALONE=1 timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof2 -o bench -- $CMD2 < /dev/null > $O/prof_relight.log 2>&1
 f2=$(find /tmp/prof2 -name "*.db" | head -1)
 cd $R
-python tools/rocpd_summary.py "$f2" $O/${RD}_relight_kernel_stats.md "rocprofv3 --kernel-trace --stats -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --relight-frames 40 --no-other-configs --repeats 0  (relight frames at K=384, S=28 + the visibility trace + 3 training steps)" < /dev/null
+python tools/rocpd_summary.py "$f2" $O/${RD}_relight_kernel_stats.md "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --relight-frames 40 --no-other-configs --repeats 0  (relight frames at K=384, S=28 + the visibility trace + 3 training steps)" < /dev/null
 # ---- HBM traffic + SQ counters: training kernels
 cd /tmp
 GA="SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE"
@@ -66,7 +66,7 @@ python tools/kernel_resources.py $O/${RD}_kernel_resources.json < /dev/null
 python tools/pmc_valu.py $O/${RD}_pmc_valu.json "rocprofv3 --pmc <one SQ counter group per pass> --kernel-trace on tools/kbench_raster.py (S=16, ACTIVE=2,3,4 NODEPTH=1: the backward as the training iteration launches it) and tools/kbench_shade.py (K=64); P=300000, 800x800, R~1.77M; mean per dispatch" --resources $O/${RD}_kernel_resources.json $dbs < /dev/null
 # ---- the same for the relight frame (bench.py's relight part)
 cd /tmp
-CMD3="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --repeats 0 --relight-frames 8"
+CMD3="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --repeats 0 --relight-frames 8"
 dbs=""; tdbs=""
 i=0
 for grp in "$GA" "$GB"; do
@@ -81,7 +81,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
   tdbs="$tdbs $(find /tmp/pt_$c -name '*.db' | head -1)"
 done
 cd $R
-python tools/pmc_valu.py $O/${RD}_pmc_valu_relight.json "rocprofv3 --pmc <one SQ group per pass> --kernel-trace -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --repeats 0 --relight-frames 8 (K=384, 300k Gaussians, 256x512 HDR map)" $dbs < /dev/null
+python tools/pmc_valu.py $O/${RD}_pmc_valu_relight.json "rocprofv3 --pmc <one SQ group per pass> --kernel-trace -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --repeats 0 --relight-frames 8 (K=384, 300k Gaussians, 256x512 HDR map)" $dbs < /dev/null
 python tools/pmc_traffic.py $O/${RD}_pmc_traffic_relight.json "the same command, FETCH_SIZE / WRITE_SIZE in separate passes" $tdbs < /dev/null
 # ---- attribution of the tile backward's time (ablation builds; only if they were built: python tools/variants_bwd.py build)
 if [ -d relightable3dgaussian_amd/lib/variants/bwd_no_atomics ]; then
@@ -92,7 +92,7 @@ timeout 200 python tools/kbench_adam.py < /dev/null > $O/${RD}_adam_cold.txt 2>&
 ROUND=$RD bash tools/gpu_job.sh pmc l2_raster "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum" "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_WRITE_sum TCC_WRITEBACK_sum" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_READ_sum" -- env ACTIVE=2,3,4 NODEPTH=1 ITERS=4 python $R/tools/kbench_raster.py > /dev/null 2>&1
 # ---- the default bench line (the counter files the line quotes must be the ones just collected: they are read from profiles/)
 cp $O/${RD}_pmc_valu.json $O/${RD}_pmc_traffic.json $O/${RD}_pmc_valu_relight.json $O/${RD}_pmc_traffic_relight.json profiles/
-timeout 900 python bench.py < /dev/null > $O/${RD}_bench_default.out 2> $O/${RD}_bench_default.err; tail -1 $O/${RD}_bench_default.out > $O/${RD}_bench_default_compact.json
+timeout 900 python bench.py --full < /dev/null > $O/${RD}_bench_default.out 2> $O/${RD}_bench_default.err; tail -1 $O/${RD}_bench_default.out > $O/${RD}_bench_default_compact.json
 cp $O/bench_full.json $O/${RD}_bench_default.json
 cut -c1-600 $O/${RD}_bench_default_compact.json
 python tools/bench_summary.py $O/${RD}_bench_default.json | head -40
