@@ -1,18 +1,23 @@
 """Fused stage-2 training iteration: the same computation as train_step.Stage2Step + loss.backward()
-+ Adam, but with the ~250 elementwise PyTorch launches around the hot ops replaced by the seven streaming HIP kernels of
++ Adam, but with the ~250 elementwise PyTorch launches around the hot ops replaced by the streaming HIP kernels of
 csrc/stage2_glue.hip and without an autograd graph: forward, loss, backward and optimizer are explicit calls in order.
 
-    GaussianModel activations + viewdirs      r3dg_stage2_activate            (scene/gaussian_model.py:183-232, neilf.py:74-76)
-    shading integral                          r3dg_shade_forward              (neilf.py:339-371)
-    S=16 feature row + light-smoothness sum   r3dg_stage2_pack_features       (neilf.py:115-122, 286-292)
-    rasterize                                 r3dg_rasterize_forward          (r3dg_rasterization.py:75-113)
-    image-space loss terms + their gradients  r3dg_stage2_loss                (neilf.py:212-318)
-    rasterize backward                        r3dg_rasterize_backward
+    GaussianModel activations + viewdirs,     r3dg_stage2_activate_with        (scene/gaussian_model.py:183-232, neilf.py:74-76,
+      softplus of the env texture, sum reset                                      direct_light_map.py:18-27)
+    shading integral                          r3dg_shade_frs_forward (fixed ray set) / r3dg_shade_forward_cached (neilf.py:339-371)
+    S=16 feature row + light-smoothness sum   written by the two launches above; r3dg_stage2_pack_features behind the general
+                                              shading kernel                   (neilf.py:115-122, 286-292)
+    rasterize                                 r3dg_rasterize_forward_*         (r3dg_rasterization.py:75-113)
+    pseudo normals + sRGB-mapped PBR image    r3dg_stage2_normals_srgb
+    SSIM of the image and the PBR image       r3dg_ssim_forward_pair / r3dg_ssim_backward_pair
+    image-space loss terms + their gradients  r3dg_stage2_loss (+ r3dg_stage2_smooth_fused)  (neilf.py:212-318)
+    rasterize backward                        r3dg_rasterize_backward_*
     feature grads -> shading upstream grads   r3dg_stage2_unpack_gradients
-    shading backward                          r3dg_shade_backward
-    activation chain rule -> parameter grads  r3dg_stage2_activate_backward
-    env texture: softplus' + TV term          r3dg_stage2_env_backward        (direct_light_map.py:18-27, neilf.py:294-300)
-    Adam, all groups in one launch            r3dg_adam_step                  (gaussian_model.py:465-497)
+    shading backward                          r3dg_shade_frs_backward / r3dg_shade_backward_cached
+    activation chain rule -> parameter grads, r3dg_stage2_activate_backward_with  (neilf.py:294-300)
+      env texture: softplus' + TV term
+    Adam, all groups in one launch            r3dg_adam_step                   (gaussian_model.py:465-497); the incident-light
+                                              group on the fixed ray set: r3dg_shade_frs_incident_chain
 
 The SH colour coefficients and the incident-light coefficients are each held as ONE [P,16,3] tensor (the reference
 concatenates features_dc / features_rest and incidents_dc / incidents_rest every iteration, gaussian_model.py:199-203);
@@ -295,8 +300,11 @@ class _BoundedForward:
 class FusedStage2Step(_BoundedForward):
     """Owns the raw parameters (copied from a bench_core.GaussianParams) and runs whole iterations."""
 
-    def __init__(self, params, sample_num, lr=1e-4, lr_rest_scale=1.0, loss_weights=None, process_group=None,
-                 overlap_geometry=False, overlap_ordering=True, lrs=None, bounded=True):
+    # whole single-GPU iterations close the incident-light group with ONE chain kernel (read by bench_core's --full attribution)
+    _chain_kernel = True
+
+    def __init__(self, params, sample_num, lr=1e-4, lr_rest_scale=1.0, loss_weights=None, process_group=None, lrs=None,
+                 bounded=True):
         """`lrs`: optional per-group learning rates {xyz, normal, scaling, rotation, opacity, shs, shs_rest, base_color,
         roughness, incidents, incidents_rest, env} as GaussianModel.training_setup / DirectLightMap.training_setup set
         them (scene/gaussian_model.py:465-486, the stage-2 values of script/run_nerf.sh:25-31); missing names use `lr`
@@ -353,7 +361,6 @@ class FusedStage2Step(_BoundedForward):
         # unweighted sums: l1, pbr l1, normal mse, light l1, TV(env), SSIM(image), SSIM(pbr), and the three edge-aware
         # smoothness sums (base colour, roughness, diffuse light)
         self.sums = torch.zeros(10, SUM_SLOTS, **f)       # R3DG_SUM_SLOTS floats per quantity (include/r3dg_hip.h)
-        self._smooth_scratch = None
         self.d_pbr, self.d_diffuse = torch.empty(P, 3, **f), torch.empty(P, 3, **f)
         self._absmax = torch.zeros((P + 255) // 256, **f)       # block maxima of |d_pbr|, |d_diffuse| (unpack kernel)
         self._d_env = None
@@ -400,21 +407,17 @@ class FusedStage2Step(_BoundedForward):
         self._pending_b = None
         self._acc = None                            # the tile backward's accumulator slab, zero-filled off the critical path
         self._early_pending = False                 # the early-Adam stream holds work no other stream has been ordered behind yet
-        self._b_early = False
-        self._a_late = False
+        # the iteration's schedule (forward_backward): work on the early stream, the incident-light chain queued there, the SH
+        # group updated with the others although the chain is queued
+        self._early = self._b_early = self._a_late = False
         self._dp_chain = None                       # data parallel: the ray set whose chain kernel closes this iteration's bucket B
         # softplus of the environment texture, refreshed behind the Adam launch that updates the texture (see optimizer_step)
         self._env_c = None                          # softplus(environment texture), see _env_buffer
         self._zero_depth_grad = None
         # instance ordering of the rasterizer runs here, under the shading forward (register-light, latency-bound kernels
         # next to a VALU-bound one)
-        self._order_stream = shared_stream(dev, "order") if overlap_ordering else None
-        self._adam_stream = None
-        self._early = False
-        # Optional second stream for the per-Gaussian geometry backward.  Measured on MI355X: a loss -- the shading
-        # backward fills the register file (2 waves/SIMD x 221 VGPRs); capping the geometry kernel at 64 VGPRs so that it
-        # fits beside it spills 35 registers and slows both (2.13 -> 2.20 ms/step).  Off by default.
-        self._side = shared_stream(dev, "geometry") if overlap_geometry else None
+        self._order_stream = shared_stream(dev, "order")
+        self._adam_stream = None                    # the early-Adam stream, created at first use (_early_stream)
         self._geo_done = None
         self.group = process_group
         self.world, self.dp = _world_of(process_group)
@@ -461,11 +464,7 @@ class FusedStage2Step(_BoundedForward):
         # incident-light chain of a whole single-GPU iteration: (ray set, coefficient tensor, its version) the rotated coefficients
         # in the ray set were computed FROM, when that was done ahead of the next iteration; work still running on the early stream
         self._pre_rotated = None
-        self._defer_b = os.environ.get("R3DG_EARLY_INCIDENTS", "1") != "0"
-        self._chain_kernel = os.environ.get("R3DG_INCIDENT_CHAIN_KERNEL", "1") != "0"   # (A/B: one kernel or three launches)
-        self._chain_late = os.environ.get("R3DG_INCIDENT_CHAIN_LATE", "1") != "0"       # (A/B: behind the other groups' Adam)
-        self._chain_deferred = None
-        self._leave_room = os.environ.get("R3DG_SHADE_LEAVE_ROOM", "auto")          # (A/B: "1" / "0" = one workgroup per CU for the shading forward always / never)
+        self._chain_deferred = None                 # (ray set, skip flag, Adam step count) of the chain optimizer_step queues
         self.opt = FusedAdam([
             dict(param=self.xyz, lr=rate("xyz")), dict(param=self.normal, lr=rate("normal")),
             dict(param=self.scaling, lr=rate("scaling")), dict(param=self.rotation, lr=rate("rotation")),
@@ -594,14 +593,18 @@ class FusedStage2Step(_BoundedForward):
         pr = self._pre_rotated
         return pr is not None and pr[0] is self._frs and pr[1] is self._incidents and pr[2] == self._incidents._version
 
+    def _early_stream(self):
+        """The early-Adam stream (the process's shared "early" stream), created at first use."""
+        if self._adam_stream is None:
+            self._adam_stream = shared_stream(self.dev, "early")
+        return self._adam_stream
+
     def _aux_stream(self):
         """The early-Adam stream, for the side work of the fixed-ray-set path on one GPU; None without that path and under data
         parallelism (the stream then carries the buckets' waits and the coefficients are updated late, in flush())."""
         if self._frs is None or self.dp or self.serial_streams:
             return None
-        if self._adam_stream is None:
-            self._adam_stream = shared_stream(self.dev, "early")
-        return self._adam_stream
+        return self._early_stream()
 
     def _listed_stream(self):
         """The early-Adam stream when the fixed-ray-set path has Gaussians off the rotated path: their general kernels run there in
@@ -609,9 +612,7 @@ class FusedStage2Step(_BoundedForward):
         idle during the forward, and in the backward bucket A's all-reduce is issued from it, behind the geometry backward)."""
         if self._frs is None or self._frs.n_invalid == 0 or self.serial_streams:
             return None
-        if self._adam_stream is None:
-            self._adam_stream = shared_stream(self.dev, "early")
-        return self._adam_stream
+        return self._early_stream()
 
     @_in_context
     def forward_backward(self, cam, bg, gt, early_adam=False, image_mask=None, split_geometry=None, chain_incidents=False):
@@ -643,27 +644,23 @@ class FusedStage2Step(_BoundedForward):
             # the rotation of the incident-light coefficients into the ray frames depends on nothing of this view: it goes to the
             # side stream now and runs beside the activations and the projection instead of in front of the shading forward
             rotated_for = None
-            acc_ready = False
             aux = self._aux_stream()
-            chained = False          # this iteration's rotated coefficients come from the previous iteration's incident-light chain
             if self._chain_deferred is not None:
                 self.flush()         # (forward_backward was called twice without optimizer_step: the pending chain runs now)
             if aux is not None:
                 _lib.stream_wait(aux, main)
-                chained = self._rotation_is_current()
-                if not chained:                              # (normally done at the end of the previous iteration: see below)
+                # (normally the previous iteration's incident-light chain left the rotated coefficients in place: see below)
+                if not self._rotation_is_current():
                     with torch.cuda.stream(aux):
                         self._frs.rotate(self._incidents)
                 rotated_for = self._frs
             # The small view-independent jobs of the iteration -- softplus of the environment texture, the loss-sum reset -- ride
-            # as extra workgroups of the activation launch (rounds 3-4: three launches on the early stream behind the coefficient
-            # rotation; round 5 first on the main stream behind the front end's launches: 52 us under contention).  The tile
-            # backward's accumulator slab needs no zero fill any more: its scatter pass writes every element.
+            # as extra workgroups of the activation launch.  The tile backward's accumulator slab needs no zero fill: its scatter
+            # pass writes every element.
             acc_n = (11 + 16) * P
             if self._acc is None or self._acc.numel() != acc_n:
                 self._acc = torch.empty(acc_n, dtype=torch.float32, device=dev)
             env_c = self._env_buffer()
-            acc_ready = True
             self.refresh_activations(cam, env_out=env_c, zero=self.sums)
             self._iter += 1
             flag_cur = self._flag_of_iteration()
@@ -671,7 +668,7 @@ class FusedStage2Step(_BoundedForward):
             if self._early_pending and (aux is None or not (use_bounded and order_stream is not None)):
                 # (the previous iteration left work on the early stream that only the bounded, three-stream schedule is ordered
                 # behind by construction: any other schedule joins it here)
-                _lib.stream_wait(main, self._early_stream)
+                _lib.stream_wait(main, self._adam_stream)
                 self._early_pending = False
             if use_bounded:
                 # bounded forward: projection + instance ordering go to the ordering stream NOW and run beside the
@@ -703,16 +700,11 @@ class FusedStage2Step(_BoundedForward):
                 rotated = rotated_for is self._frs or (self.dp and self._rotation_is_current())
                 self._frs.forward(self.a_base, self.a_rough, self.a_normal, self.a_viewdirs, self._incidents, env_c,
                                   self.visibility, self.shade_out, uniform_area=self._uniform_area,
-                                  # (one workgroup per CU beside the instance ordering while THAT is the longer path.  It is not
-                                  # when something sits in front of this kernel: the deferred incident-light update of a
-                                  # data-parallel run (558 -> 568 it/s on one rank without the cap), or the incident-light chain of
-                                  # a whole single-GPU iteration AS THREE LAUNCHES, which ends ~50 us after the projection has
-                                  # started: 781 -> 789 it/s without the cap.  The chain as one kernel ends before the projection
-                                  # starts and the cap pays again (806 vs 801 it/s), as it does for the iterations without a chain
-                                  # (frozen geometry, run_syn4.sh: 835 vs 826))
-                                  leave_room=(order_stream is not None and not self.dp and
-                                              (self._leave_room == "1" or
-                                               (self._leave_room == "auto" and not (chained and not self._chain_kernel)))),
+                                  # (one workgroup per CU beside the instance ordering while THAT is the longer path: 806 vs 801
+                                  # it/s without the cap, frozen geometry (run_syn4.sh) 835 vs 826.  Not under data parallelism,
+                                  # where the deferred incident-light update sits in front of this kernel: 558 -> 568 it/s on one
+                                  # rank without the cap)
+                                  leave_room=order_stream is not None and not self.dp,
                                   # the few hundred Gaussians off the rotated path: their general kernel on the (idle) early-Adam
                                   # stream beside the rotation and the main kernel, joined below before the features are packed
                                   listed_stream=self._listed_stream(), rotated=rotated,
@@ -771,23 +763,12 @@ class FusedStage2Step(_BoundedForward):
             active = [2, 3, 4] + ([5, 6, 7] if self.w["normal"] != 0.0 else [])
             w_bc, w_r, w_ls = (self.w[k] / (3.0 * N) for k in ("base_color_smooth", "roughness_smooth", "light_smooth"))
             if w_bc != 0.0 or w_r != 0.0 or w_ls != 0.0:
-                if os.environ.get("R3DG_SMOOTH_FUSED", "1") != "0":
-                    # one streaming kernel: the divided maps and the adjoint inputs never exist in HBM
-                    _lib.check(L.r3dg_stage2_smooth_fused(
-                        stream(), W, H, opacity.data_ptr(), feature.data_ptr(), n_contrib.data_ptr(), gt_c.data_ptr(),
-                        _lib.ptr(mask_c), w_bc, w_r, w_ls, 1 if self.w["normal"] != 0.0 else 0, g[3:4].data_ptr(),
-                        g[4:20].data_ptr(), self.sums[7].data_ptr()), "stage2_smooth_fused")
-                else:                                      # (the three-kernel reference formulation: parity tests, A/B)
-                    if self._smooth_scratch is None or self._smooth_scratch.numel() != 30 * N:
-                        self._smooth_scratch = torch.empty(30 * N, dtype=torch.float32, device=dev)
-                    sc = self._smooth_scratch
-                    _lib.check(L.r3dg_stage2_smooth_forward(
-                        stream(), W, H, opacity.data_ptr(), feature.data_ptr(), n_contrib.data_ptr(), gt_c.data_ptr(),
-                        _lib.ptr(mask_c), w_bc, w_r, w_ls, sc.data_ptr(), self.sums[7].data_ptr()), "stage2_smooth_forward")
-                    _lib.check(L.r3dg_stage2_smooth_backward(
-                        stream(), W, H, opacity.data_ptr(), feature.data_ptr(), n_contrib.data_ptr(), _lib.ptr(mask_c),
-                        sc.data_ptr(), w_bc, w_r, w_ls, 1 if self.w["normal"] != 0.0 else 0, g[3:4].data_ptr(),
-                        g[4:20].data_ptr()), "stage2_smooth_backward")
+                # one streaming kernel: the divided maps and the adjoint inputs never exist in HBM (r3dg_stage2_smooth_forward /
+                # _backward, the three-pass formulation, stay as its reference in the tests)
+                _lib.check(L.r3dg_stage2_smooth_fused(
+                    stream(), W, H, opacity.data_ptr(), feature.data_ptr(), n_contrib.data_ptr(), gt_c.data_ptr(),
+                    _lib.ptr(mask_c), w_bc, w_r, w_ls, 1 if self.w["normal"] != 0.0 else 0, g[3:4].data_ptr(),
+                    g[4:20].data_ptr(), self.sums[7].data_ptr()), "stage2_smooth_fused")
                 active += ([8, 9, 10] if w_bc != 0.0 else []) + ([11] if w_r != 0.0 else [])
                 if w_ls != 0.0:
                     active += [12, 13, 14] + ([5, 6, 7] if self.w["normal"] == 0.0 else [])
@@ -800,110 +781,73 @@ class FusedStage2Step(_BoundedForward):
                     P, 16, H, W, g[4:20], geom, R, binning, img, active_features=sorted(active))
                 dL_dmeans2D = None
             else:
-                geo_stream = None if self.serial_streams else self._side
-                if geo_stream is None and split_geometry and self._listed_stream() is not None:
-                    # whole iterations on one GPU with Gaussians off the rotated path: the per-Gaussian geometry backward goes
-                    # to the early-Adam stream and runs beside the gradient unpack and the general shading backward on those few
-                    # hundred Gaussians (a latency-bound launch that r3dg_shade_frs_backward queues FIRST) instead of in front
-                    # of them; the main shading backward, which fills the register file, starts when both are about done
-                    geo_stream = self._listed_stream()
+                # whole iterations with Gaussians off the rotated path: the per-Gaussian geometry backward goes to the early-Adam
+                # stream and runs beside the gradient unpack and the general shading backward on those few hundred Gaussians (a
+                # latency-bound launch that r3dg_shade_frs_backward queues FIRST) instead of in front of them; the main shading
+                # backward, which fills the register file, starts when both are about done
+                geo_stream = self._listed_stream() if split_geometry else None
                 bw = rasterizer_ops.rasterize_gaussians_backward(
                     bg, self.xyz, self.features, radii, empty, self.a_scales, self.a_rot, 1.0, empty, vm,
                     # (no depth gradient: an EMPTY tensor = NULL = the caller's promise that the depth image carries no loss term)
                     cam.full_proj_transform, cam.tanfovx, cam.tanfovy, g[0:3], g[3:4], empty, g[4:20],
                     self.shs, 3, campos, geom, R, binning, img, True, False, dL_dsh_out=self.grads["shs"],
                     geometry_stream=geo_stream, active_features=sorted(active),
-                    zeroed_accumulators=self._acc if acc_ready else None)
+                    zeroed_accumulators=self._acc)
                 dL_dmeans2D, _dcol, dL_dopacity, dL_dmeans3D, dL_dfeatures, _dcov, _dsh, dL_dscales, dL_drot = bw
                 if geo_stream is not None:
                     if self._geo_done is None:
                         self._geo_done = torch.cuda.Event()
                     self._geo_done.record(geo_stream)
             handle_a = None
-            if self._side is None and self._bucket_a is not None and not self._single_bucket:
+            if self._bucket_a is not None and not self._single_bucket:
                 # bucket A (SH gradient + flag) travels under the shading backward; issued from the stream that produced it
                 if geo_stream is not None:
                     with torch.cuda.stream(geo_stream):
                         handle_a = self._allreduce_async(self._bucket_a, "A")
                 else:
                     handle_a = self._allreduce_async(self._bucket_a, "A")
-            self._early = False
-            if early_adam and not self.dp and self._groups_a:
-                # Adam of the SH group on a side stream, behind the geometry backward that produces its gradient
-                side = geo_stream
-                if side is None:
-                    if self._adam_stream is None:
-                        self._adam_stream = shared_stream(dev, "early")
-                    side = self._adam_stream
+            # SCHEDULE of the two large groups' updates.
+            # a_early: the SH group's Adam on the early stream UNDER the shading backward, behind the geometry backward that
+            #   produces its gradient -- under data parallelism behind bucket A's all-reduce, which carries the overflow flag too.
+            # b_early: the INCIDENT-LIGHT CHAIN (single GPU, fixed ray set, bounded three-stream forward).  The group's gradient is
+            #   finished by the rotation back; the group's Adam and the rotation of the NEW coefficients into the ray frames (the
+            #   first thing the next iteration's shading forward needs, and independent of the next view) follow it as ONE kernel on
+            #   the early stream, queued by optimizer_step behind the other groups' Adam -- beside the next iteration's activations
+            #   + projection instead of Adam(all groups) -> activations -> rotation -> shading forward in a row (~100 us in which
+            #   only small launches ran).  Without the early Adam: frozen SH colour (run_syn4.sh / run_dtu.sh)
+            #   831 -> 843 it/s at sample_num 64, 606 -> 610 on the DTU frame, but not above 40 M samples (399 -> 392 at
+            #   sample_num 384: there the shading forward is the long path of the forward window and the chain in front of it
+            #   costs more than the launches it saves); above a million Gaussians (no early Adam: __call__) the launches it
+            #   replaces stream 2112 bytes per Gaussian, the chain 1741.
+            # a_late: the chain is queued but the SH group is updated with the others in optimizer_step.
+            a_early = early_adam and bool(self._groups_a) and (handle_a is not None or not self.dp)
+            b_early = (not self.dp and self._frs is not None and order_stream is not None and use_bounded and
+                       (a_early or (bool(self._groups_b) and (P * self.K <= 40_000_000 if early_adam else chain_incidents))))
+            self._early, self._b_early, self._a_late = a_early or b_early, b_early, b_early and not a_early
+            if self._early:
+                side = self._early_stream()
+                self.opt.begin_step()
+                self._early_pending = not self.dp
+            if a_early:
+                if geo_stream is None and not self.dp:
                     side.wait_stream(main)
-                self.opt.begin_step()
                 with torch.cuda.stream(side):
-                    self.opt.step_groups(self._groups_a, [self.grads[k] for k in self._opt_order],
-                                         skip_flag=self._skip_cur)
-                self._early_stream = side
-                self._early = True
-                self._early_pending = True
-                self._b_early = False
-                if self._defer_b and self._frs is not None and order_stream is not None and use_bounded:
-                    # INCIDENT-LIGHT CHAIN (round 5).  The incident-light group's gradient is finished by the rotation back, which
-                    # already runs on this stream behind the main shading backward; its Adam update and the rotation of the NEW
-                    # coefficients into the ray frames (the first thing the next iteration's shading forward needs, and
-                    # independent of the next view) follow it right here -- beside the activation chain rule, the other groups'
-                    # Adam and the next iteration's activations + projection on the main / ordering streams -- instead of
-                    # Adam(all groups) -> activations -> rotation -> shading forward in a row (round 4: ~100 us in which only small
-                    # launches ran).  The main stream is NOT joined with this stream at the end of the iteration:
-                    #   * the ordering stream, which reads the SH colour coefficients in the next projection, is ordered behind the
-                    #     SH group's Adam HERE (an event recorded now: it does not wait for what is queued on this stream later);
-                    #   * the main stream joins this stream in front of the next shading forward, as it always did;
-                    #   * anybody else goes through `incidents` / flush().
-                    # (The overflow flag the group's Adam reads later is this iteration's own slot of the flag ring.)
-                    _lib.stream_wait(order_stream, side)
-                    self._b_early = True
-            elif (early_adam and not self.dp and not self._groups_a and self._groups_b and self._defer_b and self._chain_kernel
-                  and self._frs is not None and order_stream is not None and use_bounded and P * self.K <= 40_000_000):
-                # frozen SH colour (run_syn4.sh / run_dtu.sh) but a training incident-light group: no early Adam, but the
-                # incident-light chain -- one kernel on the early stream behind the other groups' Adam -- all the same, instead of
-                # rotation back (main stream) -> Adam (all groups) -> ... -> rotation at the top of the next iteration: 831 -> 843
-                # it/s at sample_num 64, 606 -> 610 on the DTU frame.  (Not at sample_num 384, 399 -> 392: there the shading
-                # forward is the long path of the forward window and the chain in front of it costs more than the launches it saves.)
-                if self._adam_stream is None:
-                    self._adam_stream = shared_stream(dev, "early")
-                self.opt.begin_step()
-                self._early_stream = self._adam_stream
-                self._early = True
-                self._early_pending = True
-                self._b_early = True
-            elif (chain_incidents and not early_adam and not self.dp and not self.serial_streams and self._groups_b and self._defer_b and self._chain_kernel
-                  and self._frs is not None and order_stream is not None and use_bounded
-                  and os.environ.get("R3DG_CHAIN_WITHOUT_EARLY_ADAM", "1") != "0"):
-                # above a million Gaussians (no early Adam of the SH group: __call__) the incident-light chain all the same, as ONE
-                # kernel on the early stream behind the other groups' Adam (round 6): at 2M Gaussians the three launches it replaces
-                # -- rotation back, the incident-light group's share of the Adam launch, rotation of the new coefficients at the top
-                # of the next iteration -- stream 2112 bytes per Gaussian, the chain 1741, with every access a contiguous run per wave
-                if self._adam_stream is None:
-                    self._adam_stream = shared_stream(dev, "early")
-                self.opt.begin_step()
-                self._early_stream = self._adam_stream
-                self._early = True
-                self._early_pending = True
-                self._b_early = True
-                self._a_late = True              # (the SH group was NOT updated early: optimizer_step takes it with the others)
-            elif early_adam and handle_a is not None and self._groups_a:
-                # data parallel: the same update on the side stream, behind bucket A's all-reduce -- whenever that lands
-                # while the shading backward is still running, the SH group's Adam runs under it too (measured with a
-                # one-rank RCCL group: 510 -> see DESIGN.md section 5).  The reduced overflow flag is snapshotted there,
-                # right after the all-reduce that carries it.
-                if self._adam_stream is None:
-                    self._adam_stream = shared_stream(dev, "early")
-                side = self._adam_stream
-                self.opt.begin_step()
-                with torch.cuda.stream(side):
-                    self._wait(handle_a, "A", side)       # the SIDE stream waits for RCCL's stream
-                    self._skip_cur = self._snapshot_flag()
+                    if self.dp:
+                        # (whenever bucket A lands while the shading backward is still running, the SH group's Adam runs under it
+                        # too: DESIGN.md section 5.  The reduced overflow flag is snapshotted right after the all-reduce that
+                        # carries it.)
+                        self._wait(handle_a, "A", side)       # the SIDE stream waits for RCCL's stream
+                        self._skip_cur = self._snapshot_flag()
                     self.opt.step_groups(self._groups_a, [self.grads[k] for k in self._opt_order], 1.0 / self.world,
                                          skip_flag=self._skip_cur)
-                self._early_stream = side
-                self._early = True
+                if b_early:
+                    # The main stream is NOT joined with the early stream at the end of the iteration:
+                    #   * the ordering stream, which reads the SH colour coefficients in the next projection, is ordered behind the
+                    #     SH group's Adam HERE (an event recorded now: it does not wait for what is queued on this stream later);
+                    #   * the main stream joins this stream in front of the next shading forward;
+                    #   * anybody else goes through `incidents` / flush().
+                    # (The overflow flag the chain reads later is this iteration's own slot of the flag ring.)
+                    _lib.stream_wait(order_stream, side)
             _lib.check(L.r3dg_stage2_unpack_gradients(
                 stream(), P, dL_dfeatures.data_ptr(), self.shade_out.data_ptr(), self.w["light"] / (3.0 * P),
                 self.d_pbr.data_ptr(), self.d_diffuse.data_ptr(), self._absmax.data_ptr(),
@@ -914,17 +858,17 @@ class FusedStage2Step(_BoundedForward):
             if self._d_env is None or self._d_env.shape != env_c.shape:
                 self._d_env = torch.zeros_like(env_c)
             if self._frs is not None:
-                # (incident-light chain as ONE kernel -- rotation back, Adam, rotation of the new coefficients, every global access a
-                # contiguous run per wave: the main shading backward then leaves the coefficient gradient in the rotated frame)
-                chain = self._early and self._b_early and self._chain_kernel and len(self._groups_b) == 1
-                # DATA PARALLEL (round 6): the same kernel closes the incident-light group there too.  The coefficient gradient
-                # stays in the rotated frame (the Gaussians off the rotated path: their world-frame rows, in the same buffer), THAT
-                # buffer is bucket B -- the rotation is linear and the same on every rank, so the sum over ranks of the rotated
-                # gradients is the rotated sum -- and the chain kernel behind the all-reduce rotates it back, applies Adam with
-                # 1 / world and rotates the new coefficients: bucket B is final one rotation launch (40 us) earlier, two launches
-                # fewer sit between its arrival and the shading forward.  Whole iterations only (`chain_incidents`).
-                dp_chain = (self.dp and chain_incidents and not chain and self._chain_kernel and len(self._groups_b) == 1
-                            and not self._single_bucket and os.environ.get("R3DG_DP_CHAIN", "1") != "0")
+                # the incident-light chain kernel rotates the coefficient gradient back itself: the main shading backward then
+                # leaves it in the rotated frame (a frozen group: the chain is only the rotation of the coefficients)
+                chain = b_early and bool(self._groups_b)
+                # DATA PARALLEL: the same kernel closes the incident-light group there too.  The coefficient gradient stays in the
+                # rotated frame (the Gaussians off the rotated path: their world-frame rows, in the same buffer), THAT buffer is
+                # bucket B -- the rotation is linear and the same on every rank, so the sum over ranks of the rotated gradients is
+                # the rotated sum -- and the chain kernel behind the all-reduce rotates it back, applies Adam with 1 / world and
+                # rotates the new coefficients: bucket B is final one rotation launch (40 us) earlier, two launches fewer sit
+                # between its arrival and the shading forward.  Whole iterations only (`chain_incidents`).
+                dp_chain = (self.dp and chain_incidents and bool(self._groups_b) and not self._single_bucket
+                            and os.environ.get("R3DG_DP_CHAIN", "1") != "0")
                 d_base, d_rough, d_view, _d_inc, d_env = self._frs.backward(
                     self.a_base, self.a_rough, self.a_normal, self.a_viewdirs, self._incidents, env_c, self.visibility,
                     self.d_pbr, self.d_diffuse,
@@ -934,38 +878,13 @@ class FusedStage2Step(_BoundedForward):
                     # whole iterations: the rotation back of the coefficient gradient goes to the stream that already carries the
                     # SH group's early Adam (optimizer_step joins it before any Adam launch reads the gradient; under data
                     # parallelism bucket B's all-reduce is issued from it) and runs beside the activation chain rule
-                    rotate_stream=self._early_stream if self._early else None, rotation_back=not (chain or dp_chain))
+                    rotate_stream=self._adam_stream if self._early else None, rotation_back=not (chain or dp_chain))
                 self._dp_chain = self._frs if dp_chain else None
-                if self._early and self._b_early:
-                    # incident-light chain, behind the rotation back: the group's Adam, then the rotation of the NEW coefficients.
-                    # (As ONE kernel -- rotation back + Adam + rotation forward, thread per Gaussian, 1536 instead of 2112 bytes per
-                    # Gaussian -- this took 300 us against the three launches' 179: eight 192-byte row streams per lane with 64-byte
-                    # strides between lanes saturate the address unit, see DESIGN.md section 7.  Measured, deleted.)
-                    def run_chain(frs=self._frs, skip=self._skip_cur, chain=chain, count=self.opt.step_count):
-                        early = self._early_stream
-                        if chain or self._chain_late:
-                            _lib.stream_wait(early, torch.cuda.current_stream(dev))     # behind what the caller's stream holds now
-                        with torch.cuda.stream(early):
-                            if chain:
-                                grp = self.opt.groups[self._groups_b[0]]
-                                frs.incident_chain(
-                                    self._incidents, self.grads["incidents"], grp["exp_avg"], grp["exp_avg_sq"], grp["lr"],
-                                    grp.get("lr_tail") if grp.get("lr_tail") is not None else grp["lr"], self.opt.betas,
-                                    self.opt.eps, count, 1.0, skip_flag=skip)
-                            else:
-                                if self._groups_b:
-                                    now, self.opt.step_count = self.opt.step_count, count       # (the iteration's own step count)
-                                    self.opt.step_groups(self._groups_b, [self.grads[k] for k in self._opt_order], skip_flag=skip)
-                                    self.opt.step_count = now
-                                frs.rotate(self._incidents)
-                        self._pre_rotated = (frs, self._incidents, self._incidents._version)
-                    if self._chain_late:
-                        # LATE: optimizer_step launches the chain BEHIND the other groups' Adam.  Both are HBM streams; side by
-                        # side the activation chain rule + that Adam -- which the whole front end of the next iteration waits for --
-                        # took 68 + 45 us instead of 20 + 40, while the chain only gates the shading forward
-                        self._chain_deferred = run_chain
-                    else:
-                        run_chain()
+                if b_early:
+                    # optimizer_step queues the chain BEHIND the other groups' Adam.  Both are HBM streams; side by side the
+                    # activation chain rule + that Adam -- which the whole front end of the next iteration waits for -- took 68 + 45
+                    # us instead of 20 + 40, while the chain only gates the shading forward (801-806 vs 793-796 it/s, HISTORY.md)
+                    self._chain_deferred = (self._frs, self._skip_cur, self.opt.step_count)
             else:
                 d_base, d_rough, d_view, _d_inc, d_env = shading_ops.shade_backward(
                     self.a_base, self.a_rough, self.a_normal, self.a_viewdirs, self._incidents, env_c, self.visibility,
@@ -974,8 +893,6 @@ class FusedStage2Step(_BoundedForward):
             gr = self.grads
             if geo_stream is not None:                                       # join the geometry backward (and nothing
                 main.wait_event(self._geo_done)       # queued behind it on that stream)
-                if self._side is not None and not self._single_bucket:
-                    handle_a = self._allreduce_async(self._bucket_a, "A")
             # the environment texture's chain rule (softplus' + total-variation term; r3dg_stage2_env_backward) rides as six
             # extra workgroups of the activation chain rule's launch
             env_job = (He, We, self.env.data_ptr(), env_c.data_ptr(), d_env.data_ptr(), self.w["env_smooth"],
@@ -1008,7 +925,7 @@ class FusedStage2Step(_BoundedForward):
                     # 397 -> 374 it/s per rank at 150 GB/s, 590 -> 543 at 300)
                     handle_b = self._allreduce_async(self._dp_chain.dcprime.view(-1), "B")
                 elif self._early:       # the incident-light gradient is finished by the rotation back, on the early stream
-                    with torch.cuda.stream(self._early_stream):
+                    with torch.cuda.stream(self._adam_stream):
                         handle_b = self._allreduce_async(self._bucket_b, "B")
                 else:
                     handle_b = self._allreduce_async(self._bucket_b, "B")
@@ -1161,20 +1078,18 @@ class FusedStage2Step(_BoundedForward):
         per-Gaussian groups + env, _groups_b = incidents -- indices into self.opt.groups, one tuple per gradient bucket."""
         grads = [self.grads[k] for k in self._opt_order]
         if not self.dp:
-            if self._early and self._b_early:
-                # the SH group was updated under the shading backward and the incident-light group is being updated on the early
-                # stream (forward_backward, "incident-light chain"): no join here
-                self._early = self._b_early = False
+            if self._b_early:
+                # the incident-light group is updated by the chain queued below, on the early stream (forward_backward,
+                # "SCHEDULE"): no join here
                 todo = (self._groups_a if self._a_late else ()) + self._groups_c
-                self._a_late = False
             elif self._early:            # the SH group was updated under the shading backward (forward_backward)
-                _lib.stream_wait(torch.cuda.current_stream(), self._early_stream)
-                self._early = False
+                _lib.stream_wait(torch.cuda.current_stream(), self._adam_stream)
                 self._early_pending = False
                 todo = self._groups_c + self._groups_b
             else:
                 self.opt.begin_step()
                 todo = self._groups_a + self._groups_c + self._groups_b
+            self._early = self._b_early = self._a_late = False
             if todo:                     # ONE launch for every remaining group
                 self.opt.step_groups(todo, grads, skip_flag=self._skip_cur)
                 if set(todo) & set(self._groups_b):
@@ -1182,8 +1097,7 @@ class FusedStage2Step(_BoundedForward):
                     # through the raw pointer: the version counter _rotation_is_current() looks at does not move)
                     self._pre_rotated = None
             if self._chain_deferred is not None:
-                run, self._chain_deferred = self._chain_deferred, None
-                run()
+                self._run_chain()
             return
         # data parallel: update each bucket when its (sum) all-reduce has landed; 1/world is applied inside the kernel
         scale = 1.0 / self.world
@@ -1198,7 +1112,7 @@ class FusedStage2Step(_BoundedForward):
                 self._pre_rotated = None
             return
         if self._early:                  # bucket A was waited for and applied on the side stream (forward_backward)
-            torch.cuda.current_stream().wait_stream(self._early_stream)
+            torch.cuda.current_stream().wait_stream(self._adam_stream)
             self._early = False
             self._wait(handle_c, "C")
         else:
@@ -1214,15 +1128,32 @@ class FusedStage2Step(_BoundedForward):
             self.opt.step_groups(self._groups_c, grads, scale, skip_flag=self._skip_cur)
         self._pending_b = (handle_b, grads, scale, self._skip_cur, self._iter)
 
+    def _run_chain(self):
+        """Queue the incident-light chain forward_backward deferred (`_chain_deferred`) on the early stream, behind what the
+        current stream holds now: rotation back of the group's gradient + its Adam update with the iteration's own step count
+        + rotation of the new coefficients, one kernel; a frozen group only gets its coefficients rotated."""
+        frs, skip, count = self._chain_deferred
+        self._chain_deferred = None
+        early = self._adam_stream
+        _lib.stream_wait(early, torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(early):
+            if self._groups_b:
+                grp = self.opt.groups[self._groups_b[0]]
+                frs.incident_chain(self._incidents, self.grads["incidents"], grp["exp_avg"], grp["exp_avg_sq"], grp["lr"],
+                                   grp.get("lr_tail") if grp.get("lr_tail") is not None else grp["lr"], self.opt.betas,
+                                   self.opt.eps, count, 1.0, skip_flag=skip)
+            else:
+                frs.rotate(self._incidents)
+        self._pre_rotated = (frs, self._incidents, self._incidents._version)
+
     @_in_context
     def flush(self):
         """Complete a deferred incident-light update: data-parallel runs apply it here; a single-GPU iteration that left it running
         on the early-Adam stream gets the CURRENT stream ordered behind it (no host wait).  A no-op otherwise."""
         if self._chain_deferred is not None:          # (somebody asks for the coefficients between forward_backward and optimizer_step)
-            run, self._chain_deferred = self._chain_deferred, None
-            run()
+            self._run_chain()
         if self._early_pending:
-            _lib.stream_wait(torch.cuda.current_stream(self.dev), self._early_stream)
+            _lib.stream_wait(torch.cuda.current_stream(self.dev), self._adam_stream)
             self._early_pending = False
         if self._pending_b is not None:
             handle_b, grads, scale, skip, it_b = self._pending_b

@@ -426,21 +426,21 @@ def test_bounded_iterations_equal_two_phase_iterations():
 def test_every_schedule_of_the_whole_iteration_trains_alike(monkeypatch):
     """A whole iteration picks one of several schedules for its two large parameter groups: the SH group's Adam under the shading
     backward or with the others (R3DG_EARLY_ADAM: the size rule takes the second above a million Gaussians), the incident-light
-    chain as one kernel, as three launches, or not at all (round 6: also WITHOUT the early Adam, what a 2M-Gaussian scene runs).
-    Same losses and parameters after five iterations up to the order of the float atomics and the chain kernel's fast-math Adam."""
+    chain kernel or no chain (round 6: the chain also WITHOUT the early Adam, what a 2M-Gaussian scene runs; neither on one stream,
+    serial_streams).  Same losses and parameters after five iterations up to the order of the float atomics and the chain kernel's
+    fast-math Adam."""
     from relightable3dgaussian_amd.fused_step import FusedStage2Step
     P, res, K = 4000, 128, 16
-    settings = {"default": {}, "no early Adam, chain kernel": {"R3DG_EARLY_ADAM": "0"},
-                "no early Adam, no chain": {"R3DG_EARLY_ADAM": "0", "R3DG_CHAIN_WITHOUT_EARLY_ADAM": "0"},
-                "early Adam, three launches": {"R3DG_INCIDENT_CHAIN_KERNEL": "0"}}
+    settings = {"default": ({}, False), "no early Adam, chain kernel": ({"R3DG_EARLY_ADAM": "0"}, False),
+                "no early Adam, no chain": ({}, True)}
     runs = {}
-    for name, env in settings.items():
-        for k in ("R3DG_EARLY_ADAM", "R3DG_CHAIN_WITHOUT_EARLY_ADAM", "R3DG_INCIDENT_CHAIN_KERNEL"):
-            monkeypatch.delenv(k, raising=False)
+    for name, (env, serial) in settings.items():
+        monkeypatch.delenv("R3DG_EARLY_ADAM", raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         params, ref, fused, cam, bg, gt = _setup(P=P, res=res, K=K, seed=11)
         step = FusedStage2Step(params, K, lr=1e-3)
+        step.serial_streams = serial
         losses = []
         for it in range(5):
             step(cam, bg, gt)
@@ -462,25 +462,20 @@ def test_switching_schedules_between_iterations_keeps_the_rotated_coefficients_c
     iteration that updates the coefficients through the plain Adam launch instead must invalidate that record -- the kernel writes
     through the raw pointer, the tensor's version counter does not move -- or the iteration after it shades with coefficients that
     are one update old (a latent bug until round 6: bench.py's one-stream pass toggled schedules, nothing compared results across
-    the toggle).  Alternating schedules must train like one schedule throughout."""
+    the toggle).  Alternating schedules -- the chain, and the one-stream pass (serial_streams) without it -- must train like one
+    schedule throughout."""
     from relightable3dgaussian_amd.fused_step import FusedStage2Step
     P, res, K = 4000, 128, 16
-    plain = {"R3DG_EARLY_ADAM": "0", "R3DG_CHAIN_WITHOUT_EARLY_ADAM": "0"}
     runs = {}
-    for name, pattern in (("default", [{}] * 6), ("alternating", [{}, plain, {}, plain, plain, {}])):
+    for name, pattern in (("default", [False] * 6), ("alternating", [False, True, False, True, True, False])):
         params, ref, fused, cam, bg, gt = _setup(P=P, res=res, K=K, seed=11)
         step = FusedStage2Step(params, K, lr=2e-3)
         losses = []
-        for env in pattern:
-            for k in plain:
-                monkeypatch.delenv(k, raising=False)
-            for k, v in env.items():
-                monkeypatch.setenv(k, v)
+        for serial in pattern:
+            step.serial_streams = serial
             step(cam, bg, gt)
             losses.append(float(step.loss()))
         runs[name] = (losses, step.incidents.clone(), step.base_color.clone())
-    for k in plain:
-        monkeypatch.delenv(k, raising=False)
     assert np.allclose(runs["alternating"][0], runs["default"][0], rtol=2e-5), (runs["alternating"][0], runs["default"][0])
     for i in (1, 2):
         ok, msg = report("param %d" % i, runs["alternating"][i], runs["default"][i], 1e-4, 1e-6)

@@ -714,7 +714,7 @@ def test_fused_stage2_iteration_host_logic_with_a_recording_library(monkeypatch)
     for _ in range(2):
         step(cam, torch.ones(3), z(3, H, W), image_mask=mask)
     names = [c[0] for c in calls]
-    # the smoothness terms: one streaming kernel behind the loss kernel (the three-pass formulation only under R3DG_SMOOTH_FUSED=0)
+    # the smoothness terms: one streaming kernel behind the loss kernel (the three-pass formulation is only the tests' reference)
     assert names.count("r3dg_stage2_smooth_fused") == 2 and names.count("r3dg_stage2_smooth_forward") == 0
     assert names.index("r3dg_stage2_loss") < names.index("r3dg_stage2_smooth_fused")
     # pbr 2-4, base colour 8-10, roughness 11, diffuse light 12-14; the normal maps' gradient has no consumer
@@ -905,7 +905,7 @@ def test_fused_stage2_iteration_spreads_the_fixed_ray_set_path_over_three_stream
     assert args[pos["raster.begin"]] == (order_stream,) and args[pos["raster.finish"]] == (order_stream,)
     listed, rotated, leave_room = args[pos["frs.forward"]]
     # the chain as one kernel ends before the projection starts: the shading forward keeps its one-workgroup-per-CU cap beside the
-    # ordering chain (it loses it behind a chain of three launches: R3DG_INCIDENT_CHAIN_KERNEL=0)
+    # ordering chain
     assert listed is early and rotated is True and leave_room is True
     assert geometry_streams[-1] is early                                       # geometry backward beside the listed backward
     # the main shading backward leaves the coefficient gradient in the rotated frame: the chain kernel rotates it back
@@ -935,18 +935,6 @@ def test_fused_stage2_iteration_spreads_the_fixed_ray_set_path_over_three_stream
     step(cam, torch.ones(3), z(3, H, W))
     it4 = [e[0] for e in events[marks[3]:]]
     assert it4.count("frs.rotate") == 1 and it4.index("frs.rotate") < it4.index("r3dg_stage2_activate_with")
-    # R3DG_INCIDENT_CHAIN_KERNEL=0: the chain as three launches -- rotation back by the shading backward's call, the group's Adam and
-    # the next rotation behind the other groups' Adam -- and the shading forward uncapped behind it
-    monkeypatch.setenv("R3DG_INCIDENT_CHAIN_KERNEL", "0")
-    three = fused_step.FusedStage2Step(params, K)
-    for _ in range(3):
-        mark = len(events)
-        three(cam, torch.ones(3), z(3, H, W))
-    it5, args5 = [e[0] for e in events[mark:]], [e[1] for e in events[mark:]]
-    assert "frs.chain" not in it5 and it5.count("frs.rotate") == 1 and it5.count("r3dg_adam_step") == 3
-    assert args5[it5.index("frs.backward")] == (early, True) and args5[it5.index("frs.forward")][2] is False
-    assert it5.index("r3dg_stage2_activate_backward_with") < it5.index("frs.rotate")
-    monkeypatch.delenv("R3DG_INCIDENT_CHAIN_KERNEL")
     # ---- a second step object gets the same side streams -------------------------------------------------------------------
     other = fused_step.FusedStage2Step(params, K)
     other(cam, torch.ones(3), z(3, H, W))
