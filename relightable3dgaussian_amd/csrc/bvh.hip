@@ -11,7 +11,7 @@
 //     reference's fence-free atomicCAS hand-off (construct.cu:243-258) would read stale boxes here;
 //   * the traversal stack holds 64 entries (reference: 32 with only a printf on overflow, trace.cuh:21-28); pushes
 //     beyond that are dropped and counted in *overflow so callers can detect it.
-#include "common.hpp"
+#include "launchers.hpp"
 
 namespace r3dg {
 
@@ -671,7 +671,7 @@ trace_opacity_packed_kernel(int num_rays, int P, int xcd_chunk, const TNode* __r
 // leaves while the rest walk thousands of nodes, so a fixed assignment leaves ~3/4 of the lanes idle) pulls the next ray from
 // a per-XCD queue -- each XCD owns a contiguous eighth of the (Morton-ordered) ray set, so the locality argument above holds --
 // with one wave-aggregated atomic per refill.  Per-ray arithmetic and visit order are unchanged.
-constexpr int REFILL_MIN_IDLE = 16;      // refill when at least this many lanes are idle (or the whole wave is)
+// (refill threshold: REFILL_MIN_IDLE, launchers.hpp)
 
 __global__ void __launch_bounds__(256)
 trace_opacity_persistent_kernel(int num_rays, int P, const TNode* __restrict__ tn, const TLeaf* __restrict__ tl,
@@ -950,10 +950,6 @@ trace_opacity_phased_kernel(int num_rays, int P, const TNode* __restrict__ tn, c
     }
 }
 
-int g_trace_count_visits = 0;        // R3DG_OPT_TRACE_COUNT_VISITS
-int g_trace_packet = 4;
-int g_trace_refill = REFILL_MIN_IDLE, g_trace_node_weight = 1, g_trace_leaf_weight = 1;     // R3DG_OPT_TRACE_*: 4 = 3 + phase-separated bodies, 3 = packed records + persistent waves, 2 = packed records, 1 = wave-cooperative, 0 = round-1 kernel
-
 // ---- trace_bvh: per-ray hit lists (K19; bvh/src/trace.cu:8-192, bound at bvh/src/bindings.cpp:11) ----------------------------
 // Pass 1 counts, per ray, the leaves of every subtree of <= 4 leaves whose box the ray reaches (tmax > 0 on the way down);
 // the caller scans the counts; pass 2 repeats the walk carrying each node's (tmin, tmax) and writes one entry per such leaf:
@@ -1171,7 +1167,7 @@ void bvh_pack_traversal(hipStream_t s, int P, const int32_t* nodes, const float*
     pack_traversal_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, nodes, aabbs, means, covs, opac, normals, tn, tl);
 }
 
-// the packed formulations (g_trace_packet 2, 3, 4) over records written by bvh_pack_traversal
+// the packed formulations (R3DG_OPT_TRACE_FORMULATION 2, 3, 4) over records written by bvh_pack_traversal
 void bvh_trace_opacity_packed(hipStream_t s, int num_rays, int P, void* records, const float* rays_o, const float* rays_d,
                               int32_t* contributes, float* out, int* overflow)
 {

@@ -16,7 +16,7 @@
 // densify call evaluates the screen-size test; appended rows enter the final prune with weights_accum = 1; the split tests
 // the signed mean, the clone its absolute value; 0/0 statistics count as 0.
 // Decisions come from fp32 comparisons, so this file is compiled without FMA contraction (build.py).
-#include "common.hpp"
+#include "launchers.hpp"
 #include "r3dg_hip.h"
 
 namespace r3dg {

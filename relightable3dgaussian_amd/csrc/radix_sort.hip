@@ -10,7 +10,7 @@
 //     (plus the digit's global base), (3) scatter with a wave-synchronous stable rank: each wave matches
 //     equal digits with one 64-bit __ballot per digit bit, ranks by popcount below the lane, and keeps
 //     per-wave digit counters in LDS -- no atomics and no block barrier inside the ranking loop.
-#include "common.hpp"
+#include "launchers.hpp"
 #include <vector>
 #include <mutex>
 #include <map>

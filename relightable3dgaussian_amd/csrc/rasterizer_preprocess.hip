@@ -7,7 +7,7 @@
 // multiply-add.  These kernels are HBM-bound (236 B read + ~75 B written per Gaussian); VALU cost is irrelevant.
 #include <atomic>
 
-#include "common.hpp"
+#include "launchers.hpp"
 
 namespace r3dg {
 
@@ -743,8 +743,6 @@ tile_emit_kernel(int P, int T, int iters, const float2* __restrict__ means2D, co
     big_rect_tiles<true>(s_big, n_big, emit_blocks, means2D, radii, depths, gx, gy, emit);
 }
 
-int g_bin_iters = 2;       // R3DG_OPT_BINNING_BLOCK_K (measured at 2M Gaussians too: 2 / 3 / 4 -> 163 / 156 / 161 it/s, no trend)
-
 // `fused` (the bounded forward): tile_counts arrive zeroed (launch_preprocess zero_words), block_sums arrive UNSCANNED
 // (launch_preprocess scan_now = false: the scan kernel scans them and writes *total), and the tile order (launch_tile_order's
 // outputs) is produced by one extra block of the emit kernel -- three launches fewer on the ordering stream's chain.
@@ -795,8 +793,6 @@ void launch_mark_visible(hipStream_t s, int P, const float* means3D, const float
     if (P <= 0) return;
     mark_visible_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, means3D, vm, present);
 }
-
-extern int g_stage_sh_rows;     // rasterizer_preprocess_bwd.hip (R3DG_OPT_STAGE_SH_ROWS)
 
 void launch_preprocess(hipStream_t s, int P, int D, int M, const float* means3D, const float* scales,
                        float scale_modifier, const float* rotations, const float* opacities, const float* shs,

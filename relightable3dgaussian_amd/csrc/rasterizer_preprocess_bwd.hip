@@ -6,7 +6,7 @@
 // 192 B dL_dsh row written).  Those two rows travel through LDS (STAGED): the block moves its 256 rows with coalesced
 // 16-byte accesses (common.hpp stage_rows_*), each thread walks its own row in LDS; a thread-per-Gaussian walk straight
 // in HBM makes every wave load/store touch 64 different cache lines.
-#include "common.hpp"
+#include "launchers.hpp"
 
 namespace r3dg {
 
@@ -305,7 +305,6 @@ preprocess_backward_kernel(int P, int D, int M, const float* __restrict__ means,
     }
 }
 
-int g_stage_sh_rows = 1;        // R3DG_OPT_STAGE_SH_ROWS: 1 = SH / dL_dsh rows through LDS (default), 0 = direct per-thread walks
 static inline int staged_row_stride_host(int row_floats) { return row_floats | 1; }
 
 void launch_preprocess_backward(hipStream_t s, int P, int D, int M, const float* means, const int* radii,

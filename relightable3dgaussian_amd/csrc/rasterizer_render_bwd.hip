@@ -12,7 +12,7 @@
 //     summed over the lane's PPL pixels) are reduced across the 64 lanes with a TRANSPOSING butterfly: after
 //     log2(NV) exchange levels lane l holds the wave total of channel chan(l), so the whole 10+S-vector costs
 //     ~NV shuffles (not 6*NV) and leaves as ONE atomic instruction with 10+S active lanes per (wave, Gaussian).
-#include "common.hpp"
+#include "launchers.hpp"
 #include "wave_reduce.hpp"
 
 #include <map>
@@ -480,7 +480,7 @@ static float* gradient_records(hipStream_t s, size_t floats, bool** dirty_out)
     return st.p;
 }
 
-// r3dg_release_scratch (capi.hip): the device is idle when this runs
+// r3dg_release_scratch (capi_core.hip): the device is idle when this runs
 void release_gradient_records()
 {
     std::lock_guard<std::mutex> lk(g_records_mu);
@@ -488,9 +488,6 @@ void release_gradient_records()
         if (kv.second.p != nullptr) (void)hipFree(kv.second.p);
     g_records.clear();
 }
-
-extern int g_cull;
-int g_bwd_lean = 1;          // R3DG_OPT_BWD_LEAN
 
 // ---- feature gradients only (frozen geometry) -------------------------------------------------------------------------
 // The Synthetic4Relight / DTU stage-2 schedule (script/run_syn4.sh:27-33, run_dtu.sh) freezes positions, covariances, opacities

@@ -13,7 +13,7 @@
 //   * per-Gaussian `weights` are summed over the wave before ONE atomic per wave
 //     (the reference issues one atomic per contributing pixel, forward.cu:374);
 //   * early-out: a wave stops walking when all its pixels are done (64-bit ballot).
-#include "common.hpp"
+#include "launchers.hpp"
 #include "pseudo_normal.hpp"
 
 namespace r3dg {
@@ -259,8 +259,6 @@ pseudo_normal_kernel(int W, int H, float focal_x, float focal_y, float cx, float
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------
-int g_cull = 1;         // conservative per-block cull of the staged entries (results do not depend on it): R3DG_OPT_CULL
-
 // `splat`: the packed per-Gaussian records of preprocess_kernel (GeometryLayout::splat, 64-byte stride)
 void launch_render_forward(hipStream_t s, int W, int H, int S, const uint32_t* tile_order, const uint32_t* ranges,
                            const uint32_t* point_list, const float* splat, const float* features, float* final_T,

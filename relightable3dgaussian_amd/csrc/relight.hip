@@ -13,7 +13,7 @@
 //                                    render_env = image + (1 - opacity) * srgb(env)
 //                                    env_only   = srgb(env)
 // Parity target: the PyTorch restatement in relightable3dgaussian_amd/relight.py (frame_reference).
-#include "common.hpp"
+#include "launchers.hpp"
 #include "r3dg_hip.h"
 
 namespace r3dg {

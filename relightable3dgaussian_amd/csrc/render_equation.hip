@@ -7,7 +7,7 @@
 // The reference runs one THREAD per Gaussian with a serial loop over the samples.  Here one WAVE owns a Gaussian and
 // the 64 lanes take the samples, so the per-sample outputs ([P,K,3] directions / lights) are written coalesced and the
 // K-sums are transposing wave reductions (wave_reduce.hpp).
-#include "common.hpp"
+#include "launchers.hpp"
 #include "wave_reduce.hpp"
 
 namespace r3dg {

@@ -17,7 +17,7 @@
 //     read back as broadcasts;
 //   * backward only: record + samples of the wave's NEXT 64-sample block arrive by LDS-DMA (global_load_lds_dwordx4),
 //     double buffered, while the current block is computed (three passes per block, 12 parked floats per lane).
-#include "common.hpp"
+#include "launchers.hpp"
 #include <cmath>
 #include <cstdlib>
 #include <map>
@@ -988,7 +988,7 @@ static int shade_cus()
     int dev = 0, cus = 256;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    // persistent grids leave g_reserve_cus CUs to a collective running beside them (common.hpp)
+    // persistent grids leave R3DG_OPT_RESERVE_CUS CUs to a collective running beside them (common.hpp)
     return cus > opt(R3DG_OPT_RESERVE_CUS) ? cus - opt(R3DG_OPT_RESERVE_CUS) : 1;
 }
 
@@ -1020,8 +1020,6 @@ static unsigned int* shade_scratch()
 // scratch of the row forward kernel ([P][16] derived floats + the float4-padded texture): one grow-only buffer per
 // (device, stream), so launches on different streams or threads never share it (common.hpp stream_scratch)
 static float* shade_records(hipStream_t s, size_t floats) { return (float*)stream_scratch(s, 0, floats * sizeof(float)); }
-
-int g_shade_row_blocks_per_cu = 0;   // R3DG_OPT_SHADE_FWD_BLOCKS_PER_CU: persistent row blocks per CU, 0 = all that fit
 
 void launch_shade_build_taps(hipStream_t s, size_t n, const float* dirs, const float* tr, int He, int We, const float* env,
                              uint32_t* taps)
@@ -1224,7 +1222,7 @@ static int frs_grid(int P, const void* kernel, size_t smem)
 // uniform_area == 0 means that value
 static inline float frs_area(float uniform_area) { return uniform_area > 0.f ? uniform_area : 6.283185307179586f; }
 
-// A fixed-ray-set call is three groups of launches, timed as three stages by the C ABI (capi.hip) so that the profile's
+// A fixed-ray-set call is three groups of launches, timed as three stages by the C ABI (capi_shading.hip) so that the profile's
 // "shade_forward" / "shade_backward" rows are ONE kernel each:
 //   aux     the coefficient rotation (forward: incidents -> cprime, kept for the backward; backward: dcprime -> d_inc), the
 //           max |upstream gradient| reduction when the caller has none

@@ -3,7 +3,7 @@
 // box-distance pruning; bounds reduced with the reference's (0,0,0) initial value, :191-199).  The result is the exact
 // 3-NN mean, so it does not depend on the traversal order; compiled with -ffp-contract=off so the fp32 distances equal
 // the CPU oracle's bit for bit.  The Morton sort is this library's own stable radix sort (3 passes of 10 bits).
-#include "common.hpp"
+#include "launchers.hpp"
 #include <cfloat>
 
 namespace r3dg {

@@ -8,7 +8,7 @@
 //   ssim_backward_kernel  the window is symmetric, so dL/dx = scale * (W*dS/dmu1 + 2x W*dS/dE[x^2] + y W*dS/dE[xy])
 //                         with the same tiling over the three partial maps.
 // HBM-bound streaming kernels: 5 map reads + 3 writes forward, 5 reads + 1 write backward per channel.
-#include "common.hpp"
+#include "launchers.hpp"
 
 namespace r3dg {
 

@@ -13,7 +13,7 @@
 // Parity target: the plain-PyTorch restatement in relightable3dgaussian_amd/train_step.py (Stage2Step), fp32 tolerance.
 #include <type_traits>
 
-#include "common.hpp"
+#include "launchers.hpp"
 #include "pseudo_normal.hpp"
 #include "r3dg_hip.h"
 
