@@ -97,7 +97,7 @@ class DensificationStats:
         import torch.distributed as dist
         if not (dist.is_available() and dist.is_initialized()):
             return
-        if dist.get_world_size(group) == 1 and os.environ.get("R3DG_DP_SINGLE_RANK") != "1":     # (fused_step._world_of)
+        if dist.get_world_size(group) == 1 and os.environ.get("R3DG_DP_SINGLE_RANK") != "1":     # (fused_base._world_of)
             return
         h = dist.all_reduce(self._slab[:4], group=group, async_op=True)
         dist.all_reduce(self._slab[4], op=dist.ReduceOp.MAX, group=group)

@@ -78,7 +78,7 @@ def train_stage1(init, cameras, images, background, extent, schedule=None, itera
     (train_step.STAGE1_WEIGHTS; `loss_weights` overrides them); `masks[v]` [1,H,W] is view v's object mask
     (Camera.image_mask; None = all ones).
     The fused iteration's bounded forward drops a view on the device when it needs more tile instances than the capacity
-    learned so far (fused_step._BoundedForward): the loop asks every `poll_interval` iterations and before every densify
+    learned so far (fused_base.FusedStepBase): the loop asks every `poll_interval` iterations and before every densify
     (`poll_overflow`: one 4-byte read-back, grows the capacity, takes the step back from Adam's count) and lists what was
     dropped as (iteration, "dropped_views", n) in the history.  The reference trains on every view (it sizes the binning state
     from the count it reads back, rasterizer_impl.cu:291): with `replay_dropped` (default; single GPU) the dropped views are

@@ -41,7 +41,7 @@ def update_visibility(xyz, scales, rotations, opacity, normal, sample_num, group
     world = rank = None
     if dist.is_available() and dist.is_initialized():
         world, rank = dist.get_world_size(group), dist.get_rank(group)
-    # a one-rank group takes the all-gather path only for the single-GPU RCCL smoke test (fused_step._world_of)
+    # a one-rank group takes the all-gather path only for the single-GPU RCCL smoke test (fused_base._world_of)
     gather = bool(world) and (world > 1 or os.environ.get("R3DG_DP_SINGLE_RANK") == "1")
     if not world or world == 1:
         world, rank = 1, 0
