@@ -1,141 +1,17 @@
-"""ctypes binding of libr3dg_hip.so (include/r3dg_hip.h).  There is NO fallback: if the HIP library is missing
-or a call fails, the op raises -- a silent CPU/eager path would void every parity claim."""
+"""ctypes binding of libr3dg_hip.so; every signature is read from include/r3dg_hip.h itself (_abi.py).  There is NO fallback: if
+the HIP library is missing or a call fails, the op raises -- a silent CPU/eager path would void every parity claim."""
 import ctypes as C
 import threading
 import os
+
+from . import _abi
+from ._abi import ALLOC_FN  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # R3DG_LIB_PATH: an experiment build of the SAME library (tools/build_variant.py) for A/B measurements; never a fallback
 LIB_PATH = os.environ.get("R3DG_LIB_PATH") or os.path.join(_HERE, "lib", "libr3dg_hip.so")
 
-ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
-
 _lib = None
-
-_f = C.c_float
-_i = C.c_int
-_p = C.c_void_p
-
-_SIGNATURES = {
-    "r3dg_last_error": (C.c_char_p, []),
-    "r3dg_version": (_i, []),
-    "r3dg_release_scratch": (_i, []),
-    "r3dg_max_features_forward": (_i, []),
-    "r3dg_max_features_backward": (_i, []),
-    "r3dg_bounded_forward_supported": (_i, [_i, _i]),
-    "r3dg_geometry_state_bytes": (C.c_size_t, [_i]),
-    "r3dg_image_state_bytes": (C.c_size_t, [_i, _i]),
-    "r3dg_binning_state_bytes": (C.c_size_t, [C.c_int64]),
-    "r3dg_geometry_state_offsets": (_i, [_i, C.POINTER(C.c_size_t)]),
-    "r3dg_geometry_state_total_offset": (C.c_size_t, [_i]),
-    "r3dg_image_state_offsets": (_i, [_i, _i, C.POINTER(C.c_size_t)]),
-    "r3dg_binning_state_offsets": (_i, [C.c_int64, C.POINTER(C.c_size_t)]),
-    "r3dg_rasterize_forward": (_i, [_p, ALLOC_FN, ALLOC_FN, ALLOC_FN, _p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p,
-                                    _p, _p, _f, _p, _p, _p, _p, _p, _f, _f, _f, _f, _i, _i, _p, _p, _p, _p, _p, _p,
-                                    _p, _p, _i, C.POINTER(_i)]),
-    "r3dg_rasterize_forward_begin": (_i, [_p, ALLOC_FN, ALLOC_FN, ALLOC_FN, _p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p,
-                                    _p, _p, _f, _p, _p, _p, _p, _p, _f, _f, _f, _f, _i, _i, _p, _p, _p, _p, _p, _p,
-                                    _p, _p, _i, C.POINTER(_p)]),
-    "r3dg_rasterize_forward_begin_bounded": (_i, [_p, ALLOC_FN, ALLOC_FN, ALLOC_FN, _p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p,
-                                            _p, _p, _p, _f, _p, _p, _p, _p, _p, _f, _f, _f, _f, _i, _i, _p, _p, _p, _p,
-                                            _p, _p, _p, _p, _i, _p, C.c_longlong, _p, _p, C.POINTER(_p)]),
-    "r3dg_rasterize_forward_finish_bounded": (_i, [_p, _p]),
-    "r3dg_rasterize_forward_finish": (_i, [_p, C.POINTER(_i)]),
-    "r3dg_rasterize_forward_finish_on": (_i, [_p, _p, C.POINTER(_i)]),
-    "r3dg_rasterize_backward": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p,
-                                     _f, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
-                                     _i, _i]),
-    "r3dg_rasterize_backward_split": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p,
-                                           _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
-                                           _p, _p, _i, _i, _i, C.POINTER(_i)]),
-    "r3dg_rasterize_backward_features": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i, C.POINTER(_i), _i]),
-    "r3dg_mark_visible": (_i, [_p, _i, _p, _p, _p, _p]),
-    "r3dg_bvh_trace_count": (_i, [_p, C.c_int64, _p, _p, _p, _p, _p, _p]),
-    "r3dg_bvh_trace_fill": (_i, [_p, C.c_int64] + [_p] * 11),
-    "r3dg_sort_temp_bytes": (C.c_size_t, [C.c_int64]),
-    "r3dg_sort_pairs": (_i, [_p, C.c_int64, _p, _p, _p, _p, _i, _p]),
-    "r3dg_set_option": (_i, [_i, _i]),
-    "r3dg_context_create": (_p, []),
-    "r3dg_context_destroy": (None, [_p]),
-    "r3dg_context_set_option": (_i, [_p, _i, _i]),
-    "r3dg_context_make_current": (_i, [_p, C.POINTER(_p)]),
-    "r3dg_get_option": (_i, [_i, C.POINTER(_i)]),
-    "r3dg_selftest_transpose_reduce": (_i, [_p, _i, _i, _p, _p, _p, _p]),
-    "r3dg_shade_forward": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
-    "r3dg_shade_forward_cached": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _p, _i, _p]),
-    "r3dg_shade_build_taps": (_i, [_p, C.c_int64, _p, _p, _i, _i, _p, _p]),
-    "r3dg_shade_frs_supported": (_i, [_i, _i, _i, _i]),
-    "r3dg_shade_frs_tables_bytes": (C.c_size_t, [_i]),
-    "r3dg_shade_frs_build_tables": (_i, [_p, _i, _p, _p]),
-    "r3dg_shade_frs_classify": (_i, [_p, _i, _p, _p]),
-    "r3dg_shade_frs_rotate": (_i, [_p, _i, _p, _p, _p]),
-    "r3dg_stream_wait_stream": (_i, [_p, _p]),
-    "r3dg_spin": (_i, [_p, _f]),
-    "r3dg_store_u64_to_host": (_i, [_p, _p, _p]),
-    "r3dg_shade_frs_build_taps": (_i, [_p, _i, _i, _p, _p, _i, _i, _p]),
-    "r3dg_shade_frs_forward": (_i, [_p, _i, _i] + [_p] * 6 + [_i, _i, _p, _f] + [_p] * 6 + [_i, _p, _i, _p, _p, _p]),
-    "r3dg_shade_frs_backward": (_i, [_p, _i, _i] + [_p] * 6 + [_i, _i, _p, _f] + [_p] * 6 + [_i] + [_p] * 10 + [_i, _p]),
-    "r3dg_shade_frs_incident_chain": (_i, [_p, _i] + [_p] * 8 + [_f] * 5 + [_i, _f, _p, _i]),
-    "r3dg_shade_build_transport": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p]),
-    "r3dg_shade_forward_transport": (_i, [_p, _i, _i] + [_p] * 9),
-    "r3dg_shade_build_split": (_i, [_p, _i, _i] + [_p] * 6 + [_f, _p, _p, _p]),
-    "r3dg_shade_env_footprints_bytes": (C.c_size_t, [_i, _i]),
-    "r3dg_shade_env_footprints": (_i, [_p, _i, _i, _p, _p]),
-    "r3dg_shade_forward_split": (_i, [_p, _i, _i] + [_p] * 11 + [_i, _i, _p]),
-    "r3dg_shade_backward": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p,
-                                 _p, _p]),
-    "r3dg_shade_backward_cached": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p,
-                                        _p, _p, _p, _p, _i]),
-    "r3dg_render_equation_forward": (_i, [_p, _i, _i, _i, _i] + [_p] * 8 + [_i] + [_p] * 4),
-    "r3dg_render_equation_forward_complex": (_i, [_p, _i, _i, _i, _i] + [_p] * 8 + [_i] + [_p] * 11),
-    "r3dg_render_equation_backward": (_i, [_p, _i, _i, _i, _i] + [_p] * 8 + [_i] + [_p] * 11),
-    "r3dg_clock_probe": (_i, [_p, _i, _p, _p, C.POINTER(C.c_int)]),
-    "r3dg_stage2_activate": (_i, [_p, _i] + [_p] * 17),
-    "r3dg_stage2_activate_with": (_i, [_p, _i] + [_p] * 17 + [_i, _p, _p, _p, _i]),
-    "r3dg_stage2_pack_features": (_i, [_p, _i] + [_p] * 8),
-    "r3dg_stage2_unpack_gradients": (_i, [_p, _i, _p, _p, _f, _p, _p, _p, _p]),
-    "r3dg_stage2_activate_backward": (_i, [_p, _i] + [_p] * 24),
-    "r3dg_stage2_activate_backward_with": (_i, [_p, _i] + [_p] * 24 + [_i, _i, _p, _p, _p, _f, _p, _p, _i]),
-    "r3dg_stage2_loss": (_i, [_p, _i, _i] + [_p] * 8 + [_f, _f, _f] + [_p] * 6 + [_i]),
-    "r3dg_stage2_smooth_forward": (_i, [_p, _i, _i] + [_p] * 5 + [_f, _f, _f, _p, _p]),
-    "r3dg_stage2_smooth_backward": (_i, [_p, _i, _i] + [_p] * 5 + [_f, _f, _f, _i, _p, _p]),
-    "r3dg_stage2_smooth_fused": (_i, [_p, _i, _i] + [_p] * 5 + [_f, _f, _f, _i, _p, _p, _p]),
-    "r3dg_stage2_pbr_srgb": (_i, [_p, _i, _i] + [_p] * 5),
-    "r3dg_stage2_normals_srgb": (_i, [_p, _i, _i, _p, _f, _f, _f, _f] + [_p] * 8),
-    "r3dg_ssim_forward": (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
-    "r3dg_ssim_backward": (_i, [_p, _i, _i, _i, _p, _p, _p, _f, _p]),
-    "r3dg_ssim_forward_pair": (_i, [_p, _i, _i, _i] + [_p] * 7),
-    "r3dg_ssim_backward_pair": (_i, [_p, _i, _i, _i] + [_p] * 5 + [_f, _f, _p, _p]),
-    "r3dg_stage1_pack_features": (_i, [_p, _i, _p, _p, _p, _p]),
-    "r3dg_stage1_loss": (_i, [_p, _i, _i] + [_p] * 7 + [_f] * 5 + [_p] * 6),
-    "r3dg_stage1_activate_backward": (_i, [_p, _i] + [_p] * 16),
-    "r3dg_stage2_env_backward": (_i, [_p, _i, _i, _p, _p, _p, _f, _p, _p, _i]),
-    "r3dg_adam_step": (_i, [_p, _i, _p, _f, _f, _f, _i, _f, _p]),
-    "r3dg_relight_pack_features": (_i, [_p, _i] + [_p] * 7),
-    "r3dg_relight_compose": (_i, [_p, _i, _i, _f, _f, _f, _f, _p, _p, _p, _i, _i] + [_p] * 7),
-    "r3dg_densify_accumulate": (_i, [_p, _i] + [_p] * 10),
-    "r3dg_densify_temp_bytes": (C.c_size_t, [_i]),
-    "r3dg_densify_plan": (_i, [_p, _i] + [_p] * 12),
-    "r3dg_densify_gather": (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _f]),
-    "r3dg_reset_opacity": (_i, [_p, _i, _p, _p, _p]),
-    "r3dg_knn_temp_bytes": (C.c_size_t, [_i]),
-    "r3dg_knn_dist2": (_i, [_p, _i, _p, _p, _p]),
-    "r3dg_bvh_build_temp_bytes": (C.c_size_t, [_i]),
-    "r3dg_bvh_build": (_i, [_p, _i, _p, _p, _p, _p]),
-    "r3dg_bvh_trace_opacity": (_i, [_p, C.c_int64, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "r3dg_bvh_trace_records_bytes": (C.c_size_t, [_i]),
-    "r3dg_bvh_pack_traversal": (_i, [_p, _i] + [_p] * 7),
-    "r3dg_bvh_trace_opacity_packed": (_i, [_p, C.c_int64, _i] + [_p] * 6),
-    "r3dg_bvh_trace_visits": (_i, [_p, _i, _p, C.POINTER(C.c_uint64)]),
-    "r3dg_profile_enable": (_i, [_i]),
-    "r3dg_profile_pause": (_i, [_i]),
-    "r3dg_profile_num_stages": (_i, []),
-    "r3dg_profile_stage_name": (C.c_char_p, [_i]),
-    "r3dg_profile_read": (_i, [C.POINTER(C.c_double), C.POINTER(_i)]),
-}
-
-# entry points added by later translation units register themselves here (shading, bvh, knn)
-EXTRA_SIGNATURES = {}
 
 
 def lib():
@@ -151,9 +27,7 @@ def lib():
         # device" once torch has initialised its copy)
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        sigs = dict(_SIGNATURES)
-        sigs.update(EXTRA_SIGNATURES)
-        for name, (res, args) in sigs.items():
+        for name, (res, args) in _abi.prototypes.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -161,9 +35,7 @@ def lib():
     return _lib
 
 
-# enum r3dg_option (include/r3dg_hip.h); tests/test_oracle_cpu.py checks the numbering against the header
-OPTIONS = ("TILE_ORDER", "CULL", "TILE_BINNING", "BINNING_BLOCK_K", "STAGE_SH_ROWS", "SHADE_FWD_BLOCKS_PER_CU", "TRACE_FORMULATION",
-           "TRACE_REFILL", "TRACE_NODE_WEIGHT", "TRACE_LEAF_WEIGHT", "RESERVE_CUS", "TRACE_COUNT_VISITS", "BWD_LEAN")
+OPTIONS = _abi.options       # enum r3dg_option, by index
 
 
 def set_option(name, value):
@@ -194,7 +66,7 @@ class OptionContext:
         check(lib().r3dg_context_set_option(self._h, OPTIONS.index(name), int(value)), "context_set_option(%s)" % name)
 
     def __enter__(self):
-        prev = _p()
+        prev = C.c_void_p()
         check(lib().r3dg_context_make_current(self._h, C.byref(prev)), "context_make_current")
         stack = getattr(self._tls, "prev", None)
         if stack is None:

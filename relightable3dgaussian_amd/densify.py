@@ -22,24 +22,14 @@ import os
 
 import torch
 
-from . import _lib
+from . import _abi, _lib
 
-_f, _i, _p = C.c_float, C.c_int, C.c_void_p
-
-
-class DensifyConfig(C.Structure):
-    _fields_ = [("mode", C.c_int32), ("n_split", C.c_int32), ("grad_threshold", _f), ("grad_normal_threshold", _f),
-                ("min_opacity", _f), ("weights_threshold", _f), ("dense_size", _f), ("world_size_limit", _f),
-                ("split_divisor", _f), ("max_screen_size", _f)]
-
-
-class DensifyGroup(C.Structure):
-    _fields_ = [("src_param", _p), ("src_exp_avg", _p), ("src_exp_avg_sq", _p), ("dst_param", _p),
-                ("dst_exp_avg", _p), ("dst_exp_avg_sq", _p), ("row_floats", C.c_uint32), ("role", C.c_uint32)]
-
-
-MAX_GROUPS = 20          # R3DG_DENSIFY_MAX_GROUPS (24) minus the four statistics rows prune() adds
-ROLE = {"xyz": 1, "scaling": 2}
+_K = _abi.constants
+DensifyConfig = _abi.structs["r3dg_densify_config"]
+DensifyGroup = _abi.structs["r3dg_densify_group"]
+MAX_GROUPS = _K["R3DG_DENSIFY_MAX_GROUPS"] - 4          # minus the four statistics rows prune() adds
+ROLE = {"xyz": _K["R3DG_DENSIFY_ROLE_XYZ"], "scaling": _K["R3DG_DENSIFY_ROLE_SCALING"]}
+ROLE_COPY = _K["R3DG_DENSIFY_ROLE_COPY"]
 
 
 def _need_device(t, what):
@@ -167,7 +157,7 @@ def _run(groups, stats, cfg, generator, normal_table=None):
         arr = (DensifyGroup * (len(groups) + len(carried)))()
         for j, name in enumerate(carried):
             arr[len(groups) + j] = DensifyGroup(getattr(stats, name).data_ptr() if P else None, None, None,
-                                                getattr(new_stats, name).data_ptr(), None, None, 1, 0)
+                                                getattr(new_stats, name).data_ptr(), None, None, 1, ROLE_COPY)
         for j, (name, g) in enumerate(groups.items()):
             p = g["param"]
             row = int(p[0].numel()) if P else int(torch.Size(p.shape[1:]).numel())
@@ -179,7 +169,7 @@ def _run(groups, stats, cfg, generator, normal_table=None):
             arr[j] = DensifyGroup(p.data_ptr(), g["exp_avg"].data_ptr() if has_m else None,
                                   g["exp_avg_sq"].data_ptr() if has_m else None, dst["param"].data_ptr(),
                                   dst["exp_avg"].data_ptr() if has_m else None,
-                                  dst["exp_avg_sq"].data_ptr() if has_m else None, max(row, 1), ROLE.get(name, 0))
+                                  dst["exp_avg_sq"].data_ptr() if has_m else None, max(row, 1), ROLE.get(name, ROLE_COPY))
         st = L.r3dg_densify_gather(
             _lib.current_stream(), n_out, rowmap[0].data_ptr(), rowmap[1].data_ptr(), len(arr),
             C.cast(arr, C.c_void_p), xyz.data_ptr() if P else None, scaling.data_ptr() if P else None,

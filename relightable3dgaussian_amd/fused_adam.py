@@ -4,19 +4,16 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _abi, _lib
 
-
-class AdamGroup(C.Structure):
-    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
-                ("n", C.c_uint64), ("lr", C.c_float), ("lr_tail", C.c_float), ("period", C.c_uint32), ("split", C.c_uint32)]
+AdamGroup = _abi.structs["r3dg_adam_group"]
 
 
 class FusedAdam:
     """torch.optim.Adam semantics (no weight decay / amsgrad) over a fixed set of tensors, one kernel launch per step.
     `groups`: list of dicts {param, lr, lr_tail=None, period=0, split=0}; elements whose index modulo `period` is >= `split`
     train with `lr_tail`, resolved HERE (None -> lr).  A group with period 0 has one rate: the kernel never reads its `lr_tail`."""
-    MAX_GROUPS = 16
+    MAX_GROUPS = _abi.constants["R3DG_ADAM_MAX_GROUPS"]
 
     def __init__(self, groups, betas=(0.9, 0.999), eps=1e-15):
         if len(groups) > self.MAX_GROUPS:

@@ -6,9 +6,9 @@ import os
 
 import torch
 
-from . import _lib, rasterizer_ops
+from . import _abi, _lib, rasterizer_ops
 
-SUM_SLOTS = 32           # R3DG_SUM_SLOTS (include/r3dg_hip.h): floats per scalar accumulator of the glue kernels
+SUM_SLOTS = _abi.constants["R3DG_SUM_SLOTS"]           # floats per scalar accumulator of the glue kernels
 
 
 def _in_context(method):

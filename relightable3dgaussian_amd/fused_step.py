@@ -38,6 +38,7 @@ from .fused_adam import AdamGroup, FusedAdam                                    
 from .fused_base import _STREAMS, SUM_SLOTS, FusedStepBase, _in_context, _world_of, grad_slab, learning_rates, shared_stream  # noqa: F401
 from .fused_stage1 import FusedStage1Step                                                 # noqa: F401  (re-exported)
 from .grad_comm import BucketComm
+from .shading_ops import LEAVE_ROOM, TRAIN_OUTPUTS
 from .train_step import FROZEN_GEOMETRY_GROUPS, LAMBDA_DSSIM, STAGE2_WEIGHTS, update_visibility
 
 PARAM_NAMES = ("xyz", "normal", "scaling", "rotation", "opacity", "shs", "base_color", "roughness", "incidents", "env")
@@ -409,7 +410,7 @@ class FusedStage2Step(FusedStepBase):
                 self.a_viewdirs.data_ptr(), self._incidents.data_ptr(), env_c.data_ptr(), He, We, None,
                 self.visibility.data_ptr(), self.incident_dirs.data_ptr(),
                 None if self._uniform_area is not None else self.incident_areas.data_ptr(), self._uniform_area or 0.0,
-                taps.data_ptr(), 1 | (4 if v.order_stream is not None else 0),     # train outputs | leave room
+                taps.data_ptr(), TRAIN_OUTPUTS | (LEAVE_ROOM if v.order_stream is not None else 0),
                 self.shade_out.data_ptr()), "shade_forward")
         if self._frs is not None and self._listed_stream() is not None:
             _lib.stream_wait(v.main, self._listed_stream())

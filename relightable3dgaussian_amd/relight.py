@@ -207,8 +207,8 @@ class RelightRenderer:
             self.a_viewdirs.data_ptr(), self.incidents.data_ptr(), self.envmap.data_ptr(), He, We, _lib.ptr(tr),
             self.visibility.data_ptr(), self.incident_dirs.data_ptr(),
             None if self._uniform_area is not None else self.incident_areas.data_ptr(), self._uniform_area or 0.0,
-            # 2 = R3DG_SHADE_TAPS_ARE_RADIANCE; no cache (a light that changes every frame): lookup in the kernel
-            taps.data_ptr() if taps is not None else None, 2 if taps is not None else 0,
+            # no cache (a light that changes every frame): lookup in the kernel
+            taps.data_ptr() if taps is not None else None, shading_ops.TAPS_ARE_RADIANCE if taps is not None else 0,
             self.shade_out.data_ptr()), "shade_forward")
 
     @torch.no_grad()

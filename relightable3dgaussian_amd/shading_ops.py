@@ -10,9 +10,14 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _abi, _lib
 
 NOUT = 19
+# the `flags` of r3dg_shade_forward_cached / r3dg_shade_frs_forward, and the rotate_stream that is no stream
+_K = _abi.constants
+TRAIN_OUTPUTS, TAPS_ARE_RADIANCE = _K["R3DG_SHADE_TRAIN_OUTPUTS"], _K["R3DG_SHADE_TAPS_ARE_RADIANCE"]
+LEAVE_ROOM, ROTATED = _K["R3DG_SHADE_LEAVE_ROOM"], _K["R3DG_SHADE_ROTATED"]
+NO_ROTATION_BACK = ctypes.c_void_p(_K["R3DG_SHADE_NO_ROTATION_BACK"])
 
 
 def _c(t):
@@ -63,7 +68,8 @@ def shade_forward(base_color, roughness, normals, viewdirs, incidents, env, visi
                                          tr.data_ptr() if tr is not None else None, t[6].data_ptr(), t[7].data_ptr(),
                                          None if uniform_area is not None else t[8].data_ptr(),
                                          float(uniform_area or 0.0), taps.data_ptr() if taps is not None else None,
-                                         (1 if train_outputs else 0) | (2 if taps_are_radiance else 0), out.data_ptr())
+                                         (TRAIN_OUTPUTS if train_outputs else 0) | (TAPS_ARE_RADIANCE if taps_are_radiance else 0),
+                                         out.data_ptr())
     _lib.check(st, "shade_forward")
     return out
 
@@ -299,7 +305,8 @@ class FixedRaySet:
         head, _keep = self._common(base_color, roughness, normals, viewdirs, incidents, env, visibility, uniform_area)
         with torch.cuda.device(base_color.device):
             st = _lib.lib().r3dg_shade_frs_forward(_lib.current_stream(), *head, self.cprime.data_ptr(),
-                                                   1 | (4 if leave_room else 0) | (8 if rotated else 0), out.data_ptr(),
+                                                   TRAIN_OUTPUTS | (LEAVE_ROOM if leave_room else 0) | (ROTATED if rotated else 0),
+                                                   out.data_ptr(),
                                                    listed_stream.cuda_stream if listed_stream is not None else None,
                                                    _lib.ptr(feature_rows))
         _lib.check(st, "shade_frs_forward")
@@ -329,7 +336,7 @@ class FixedRaySet:
                 d_base.data_ptr(), d_rough.data_ptr(), d_view.data_ptr(), d_inc.data_ptr(), d_env.data_ptr(),
                 block_absmax.data_ptr() if block_absmax is not None else None,
                 block_absmax.numel() if block_absmax is not None else 0,
-                (ctypes.c_void_p(-1) if not rotation_back else
+                (NO_ROTATION_BACK if not rotation_back else
                  (rotate_stream.cuda_stream if rotate_stream is not None else None)))
         _lib.check(st, "shade_frs_backward")
         return d_base, d_rough, d_view, d_inc, d_env

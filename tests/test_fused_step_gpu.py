@@ -370,7 +370,7 @@ def test_fused_stage1_training_with_densification():
 def test_ssim_kernels_match_reference_formula(H, W):
     """r3dg_ssim_forward/backward vs the conv2d restatement of utils/loss_utils.py:20-63 under autograd."""
     import ctypes as C
-    from relightable3dgaussian_amd import _lib
+    from relightable3dgaussian_amd import _lib, fused_base
     from relightable3dgaussian_amd.train_step import ssim
     L = _lib.lib()
     g = torch.Generator().manual_seed(H * 100 + W)
@@ -380,7 +380,7 @@ def test_ssim_kernels_match_reference_formula(H, W):
     val = ssim(xr, y)
     val.backward()
     part = torch.empty(3, 3, H, W, device=DEV)
-    total = torch.zeros(32, device=DEV)              # R3DG_SUM_SLOTS floats per accumulator
+    total = torch.zeros(fused_base.SUM_SLOTS, device=DEV)    # R3DG_SUM_SLOTS floats per accumulator
     grad = torch.empty(3, H, W, device=DEV)
     st = _lib.current_stream()
     _lib.check(L.r3dg_ssim_forward(st, W, H, 3, x.data_ptr(), y.data_ptr(), part.data_ptr(), total.data_ptr()), "f")
@@ -520,7 +520,7 @@ def test_folded_launches_equal_the_launches_they_replace():
     sRGB-mapped PBR image, pixel by pixel) against the separate launches / torch: same bits from the shared device code, the softplus
     within an ulp of torch.nn.functional.softplus (direct_light_map.py:18-23)."""
     import torch.nn.functional as F
-    from relightable3dgaussian_amd import _lib, rasterizer_ops
+    from relightable3dgaussian_amd import _lib, fused_base, rasterizer_ops
     params, ref, fused, cam, bg, gt = _setup(P=3001, res=150, K=8, seed=5)
     L = _lib.lib()
     S = lambda: _lib.current_stream()
@@ -560,7 +560,7 @@ def test_folded_launches_equal_the_launches_they_replace():
     outs_b = [torch.full(s, float("nan"), device=DEV) for s in shapes]
     da, db = d_env.clone(), d_env.clone()
     ga, gb = torch.full_like(env_c, float("nan")), torch.full_like(env_c, float("nan"))
-    tva, tvb = torch.zeros(32, device=DEV), torch.zeros(32, device=DEV)
+    tva, tvb = torch.zeros(fused_base.SUM_SLOTS, device=DEV), torch.zeros(fused_base.SUM_SLOTS, device=DEV)
     run("r3dg_stage2_activate_backward", (), outs_a, None, None, None)
     _lib.check(L.r3dg_stage2_env_backward(S(), He, We, fused.env.data_ptr(), env_c.data_ptr(), da.data_ptr(), 0.37, ga.data_ptr(),
                                           tva.data_ptr(), 1), "env_backward")
@@ -848,7 +848,7 @@ def test_fused_smoothness_kernel_equals_the_three_pass_formulation(H, W, weights
     (tests/test_reference_pipeline_gpu.py::test_stage2_syn4_objective_matches_the_reference_python).  The per-pixel arithmetic
     is the same, expression for expression: gradients bit-identical, the three sums up to the order of their float atomics;
     image sizes that are not multiples of the strip (one strip, three strips, a last strip of one column), every border, every subset of the three terms."""
-    from relightable3dgaussian_amd import _lib
+    from relightable3dgaussian_amd import _lib, fused_base
     L = _lib.lib()
     g = torch.Generator().manual_seed(H * 1000 + W)
     N = H * W
@@ -864,7 +864,7 @@ def test_fused_smoothness_kernel_equals_the_three_pass_formulation(H, W, weights
     for fused in (False, True):
         d_op = torch.full((1, H, W), 0.25, device=DEV)
         d_f = torch.full((16, H, W), -3.0, device=DEV)
-        sums = torch.zeros(3, 32, device=DEV)
+        sums = torch.zeros(3, fused_base.SUM_SLOTS, device=DEV)
         args = (W, H, opacity.data_ptr(), feature.data_ptr(), n_contrib.data_ptr())
         if fused:
             _lib.check(L.r3dg_stage2_smooth_fused(s, *args, gt.data_ptr(), _lib.ptr(mask), wb, wr, wl, acc_normal, d_op.data_ptr(),

@@ -222,6 +222,8 @@ def test_hip_library_exports_every_declared_symbol():
             names |= set(re.findall(r"\b(r3dg_\w+)\s*\(", src))
     names.discard("r3dg_alloc_fn")
     assert len(names) >= 15
+    from relightable3dgaussian_amd import _abi
+    assert set(_abi.prototypes) == names                    # what lib() binds is what the headers declare, no more, no less
     L = C.CDLL(_lib.LIB_PATH)
     missing = [n for n in sorted(names) if not hasattr(L, n)]
     assert not missing, "declared in include/*.h but not exported: %s" % missing
@@ -232,7 +234,10 @@ def test_hip_library_exports_every_declared_symbol():
     hdr = open(os.path.join(root, "include", "r3dg_hip.h")).read()
     enum = re.search(r"enum r3dg_option \{(.*?)\};", hdr, re.S).group(1)
     declared = [n[len("R3DG_OPT_"):] for n in re.findall(r"\b(R3DG_OPT_\w+)\b", re.sub(r"/\*.*?\*/", "", enum, flags=re.S))]
-    assert declared[-1] == "COUNT" and tuple(declared[:-1]) == _lib.OPTIONS
+    # (_lib.OPTIONS is read from the header too: the literal keeps this from comparing the header with itself)
+    assert declared[-1] == "COUNT" and tuple(declared[:-1]) == _lib.OPTIONS == (
+        "TILE_ORDER", "CULL", "TILE_BINNING", "BINNING_BLOCK_K", "STAGE_SH_ROWS", "SHADE_FWD_BLOCKS_PER_CU", "TRACE_FORMULATION",
+        "TRACE_REFILL", "TRACE_NODE_WEIGHT", "TRACE_LEAF_WEIGHT", "RESERVE_CUS", "TRACE_COUNT_VISITS", "BWD_LEAN")
     assert _lib.get_option("TILE_BINNING") == 2 and _lib.get_option("CULL") == 1 and _lib.get_option("RESERVE_CUS") == 0
     _lib.set_option("RESERVE_CUS", 8)
     assert _lib.get_option("RESERVE_CUS") == 8
