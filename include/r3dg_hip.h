@@ -277,7 +277,7 @@ int r3dg_shade_forward_split(void* stream, int P, int K, const int32_t* d_perm, 
                              const float* d_roughness, const float* d_normals, const float* d_viewdirs, const float* d_lt,
                              const float* d_vis_t, const float* d_consts, const float* d_zsamples,
                              const float* d_env_transform, const float* d_env_footprints, int He, int We, float* d_out);
-/* ---- the same integral over a FIXED RAY SET (csrc/shading_frs.hpp) -----------------------------------------------------------
+/* ---- the same integral over a FIXED RAY SET (csrc/shading_frs.hip) -----------------------------------------------------------
  * For callers whose cached directions are the Fibonacci set rotated to each Gaussian's normal, d_k = normalize(R(n) z_k) --
  * what GaussianModel.update_visibility produces (scene/gaussian_model.py:312-342 -> utils/graphics_utils.py:9-37,
  * rotation_between_z utils/sh_utils.py:36-68).  Then NOTHING per sample depends on a stored direction (SURVEY section 8f n2:

@@ -243,7 +243,7 @@ def _kernel_names(stage):
     """Kernel(s) a profile stage times, dominant first (names as tools/pmc_*.py shorten them)."""
     return {"sort_pairs": ["tile_sort_small_kernel", "partition_scatter_kernel"],
             "duplicate_with_keys": ["tile_emit_kernel", "duplicate_with_keys_kernel"],      # (stage name kept from K5)
-            # (the training iteration runs the fixed-ray-set kernels, csrc/shading_frs.hpp; the row kernel is what a caller with
+            # (the training iteration runs the fixed-ray-set kernels, csrc/shading_frs.hip; the row kernel is what a caller with
             # other caches gets)
             "shade_forward": ["shade_forward_frs_kernel", "shade_forward_row_kernel"],
             "shade_backward": ["shade_backward_frs_kernel", "shade_backward_kernel"],

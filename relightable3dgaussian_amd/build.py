@@ -23,14 +23,17 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno
           "-I", os.path.join(os.path.dirname(HERE), "include")]
 # Per-file extra flags.  rasterizer_preprocess.hip decides integer outputs (radii, tile rects, sort keys) from
 # fp32 math and must match the CPU oracle bit for bit -> no fused multiply-add contraction there.
+# shading units: VALU-bound transcendental-heavy float math; fp32 tolerance is 1e-4, so reciprocal/sqrt approximations
+# (v_rcp_f32, v_sqrt_f32: 1 ulp) replace the IEEE division/sqrt expansions
+SHADING_FLAGS = ["-ffast-math", "-fno-slp-vectorize"]
 EXTRA = {
     "rasterizer_preprocess.hip": ["-ffp-contract=off"],
     "bvh.hip": ["-ffp-contract=off"],
     "simple_knn.hip": ["-ffp-contract=off"],
     "densify.hip": ["-ffp-contract=off"],         # clone / split / prune decisions are fp32 comparisons
-    # shading: VALU-bound transcendental-heavy float math; fp32 tolerance is 1e-4, so reciprocal/sqrt approximations
-    # (v_rcp_f32, v_sqrt_f32: 1 ulp) replace the IEEE division/sqrt expansions
-    "shading.hip": ["-ffast-math", "-fno-slp-vectorize"],
+    "shading.hip": SHADING_FLAGS,
+    "shading_frs.hip": SHADING_FLAGS,
+    "shading_relight.hip": SHADING_FLAGS,
 }
 
 

@@ -1178,10 +1178,7 @@ void bvh_trace_opacity_packed(hipStream_t s, int num_rays, int P, void* records,
     int* queues = reinterpret_cast<int*>(rec + (size_t)P * 128);               // 8 x 64 bytes behind the records
     const int nblk = (num_rays + 255) / 256, chunk = (nblk + 7) / 8;
     if (opt(R3DG_OPT_TRACE_FORMULATION) >= 3 || opt(R3DG_OPT_TRACE_FORMULATION) < 2) {
-        int dev = 0, cus = 256;
-        R3DG_HIP(hipGetDevice(&dev));
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        cus = cus > opt(R3DG_OPT_RESERVE_CUS) ? cus - opt(R3DG_OPT_RESERVE_CUS) : 1;                    // leave CUs to a concurrent collective
+        const int cus = persistent_cus();                                       // leaves CUs to a concurrent collective
         R3DG_HIP(hipMemsetAsync(queues, 0, 8 * 64, s));
         const int cap = cus * 8;                                                // 8 waves per SIMD, all resident
         const int grid = chunk * 8 < cap ? chunk * 8 : cap;

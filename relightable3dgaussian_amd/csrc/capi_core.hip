@@ -66,6 +66,14 @@ int opt(int option)
     return (g_process_options.set_mask >> option) & 1u ? g_process_options.value[option] : kOptions[option].def;
 }
 
+int persistent_cus()
+{
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus > opt(R3DG_OPT_RESERVE_CUS) ? cus - opt(R3DG_OPT_RESERVE_CUS) : 1;
+}
+
 namespace {
 struct ScratchBuf { void* p = nullptr; size_t cap = 0; };
 std::mutex g_scratch_mu;

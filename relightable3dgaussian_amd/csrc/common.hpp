@@ -98,6 +98,15 @@ __device__ __forceinline__ float wave_sum(float v)
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// Sum over a 256-thread block (four waves); s_part: 4 floats of LDS.  Valid in every thread; ends in a barrier-free read, so the
+// caller synchronises before reusing s_part.
+__device__ __forceinline__ float block_sum_256(float v, float* s_part)
+{
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return s_part[0] + s_part[1] + s_part[2] + s_part[3];
+}
 // Full-wave sum that stays in the VALU (DPP row shifts + row broadcasts, no LDS-crossbar shuffles): the total is
 // valid in lane 63 ONLY.
 __device__ __forceinline__ float wave_sum_to_lane63(float v)
@@ -119,6 +128,9 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor((int)v, o, 64);
     return v;
 }
+// exp(x) of both tile kernels.  v_exp_f32 is 2^x: exp(x) = 2^(x*log2(e)); |x| < ~6 wherever the result matters (alpha >= 1/255)
+__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
+
 // Conservative sub-tile cull used by both tile kernels: can the Gaussian (mean m, conic (a, b, c), opacity op) reach
 // alpha >= 1/255 at ANY pixel centre of the box [x0,x1] x [y0,y1]?  alpha = op * exp(-q/2) with the convex quadratic
 // q(d) = a dx^2 + 2 b dx dy + c dy^2, so it is enough to bound q from below over the box: 0 if the mean is inside,

@@ -10,6 +10,10 @@ namespace r3dg {
 // the constant the non-phased kernel is compiled with AND the default of R3DG_OPT_TRACE_REFILL (capi_core.hip kOptions).
 constexpr int REFILL_MIN_IDLE = 16;      // refill when at least this many lanes are idle (or the whole wave is)
 
+// CUs a persistent grid may fill: the device's CUs minus the R3DG_OPT_RESERVE_CUS left to a collective running beside it on
+// another stream, at least 1 (capi_core.hip; library-internal, not part of the exported surface)
+__attribute__((visibility("hidden"))) int persistent_cus();
+
 void release_gradient_records();        // rasterizer_render_bwd.hip; the device is idle when r3dg_release_scratch calls it
 void launch_mark_visible(hipStream_t s, int P, const float* means3D, const float* vm, uint8_t* present);
 void launch_preprocess(hipStream_t s, int P, int D, int M, const float* means3D, const float* scales, float scale_modifier,

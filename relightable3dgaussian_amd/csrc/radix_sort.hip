@@ -628,11 +628,7 @@ void launch_tile_sort(hipStream_t s, int T, const uint32_t* tile_order, const ui
     const uint2* rg = (const uint2*)ranges;
     // persistent grid: 2 x 1024 threads fill a CU (most workgroups exit at once when few tiles are long); the device's CU count
     // minus the CUs left to a collective
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const int reserve = opt(R3DG_OPT_RESERVE_CUS);
-    const int grid = 2 * (cus > reserve ? cus - reserve : 1);
+    const int grid = 2 * persistent_cus();
     // (Round 5, measured and not kept: the long tiles' kernel on a side stream of the library beside the small tiles' kernel -- the
     // two sort disjoint tiles.  Beside each other the long kernel takes 82 us instead of 30, the pair ends where the sequence did:
     // 772-774 against 776-777 it/s.  One stream.)

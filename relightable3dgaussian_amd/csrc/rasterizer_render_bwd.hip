@@ -27,8 +27,6 @@ namespace r3dg {
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ float fast_exp_b(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-
 // self-test kernel: out[lane] = transpose_reduce of in[lane*N + k]; host compares against a plain sum
 template <int N, bool DPP>
 __global__ void transpose_reduce_selftest_kernel(const float* __restrict__ in, float* __restrict__ out,
@@ -301,7 +299,7 @@ render_backward_wave_kernel(const uint2* __restrict__ ranges, const uint32_t* __
             const uint32_t front = __float_as_uint(g1.z);
             const float dx = g0.x - pxf, dy = g0.y - pyf;
             const float power = -0.5f * (g0.z * dx * dx + g1.x * dy * dy) - g0.w * dx * dy;
-            const float Gv0 = fast_exp_b(power);
+            const float Gv0 = fast_exp(power);
             float al = fminf(0.99f, g1.y * Gv0);
             // reference: skip while contributor >= last_contributor, power > 0, alpha < 1/255
             if (!(front < lastc) || power > 0.0f || al < 1.0f / 255.0f) al = 0.f;
@@ -569,7 +567,7 @@ render_backward_features_kernel(const uint2* __restrict__ ranges, const uint32_t
             const uint32_t front = __float_as_uint(g1.z);
             const float dx = g0.x - pxf, dy = g0.y - pyf;
             const float power = -0.5f * (g0.z * dx * dx + g1.x * dy * dy) - g0.w * dx * dy;
-            float a = fminf(0.99f, g1.y * fast_exp_b(power));
+            float a = fminf(0.99f, g1.y * fast_exp(power));
             if (!(front < lastc) || power > 0.0f || a < 1.0f / 255.0f) a = 0.f;
             if (__ballot(a != 0.f) == 0ull) continue;
             // back to front: T before this Gaussian = T after it / (1 - alpha)   (backward.cu:533)

@@ -18,12 +18,6 @@
 
 namespace r3dg {
 
-__device__ __forceinline__ float fast_exp(float x)
-{
-    // v_exp_f32 is 2^x: exp(x) = 2^(x*log2(e)); |x| < ~6 wherever the result matters (alpha >= 1/255)
-    return __builtin_amdgcn_exp2f(x * 1.4426950408889634f);
-}
-
 // One wave = one workgroup = one 8x8 pixel block of a 16x16 tile (round 3).  Rounds 1-2 ran four waves per tile over a shared
 // staging buffer: 256 entries staged by all, two workgroup barriers per round, every wave waiting for the one whose block has the
 // most candidates -- PMC: the VALU the busiest unit at 54 %, the waves half their life in s_waitcnt, 2.8 resident per SIMD

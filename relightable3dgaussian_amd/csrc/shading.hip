@@ -1,4 +1,7 @@
-// Fused per-Gaussian shading integral (the LIVE stage-2 model) for gfx950, forward and backward.
+// Fused per-Gaussian shading integral (the LIVE stage-2 model) for gfx950, forward and backward: the GENERAL kernels (row
+// forward, 16-lane backward, prepare / pad / build-taps, max |upstream gradient|) and their launchers.  The fixed-ray-set
+// kernels are shading_frs.hip, the relight caches shading_relight.hip; shared device helpers shading_lookup.hpp /
+// shading_sample.hpp, shared host declarations shading_host.hpp.
 // Reference semantics: rendering_equation neilf.py:339-371, GGX_specular :374-407, eval_sh sh_utils.py:71-128,
 // DirectLightMap.direct_light direct_light_map.py:70-83 / EnvLight.direct_light envmap.py:35-53.
 //
@@ -17,228 +20,18 @@
 //     read back as broadcasts;
 //   * backward only: record + samples of the wave's NEXT 64-sample block arrive by LDS-DMA (global_load_lds_dwordx4),
 //     double buffered, while the current block is computed (three passes per block, 12 parked floats per lane).
-#include "launchers.hpp"
+#include "shading_host.hpp"
 #include <cmath>
 #include <cstdlib>
 #include <map>
 #include <mutex>
 #include <stdexcept>
-#include <tuple>
 #include "wave_reduce.hpp"
-#include "shading_math.hpp"
+#include "shading_sample.hpp"
 
 namespace r3dg {
 
 constexpr int SHADE_WAVES = 4;               // Gaussians in flight per block
-constexpr int ENV_LDS_MAX = 12288;           // floats (48 KB) -- larger maps are sampled from global/L2
-
-// acos / atan2 for the lat-long lookup, branch-free (Cephes single-precision minimax polynomials, ~1 ulp like the libm
-// versions they replace at about a third of the instructions: the lookup runs once per cached sample, forward and
-// backward).  acos: |x| <= 0.5 -> pi/2 - asin(x), else 2 asin(sqrt((1-|x|)/2)) reflected; atan: argument reduced to
-// [0, tan(pi/8)] by the octant identities.
-__device__ __forceinline__ float fast_acosf(float x)
-{
-    const float ax = fabsf(x);
-    const bool big = ax > 0.5f;
-    const float z = big ? 0.5f * (1.0f - ax) : x * x;
-    const float s = big ? sqrtf(z) : ax;
-    float p = 4.2163199048e-2f;
-    p = p * z + 2.4181311049e-2f;
-    p = p * z + 4.5470025998e-2f;
-    p = p * z + 7.4953002686e-2f;
-    p = p * z + 1.6666752422e-1f;
-    const float a = s + s * z * p;                         // asin(s)
-    const float pos = big ? 2.0f * a : 1.5707963267948966f - a;      // acos(|x|)
-    return x >= 0.f ? pos : 3.14159265358979323846f - pos;
-}
-
-__device__ __forceinline__ float fast_atan2f(float y, float x)
-{
-    const float ax = fabsf(x), ay = fabsf(y);
-    const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-    float a = mx > 0.f ? mn / mx : 0.f;                    // in [0,1]
-    const bool hi = a > 0.4142135623730950f;               // tan(pi/8)
-    a = hi ? (a - 1.0f) / (a + 1.0f) : a;
-    const float z = a * a;
-    float p = 8.05374449538e-2f;
-    p = p * z - 1.38776856032e-1f;
-    p = p * z + 1.99777106478e-1f;
-    p = p * z - 3.33329491539e-1f;
-    float r = p * z * a + a;
-    r = hi ? r + 0.7853981633974483f : r;
-    r = ay > ax ? 1.5707963267948966f - r : r;
-    r = x < 0.f ? 3.14159265358979323846f - r : r;
-    return __uint_as_float(__float_as_uint(r) | (__float_as_uint(y) & 0x80000000u));     // copysign: atan2(-0, x<0) = -pi
-}
-
-struct EnvTap {
-    int idx[4];      // texel index (y*We + x), -1 when out of range (zero padding)
-    float w[4];
-};
-
-// lat-long lookup coordinates + bilinear taps (direct_light_map.py:70-83; grid_sample align_corners=True, zeros)
-__device__ __forceinline__ EnvTap env_taps(float dx, float dy, float dz, const float* __restrict__ tr, int He, int We)
-{
-    if (tr != nullptr) {
-        const float tx = dx * tr[0] + dy * tr[1] + dz * tr[2];
-        const float ty = dx * tr[3] + dy * tr[4] + dz * tr[5];
-        const float tz = dx * tr[6] + dy * tr[7] + dz * tr[8];
-        dx = tx; dy = ty; dz = tz;
-    }
-    const float phi = fast_acosf(dz) - 1e-6f;
-    const float theta = fast_atan2f(dy, dx);
-    const float qy = (phi / kPi) * 2.f - 1.f;
-    const float qx = -theta / kPi;
-    const float ix = (qx + 1.f) * 0.5f * (float)(We - 1);
-    const float iy = (qy + 1.f) * 0.5f * (float)(He - 1);
-    const float x0f = floorf(ix), y0f = floorf(iy);
-    const float wx1 = ix - x0f, wy1 = iy - y0f, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
-    const int x0 = (int)x0f, y0 = (int)y0f;
-    EnvTap t;
-    const int xs[2] = {x0, x0 + 1}, ys[2] = {y0, y0 + 1};
-    const float wxs[2] = {wx0, wx1}, wys[2] = {wy0, wy1};
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++) {
-            const bool ok = xs[b] >= 0 && xs[b] <= We - 1 && ys[a] >= 0 && ys[a] <= He - 1;
-            t.idx[a * 2 + b] = ok ? ys[a] * We + xs[b] : -1;
-            t.w[a * 2 + b] = wys[a] * wxs[b];
-        }
-    return t;
-}
-
-struct PackedTap {           // 12 bytes per cached sample
-    uint32_t xy;             // (x0 + 1) | (y0 + 1) << 16, (x0, y0) = floor of the lat-long pixel coordinate (>= -1)
-    float wx1, wy1;          // bilinear weights of column x0 + 1 / row y0 + 1
-};
-
-__device__ __forceinline__ PackedTap make_tap(float dx, float dy, float dz, const float* __restrict__ tr, int He, int We)
-{
-    if (tr != nullptr) {
-        const float tx = dx * tr[0] + dy * tr[1] + dz * tr[2];
-        const float ty = dx * tr[3] + dy * tr[4] + dz * tr[5];
-        const float tz = dx * tr[6] + dy * tr[7] + dz * tr[8];
-        dx = tx; dy = ty; dz = tz;
-    }
-    const float phi = fast_acosf(dz) - 1e-6f;
-    const float theta = fast_atan2f(dy, dx);
-    const float qy = (phi / kPi) * 2.f - 1.f;
-    const float qx = -theta / kPi;
-    const float ix = (qx + 1.f) * 0.5f * (float)(We - 1);
-    const float iy = (qy + 1.f) * 0.5f * (float)(He - 1);
-    const float x0f = floorf(ix), y0f = floorf(iy);
-    PackedTap t;
-    t.wx1 = ix - x0f;
-    t.wy1 = iy - y0f;
-    const int x0 = max((int)x0f, -1), y0 = max((int)y0f, -1);
-    t.xy = (uint32_t)(x0 + 1) | ((uint32_t)(y0 + 1) << 16);
-    return t;
-}
-
-// cached lookup record -> the four (texel, weight) taps of env_taps (texel -1 = zero padding)
-__device__ __forceinline__ EnvTap taps_from_packed(const PackedTap& t, int He, int We)
-{
-    const int x0 = (int)(t.xy & 0xffffu) - 1, y0 = (int)(t.xy >> 16) - 1;
-    const float wx[2] = {1.f - t.wx1, t.wx1}, wy[2] = {1.f - t.wy1, t.wy1};
-    EnvTap o;
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++) {
-            const int x = x0 + b, y = y0 + a;
-            const bool ok = x >= 0 && x <= We - 1 && y >= 0 && y <= He - 1;
-            o.idx[a * 2 + b] = ok ? __mul24(y, We) + x : -1;
-            o.w[a * 2 + b] = wy[a] * wx[b];
-        }
-    return o;
-}
-
-struct SampleFwd {
-    float local[3], glob[3], lin[3], transport[3];
-    float spec, ndi, area_ndi;
-    // intermediates kept for the backward
-    float Y[16], shsum[3];
-    float L[3], Hh[3], ulen, NoL, NoH, VoH, rawNoH, rawVoH, nom0, nom1, nom2, nomr, frac0, p2;
-    EnvTap taps;
-    float vis;
-};
-
-// Layout of the per-wave uniform record u[64]: 0..47 SH coefficients (i*3+c), 48..50 albedo, 51 roughness,
-// 52..54 normal, 55..57 view direction, 58..60 dL_dpbr, 61..63 dL_ddiffuse_light (the last six only in the backward).
-template <bool ENV_LDS, bool HAVE_SHSUM = false, bool HAVE_TAP = false>
-__device__ __forceinline__ void shade_sample(SampleFwd& s, const GaussFwd& G, const float* sh /*[48] in LDS, zero padded*/,
-                                             int M, float dx, float dy, float dz, float vis, float area,
-                                             const float* __restrict__ env, const float* s_env,
-                                             const float* __restrict__ tr, int He, int We, const PackedTap* cached = nullptr)
-{
-    // environment light (global) * visibility
-    if (HAVE_TAP) s.taps = taps_from_packed(*cached, He, We);
-    else s.taps = env_taps(dx, dy, dz, tr, He, We);
-    s.vis = vis;
-    float e[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-        if (s.taps.idx[t] >= 0) {
-            float3 px;
-            if (ENV_LDS) {
-                const float* q = s_env + 3 * s.taps.idx[t];
-                px = make_float3(q[0], q[1], q[2]);
-            } else {
-                // large maps live in L2: one 12-byte load per tap (global_load_dwordx3), not three 4-byte ones
-                px = *reinterpret_cast<const float3*>(env + 3 * (size_t)s.taps.idx[t]);
-            }
-            e[0] += px.x * s.taps.w[t];
-            e[1] += px.y * s.taps.w[t];
-            e[2] += px.z * s.taps.w[t];
-        }
-    }
-    // local incident light: max(SH(d), 0)
-    {
-        float acc[3];
-        if (HAVE_SHSUM) {                        // the caller evaluated the SH sum in an earlier pass (passed via s.shsum)
-            acc[0] = s.shsum[0]; acc[1] = s.shsum[1]; acc[2] = s.shsum[2];
-        } else {
-            sh_basis16(dx, dy, dz, M, s.Y);      // Y[i] = 0 for i >= M, and the LDS record is zero padded
-            sh_local_sum(sh, s.Y, acc);
-        }
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            s.shsum[c] = acc[c];
-            s.local[c] = fmaxf(acc[c], 0.f);
-            s.glob[c] = e[c] * vis;
-            s.lin[c] = s.local[c] + s.glob[c];
-        }
-    }
-    s.ndi = fmaxf(G.n[0] * dx + G.n[1] * dy + G.n[2] * dz, 0.f);
-    s.area_ndi = area * s.ndi;
-    // GGX specular (neilf.py:374-407)
-    const float dlen = fmaxf(sqrtf(dx * dx + dy * dy + dz * dz), 1e-12f);
-    s.L[0] = dx / dlen; s.L[1] = dy / dlen; s.L[2] = dz / dlen;
-    float u[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) u[c] = (s.L[c] + G.V[c]) / 2.0f;
-    s.ulen = fmaxf(sqrtf(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]), 1e-12f);
-#pragma unroll
-    for (int c = 0; c < 3; c++) s.Hh[c] = u[c] / s.ulen;
-    s.NoL = fminf(fmaxf(G.N[0] * s.L[0] + G.N[1] * s.L[1] + G.N[2] * s.L[2], 1e-6f), 1.f);
-    s.rawNoH = G.N[0] * s.Hh[0] + G.N[1] * s.Hh[1] + G.N[2] * s.Hh[2];
-    s.NoH = fminf(fmaxf(s.rawNoH, 1e-6f), 1.f);
-    s.rawVoH = G.V[0] * s.Hh[0] + G.V[1] * s.Hh[1] + G.V[2] * s.Hh[2];
-    s.VoH = fminf(fmaxf(s.rawVoH, 1e-6f), 1.f);
-    const float FMi = (-5.55473f * s.VoH - 6.98316f) * s.VoH;
-    s.p2 = exp2f(FMi);
-    s.frac0 = 0.04f + 0.96f * s.p2;
-    const float frac = s.frac0 * G.a2;
-    s.nom0 = s.NoH * s.NoH * (G.a2 - 1.f) + 1.f;
-    s.nom1 = G.NoV * (1.f - G.kk) + G.kk;
-    s.nom2 = s.NoL * (1.f - G.kk) + G.kk;
-    s.nomr = 4.f * kPi * s.nom0 * s.nom0 * s.nom1 * s.nom2;
-    const float nom = fminf(fmaxf(s.nomr, 1e-6f), 4.f * kPi);
-    s.spec = frac / nom;
-#pragma unroll
-    for (int c = 0; c < 3; c++) s.transport[c] = s.lin[c] * s.area_ndi;
-}
 
 // ---- 16 lanes per Gaussian, 4 Gaussians per wave ----------------------------------------------------------
 // One Gaussian occupies one 16-lane DPP row; its K samples are strided over the 16 lanes (k = l, l+16, ...), so each
@@ -261,51 +54,8 @@ __device__ __forceinline__ float row_transpose_reduce16(float (&v)[16])
     return transpose_step<1, true>(v[0], v[1], (lane & 1) != 0);
 }
 
-// ---- register-free prefetch: global -> LDS DMA (global_load_lds), double buffered per wave -----------------------------
-// Every wave owns two copies of {4 uniform records (4x64 floats), its 4 Gaussians' next 64 sample directions (4x64x3),
-// visibilities (4x64), areas (4x64)}.  While the wave computes on one copy, the loads of its NEXT (Gaussian group,
-// 64-sample block) are in flight into the other: the HBM/L2 latency of the three [P,K,*] caches and of the per-Gaussian
-// record is hidden without spending VGPRs or extra waves (the kernels run at 2 waves/SIMD).  The LDS image of a DMA
-// load is wave base + lane * size, so the copies keep the global layout: dirs [grp][k][3], vis/area [grp][k],
-// record [grp][64].  With K % 4 == 0 every lane moves 16 bytes per instruction (9 DMA instructions per block),
-// otherwise 4 bytes (24 instructions).
-// The DMA is issued from inline assembly on purpose: the compiler's wait-count pass does not tell which LDS-DMA load
-// feeds which LDS read and drains the whole vector-memory queue (s_waitcnt vmcnt(0)) in front of the first LDS access
-// after a __builtin_amdgcn_global_load_lds -- including the prefetch that was just issued.  Loads it does not know
-// about can only make its own waits stricter, never too weak (vmcnt completes in order), and the one true dependency
-// -- "my previous prefetch has landed" -- is a single explicit s_waitcnt at the top of each block.  m0 (LDS base of
-// the DMA) is saved and restored inside the statement.
-template <int BYTES>
-__device__ __forceinline__ void lds_dma(const float* gptr, float* lds_base /* wave-uniform */)
-{
-    const unsigned int off = __builtin_amdgcn_readfirstlane(
-        (unsigned int)(size_t)(__attribute__((address_space(3))) float*)lds_base);
-    unsigned int saved;
-    if (BYTES == 16)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-                     "s_mov_b32 m0, %0" : "=&s"(saved) : "v"(gptr), "s"(off) : "memory");
-    else
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\t"
-                     "s_mov_b32 m0, %0" : "=&s"(saved) : "v"(gptr), "s"(off) : "memory");
-}
+// the LDS-DMA loads (shading_lookup.hpp lds_dma) of one double-buffered block of the 16-lane backward
 #define R3DG_GLDS(gp, lp, sz) lds_dma<sz>(gp, lp)
-// the same with the LDS byte address already in an SGPR (lds_address_of, computed once per wave): the generic-pointer form above
-// costs a 64-bit VGPR pair + a null test per destination, which the compiler hoists out of loops and keeps live
-__device__ __forceinline__ unsigned int lds_address_of(const float* lds_ptr /* wave-uniform */)
-{
-    return __builtin_amdgcn_readfirstlane((unsigned int)(size_t)(__attribute__((address_space(3))) const float*)lds_ptr);
-}
-template <int BYTES>
-__device__ __forceinline__ void lds_dma_at(const float* gptr, unsigned int lds_byte_address /* SGPR */)
-{
-    unsigned int saved;
-    if (BYTES == 16)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-                     "s_mov_b32 m0, %0" : "=&s"(saved) : "v"(gptr), "s"(lds_byte_address) : "memory");
-    else
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\t"
-                     "s_mov_b32 m0, %0" : "=&s"(saved) : "v"(gptr), "s"(lds_byte_address) : "memory");
-}
 
 constexpr int SB_USTRIDE = 68;
 constexpr int SB_U = 0, SB_DIRS = 272, SB_VIS = 1040, SB_AREA = 1296, SB_FLOATS = 1552;   // one buffer of one wave
@@ -367,8 +117,6 @@ __device__ __forceinline__ void issue_block_loads(int lane, int gb, int k0, int 
     }
 }
 
-// all DMA loads of this wave have landed (they are the only vector-memory loads in the steady-state loop)
-__device__ __forceinline__ void wait_block_loads() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // =====================================================================================================================
 // Forward, second formulation ("row" kernels): ONE WAVE PER GAUSSIAN, lane = sample.
@@ -451,26 +199,6 @@ shade_build_taps_kernel(size_t n, const float* __restrict__ dirs, const float* _
     taps[3 * i + 2] = __float_as_uint(e[2]);
 }
 
-// bilinear sample with zero padding (grid_sample align_corners=True, padding_mode zeros) from a packed tap; the texture
-// holds one float4 per texel (LDS or global)
-__device__ __forceinline__ void env_fetch(const PackedTap& t, const float4* tex4, int He, int We, float (&e)[3],
-                                          int (&tex)[4], float (&w)[4])
-{
-    const int x0 = (int)(t.xy & 0xffffu) - 1, y0 = (int)(t.xy >> 16) - 1;
-    const float wx0 = 1.f - t.wx1, wy0 = 1.f - t.wy1;
-    const bool xa = x0 >= 0, xb = x0 + 1 <= We - 1, ya = y0 >= 0, yb = y0 + 1 <= He - 1;    // x0 <= We-1, y0 <= He-1 always
-    const int xc0 = xa ? x0 : 0, xc1 = xb ? x0 + 1 : We - 1, yc0 = ya ? y0 : 0, yc1 = yb ? y0 + 1 : He - 1;
-    const float fx0 = xa ? wx0 : 0.f, fx1 = xb ? t.wx1 : 0.f, fy0 = ya ? wy0 : 0.f, fy1 = yb ? t.wy1 : 0.f;
-    const int r0 = __mul24(yc0, We), r1 = __mul24(yc1, We);          // 24-bit operands (He, We <= 32767): full-rate multiply
-    tex[0] = r0 + xc0; tex[1] = r0 + xc1; tex[2] = r1 + xc0; tex[3] = r1 + xc1;
-    w[0] = fy0 * fx0; w[1] = fy0 * fx1; w[2] = fy1 * fx0; w[3] = fy1 * fx1;
-    e[0] = e[1] = e[2] = 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const float4 v = tex4[tex[q]];
-        e[0] += v.x * w[q]; e[1] += v.y * w[q]; e[2] += v.z * w[q];
-    }
-}
 
 constexpr int ROW_WAVES = 4;
 
@@ -668,27 +396,6 @@ shade_pad_env_kernel(int n, const float* __restrict__ env, float4* __restrict__ 
 // Backward: gradients of sum(pbr*g_pbr) + sum(diffuse_light*g_diff) w.r.t. base_color, roughness, viewdirs,
 // incidents and the (activated) environment texture.  normals / dirs / visibility carry no gradient in the
 // reference (normal.detach(), cached samples).
-// the largest of `n` non-negative floats (the block maxima of max|upstream gradient|; n == 1: grad_absmax_kernel's word),
-// +inf = "some upstream gradient is not finite"; uniform over the wave.  This file is compiled with -ffast-math, which lets the
-// compiler assume that no float is inf / nan and fold `x <= FLT_MAX` to true: everything that DECIDES on finiteness works on
-// the bit patterns (non-negative floats order like unsigned integers; exponent all ones = inf / nan).
-__device__ __forceinline__ bool not_finite_bits(unsigned int bits) { return (bits & 0x7f800000u) == 0x7f800000u; }
-__device__ __forceinline__ unsigned int wave_gmax_bits(const unsigned int* __restrict__ gmax_bits, int n)
-{
-    unsigned int m = 0u;
-    for (int i = threadIdx.x & 63; i < n; i += 64) {
-        const unsigned int b = gmax_bits[i] & 0x7fffffffu;
-        m = not_finite_bits(b) ? 0x7f800000u : (b > m ? b : m);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned int other = (unsigned int)__shfl_xor((int)m, o, 64);
-        m = other > m ? other : m;
-    }
-    return m;
-}
-// fixed-point accumulation is possible for a positive, finite maximum
-__device__ __forceinline__ bool gmax_usable(unsigned int bits) { return bits != 0u && bits < 0x7f800000u; }
 
 // max(|g_pbr|, |g_diff|) over all Gaussians -> *out (as float bits; non-negative floats order like unsigned ints), +inf if any
 // element is inf / nan.  Integer arithmetic on the bit patterns from the load on: under -ffast-math every float operation carries
@@ -983,18 +690,9 @@ shade_backward_kernel(int P, int K, int M, ShadeSrc src, const float* __restrict
     }
 }
 
-static int shade_cus()
-{
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    // persistent grids leave R3DG_OPT_RESERVE_CUS CUs to a collective running beside them (common.hpp)
-    return cus > opt(R3DG_OPT_RESERVE_CUS) ? cus - opt(R3DG_OPT_RESERVE_CUS) : 1;
-}
-
 static int shade_grid(int P, int blocks_per_cu = 2)
 {
-    const int cus = shade_cus();
+    const int cus = persistent_cus();
     const int want = (P + SH_GB - 1) / SH_GB;
     const int cap = cus * blocks_per_cu;      // persistent blocks, all resident: nothing queued behind them
     return want < cap ? (want > 0 ? want : 1) : cap;
@@ -1068,7 +766,7 @@ void launch_shade_forward(hipStream_t s, int P, int K, int M, const float* base_
         /* beside the instance ordering (fused iteration): 3 of the ~6 resident blocks per CU measured best for the     \
            iteration as a whole (2.05 -> 1.97 ms: the ordering kernels get CU time earlier) */                        \
         if (leave_room && opt(R3DG_OPT_SHADE_FWD_BLOCKS_PER_CU) == 0 && bpc > 3) bpc = 3;                                         \
-        const int cap = shade_cus() * bpc;                                                                            \
+        const int cap = persistent_cus() * bpc;                                                                           \
         const int grid = want < cap ? want : cap;                                                                     \
         if (M == 16)                                                                                                  \
             shade_forward_row_kernel<N, L, T, true><<<grid, 64 * ROW_WAVES, smem, s>>>(                               \
@@ -1087,6 +785,23 @@ void launch_shade_forward(hipStream_t s, int P, int K, int M, const float* base_
 #undef R3DG_ROW
 }
 
+const unsigned int* shade_upstream_absmax(hipStream_t s, int P, const float* g_pbr, const float* g_diff,
+                                          const float* block_absmax, int n_block_absmax, int* gmax_n)
+{
+    unsigned int* scratch = shade_scratch();
+    const unsigned int* gmax = scratch;
+    *gmax_n = 1;
+    if (block_absmax != nullptr && n_block_absmax > 0) {
+        gmax = reinterpret_cast<const unsigned int*>(block_absmax);
+        *gmax_n = n_block_absmax;
+    } else {
+        R3DG_HIP(hipMemsetAsync(scratch, 0, 4, s));
+        const int nb = (3 * P + 255) / 256;
+        grad_absmax_kernel<<<nb < 256 ? nb : 256, 256, 0, s>>>(3 * P, g_pbr, g_diff, scratch);
+    }
+    return gmax;
+}
+
 void launch_shade_backward(hipStream_t s, int P, int K, int M, const float* base_color, const float* roughness,
                            const float* normals, const float* viewdirs, const float* incidents, const float* env,
                            int He, int We, const float* tr, const float* visibility, const float* dirs,
@@ -1095,18 +810,8 @@ void launch_shade_backward(hipStream_t s, int P, int K, int M, const float* base
                            int n_block_absmax)
 {
     unsigned int* scratch = shade_scratch();
-    // scale of the fixed-point texture accumulation: max |upstream gradient|, either handed over as block maxima by the
-    // producer of g_pbr / g_diff (r3dg_stage2_unpack_gradients) or reduced here
-    const unsigned int* gmax = scratch;
     int gmax_n = 1;
-    if (block_absmax != nullptr && n_block_absmax > 0) {
-        gmax = reinterpret_cast<const unsigned int*>(block_absmax);
-        gmax_n = n_block_absmax;
-    } else {
-        R3DG_HIP(hipMemsetAsync(scratch, 0, 4, s));
-        const int nb = (3 * P + 255) / 256;
-        grad_absmax_kernel<<<nb < 256 ? nb : 256, 256, 0, s>>>(3 * P, g_pbr, g_diff, scratch);
-    }
+    const unsigned int* gmax = shade_upstream_absmax(s, P, g_pbr, g_diff, block_absmax, n_block_absmax, &gmax_n);
     const int ntex = He * We * 3;
     const int n = P;
     const ShadeSrc src = {base_color, roughness, normals, viewdirs, incidents, g_pbr, g_diff,
@@ -1134,302 +839,5 @@ void launch_shade_backward(hipStream_t s, int P, int K, int M, const float* base
 #undef R3DG_SB3
     check_launch(s, false, "shade_backward_kernel");
 }
-
-}  // namespace r3dg
-#include "shading_transport.hpp"
-#include "shading_split.hpp"
-#include "shading_frs.hpp"
-namespace r3dg {
-
-// ---- fixed ray set (shading_frs.hpp) -------------------------------------------------------------------------------------
-size_t shade_frs_table_floats(int K) { return (size_t)((K + 15) / 16) * 512; }
-
-void launch_shade_frs_build_tables(hipStream_t s, int K, const float* zsamples, float* tables)
-{
-    const int nblk = (K + 15) / 16;
-    frs_build_tables_kernel<<<(nblk * 512 + 255) / 256, 256, 0, s>>>(K, nblk, zsamples, tables);
-    check_launch(s, false, "frs_build_tables_kernel");
-}
-
-void launch_shade_frs_classify(hipStream_t s, int P, const float* ray_normals, uint8_t* valid)
-{
-    if (P == 0) return;
-    frs_classify_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, ray_normals, valid);
-    check_launch(s, false, "frs_classify_kernel");
-}
-
-void launch_shade_frs_build_taps(hipStream_t s, int P, int K, const float* ray_normals, const float* zsamples, int He, int We,
-                                 uint32_t* taps)
-{
-    const size_t n = (size_t)P * K;
-    if (n == 0) return;
-    frs_build_taps_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(P, K, ray_normals, zsamples, He, We, taps);
-    check_launch(s, false, "frs_build_taps_kernel");
-}
-
-// can the fixed-ray-set kernels take this configuration?  (everything else goes through the general kernels)
-bool shade_frs_supported(int K, int M, int He, int We)
-{
-    return M == 16 && K >= 4 && (K % 4) == 0 && He <= 511 && We <= 511 &&
-           (size_t)He * We * (16 + 24) <= (size_t)ENV_LDS_MAX * 4;
-}
-
-// dynamic LDS of the two kernels: the texture as float4 texels (+ its 3 x 64-bit gradient accumulators), the per-wave staging
-// areas of the next group's per-Gaussian data, the backward's table words when they fit
-static size_t frs_forward_lds_bytes(int He, int We)
-{
-    return ((size_t)He * We * 4 + (size_t)FRS_WAVES * FRS_ST_FWD) * sizeof(float);
-}
-static size_t frs_backward_lds_bytes(int K, int He, int We)
-{
-    const size_t ntexel = (size_t)He * We, nblk = (size_t)(K + 15) / 16;
-    return (((10 * ntexel + 3) & ~(size_t)3) + (size_t)FRS_WAVES * FRS_ST_BWD + (K <= FRS_TAB_LDS_MAX_K ? nblk * 512 : 0)) *
-           sizeof(float);
-}
-
-static int frs_grid(int P, const void* kernel, size_t smem)
-{
-    // resident workgroups per CU of (kernel, LDS size): asked once per device (the attribute / occupancy calls take the
-    // runtime's locks on every launch otherwise)
-    static std::mutex mu;
-    static std::map<std::tuple<int, const void*, size_t>, int> cache;
-    int dev = 0;
-    R3DG_HIP(hipGetDevice(&dev));
-    int nb = 0;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = cache.find(std::make_tuple(dev, kernel, smem));
-        if (it != cache.end()) {
-            nb = it->second;
-        } else {
-            if (smem > 65536)
-                R3DG_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            R3DG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 64 * FRS_WAVES, smem));
-            hipFuncAttributes fa;
-            R3DG_HIP(hipFuncGetAttributes(&fa, kernel));
-            const int by_vgpr = 512 / (((fa.numRegs + 7) / 8) * 8);   // waves per SIMD = 256-thread blocks per CU
-            nb = nb < by_vgpr ? nb : by_vgpr;
-            nb = nb > 0 ? (nb < 8 ? nb : 8) : 1;
-            cache[std::make_tuple(dev, kernel, smem)] = nb;
-        }
-    }
-    const int want = ((P + FRS_G - 1) / FRS_G + FRS_WAVES - 1) / FRS_WAVES;
-    const int cap = shade_cus() * nb;
-    return want < cap ? (want > 0 ? want : 1) : cap;
-}
-
-// every sample of the Fibonacci set carries the same area, 2 pi (fibonacci_sphere_sampling, utils/graphics_utils.py:26-37);
-// uniform_area == 0 means that value
-static inline float frs_area(float uniform_area) { return uniform_area > 0.f ? uniform_area : 6.283185307179586f; }
-
-// A fixed-ray-set call is three groups of launches, timed as three stages by the C ABI (capi_shading.hip) so that the profile's
-// "shade_forward" / "shade_backward" rows are ONE kernel each:
-//   aux     the coefficient rotation (forward: incidents -> cprime, kept for the backward; backward: dcprime -> d_inc), the
-//           max |upstream gradient| reduction when the caller has none
-//   main    the MFMA kernel for the Gaussians on the rotated path
-//   listed  the wave-per-Gaussian kernels for the listed rest
-void launch_shade_frs_forward_aux(hipStream_t s, int P, const float* incidents, const float* ray_normals, float* cprime)
-{
-    if (P == 0) return;
-    frs_rotate_kernel<false><<<(P + 255) / 256, 256, 0, s>>>(P, ray_normals, incidents, cprime, nullptr);
-    check_launch(s, false, "frs_rotate_kernel");
-}
-
-void launch_shade_frs_forward_main(hipStream_t s, int P, int K, const float* base_color, const float* roughness,
-                                   const float* normals, const float* viewdirs, const float* env, int He, int We,
-                                   const float* visibility, float uniform_area, const uint32_t* taps, const float* ray_normals,
-                                   const float* tables, const uint8_t* valid, const float* cprime, bool leave_room, float* out,
-                                   float* feat)
-{
-    if (P == 0) return;
-    const size_t smem = frs_forward_lds_bytes(He, We);
-    int grid = frs_grid(P, (const void*)shade_forward_frs_kernel, smem);
-    // beside the instance ordering (fused iteration) ONE workgroup per CU: the ordering chain (projection -> binning -> tile sort) is
-    // the longer of the two concurrent paths and every wave this kernel keeps resident slows it -- measured per CU cap: 1 -> 618-627,
-    // 2 -> 598-610, 3 -> 597-607 it/s (this kernel alone 0.21 / 0.195 / 0.21 ms; a high-priority ordering stream: no effect)
-    // That holds while this kernel is the SHORTER path.  With more samples it becomes the longer one and the cap costs more
-    // than it buys: 300k x 384 samples 339 (one per CU) / 365 (two) / 365 (three) it/s, 2M x 64 samples 152 / 158 / 155 -- two
-    // per CU above 40 M samples per launch.  (R3DG_OPT_SHADE_FWD_BLOCKS_PER_CU > 0 replaces the choice for A/B runs)
-    if (leave_room) {
-        const int by_size = (long long)P * K > 40000000ll ? 2 : 1;
-        const int per_cu = opt(R3DG_OPT_SHADE_FWD_BLOCKS_PER_CU) > 0 ? opt(R3DG_OPT_SHADE_FWD_BLOCKS_PER_CU) : by_size;
-        grid = grid > per_cu * shade_cus() ? per_cu * shade_cus() : grid;
-    }
-    const FrsSrc src = {base_color, roughness, normals, viewdirs, ray_normals, cprime, nullptr, nullptr, visibility, taps};
-    shade_forward_frs_kernel<<<grid, 64 * FRS_WAVES, smem, s>>>(P, K, src, env, He, We, frs_area(uniform_area), tables, valid, out,
-                                                                feat);
-    check_launch(s, false, "shade_forward_frs_kernel");
-}
-
-// grid of the listed kernels: one wave per Gaussian up to a few hundred waves, grid-stride beyond
-static int frs_listed_grid(int n_list)
-{
-    const int want = (n_list + FRS_LISTED_WAVES - 1) / FRS_LISTED_WAVES;
-    const int cap = shade_cus();
-    return want < cap ? (want > 0 ? want : 1) : cap;
-}
-
-void launch_shade_frs_forward_listed(hipStream_t s, int K, const float* base_color, const float* roughness,
-                                     const float* normals, const float* viewdirs, const float* incidents, const float* env, int He,
-                                     int We, const float* visibility, const float* ray_normals, const float* zsamples,
-                                     float uniform_area, const int* invalid_list, int n_invalid, float* out, float* feat)
-{
-    if (n_invalid <= 0) return;
-    const FrsSrc src = {base_color, roughness, normals, viewdirs, ray_normals, nullptr, nullptr, nullptr, visibility, nullptr};
-    const size_t smem = ((((size_t)3 * He * We + 3) & ~(size_t)3) + 64 * FRS_LISTED_WAVES) * sizeof(float);
-    shade_forward_frs_listed_kernel<<<frs_listed_grid(n_invalid), 64 * FRS_LISTED_WAVES, smem, s>>>(
-        n_invalid, invalid_list, K, src, incidents, env, He, We, zsamples, frs_area(uniform_area), out, feat);
-    check_launch(s, false, "shade_forward_frs_listed_kernel");
-}
-
-// (before _main) -> the words the main kernel scales its fixed-point texture accumulation by
-const unsigned int* launch_shade_frs_backward_aux(hipStream_t s, int P, const float* g_pbr, const float* g_diff,
-                                                  const float* block_absmax, int n_block_absmax, int* gmax_n)
-{
-    unsigned int* scratch = shade_scratch();
-    const unsigned int* gmax = scratch;
-    *gmax_n = 1;
-    if (block_absmax != nullptr && n_block_absmax > 0) {
-        gmax = reinterpret_cast<const unsigned int*>(block_absmax);
-        *gmax_n = n_block_absmax;
-    } else {
-        R3DG_HIP(hipMemsetAsync(scratch, 0, 4, s));
-        const int nb = (3 * P + 255) / 256;
-        grad_absmax_kernel<<<nb < 256 ? nb : 256, 256, 0, s>>>(3 * P, g_pbr, g_diff, scratch);
-    }
-    return gmax;
-}
-
-void launch_shade_frs_backward_main(hipStream_t s, int P, int K, const float* base_color, const float* roughness,
-                                    const float* normals, const float* viewdirs, const float* env, int He, int We,
-                                    const float* visibility, float uniform_area, const uint32_t* taps, const float* ray_normals,
-                                    const float* tables, const uint8_t* valid, const float* cprime, float* dcp, const float* g_pbr,
-                                    const float* g_diff, float* d_base, float* d_rough, float* d_view, float* d_env,
-                                    const unsigned int* gmax, int gmax_n)
-{
-    if (P == 0) return;
-    const bool tab_lds = K <= FRS_TAB_LDS_MAX_K;
-    const size_t smem = frs_backward_lds_bytes(K, He, We);
-    const FrsSrc src = {base_color, roughness, normals, viewdirs, ray_normals, cprime, g_pbr, g_diff, visibility, taps};
-    if (tab_lds) {
-        const int grid = frs_grid(P, (const void*)shade_backward_frs_kernel<true>, smem);
-        shade_backward_frs_kernel<true><<<grid, 64 * FRS_WAVES, smem, s>>>(
-            P, K, src, env, He, We, frs_area(uniform_area), tables, valid, d_base, d_rough, d_view, dcp, d_env, gmax, gmax_n);
-    } else {
-        const int grid = frs_grid(P, (const void*)shade_backward_frs_kernel<false>, smem);
-        shade_backward_frs_kernel<false><<<grid, 64 * FRS_WAVES, smem, s>>>(
-            P, K, src, env, He, We, frs_area(uniform_area), tables, valid, d_base, d_rough, d_view, dcp, d_env, gmax, gmax_n);
-    }
-    check_launch(s, false, "shade_backward_frs_kernel");
-}
-
-// gradient back to the unrotated coefficients.  valid == nullptr: every row of d_inc is written; valid != nullptr: only the rows
-// on the rotated path are written (the listed Gaussians' rows come from their own kernel, possibly on another stream)
-void launch_shade_frs_backward_rotate(hipStream_t s, int P, const float* ray_normals, const float* dcp, float* d_inc,
-                                      const uint8_t* valid)
-{
-    if (P == 0) return;
-    frs_rotate_kernel<true><<<(P + 255) / 256, 256, 0, s>>>(P, ray_normals, dcp, d_inc, valid);
-    check_launch(s, false, "frs_rotate_kernel");
-}
-
-void launch_shade_frs_incident_chain(hipStream_t s, int P, const float* ray_normals, const uint8_t* valid, const float* dcp,
-                                     float* d_inc, float* incidents, float* exp_avg, float* exp_avg_sq, float* cprime, float lr,
-                                     float lr_tail, float beta1, float beta2, float eps, int step, float grad_scale,
-                                     const float* skip_flag, int listed_in_dcprime)
-{
-    if (P == 0) return;
-    // (bias corrections exactly as launch_adam forms them, stage2_glue.hip)
-    const double b1 = 1.0 - pow((double)beta1, (double)step), b2 = 1.0 - pow((double)beta2, (double)step);
-    FrsAdam a = {lr, lr_tail, beta1, beta2, eps, (float)b1, (float)(1.0 / sqrt(b2)), grad_scale, 1.f - beta1, 1.f - beta2};
-    // 49 KB of LDS per workgroup = three per CU: measured against two (56 KB) and one (81 KB) per CU, which are gentler on the
-    // activation / projection kernels running beside it but make the chain the longer path: 805 / 797 / 771 it/s
-    const size_t lds = 4 * 64 * FRS_CHAIN_LD * sizeof(float);
-    // (49 KB of dynamic LDS: under the 64 KB every launch may ask for, so no per-device function attribute is needed)
-    frs_incident_chain_kernel<<<(P + 255) / 256, 256, lds, s>>>(P, ray_normals, valid, dcp, d_inc, incidents, exp_avg, exp_avg_sq,
-                                                                cprime, a, skip_flag, listed_in_dcprime);
-    check_launch(s, false, "frs_incident_chain_kernel");
-}
-
-void launch_shade_frs_backward_listed(hipStream_t s, int K, const float* base_color, const float* roughness,
-                                      const float* normals, const float* viewdirs, const float* incidents, const float* env, int He,
-                                      int We, const float* visibility, const float* ray_normals, const float* zsamples,
-                                      float uniform_area, const int* invalid_list, int n_invalid, const float* g_pbr,
-                                      const float* g_diff, float* d_base, float* d_rough, float* d_view, float* d_inc, float* d_env,
-                                      const unsigned int* gmax, int gmax_n)
-{
-    if (n_invalid <= 0) return;
-    const FrsSrc src = {base_color, roughness, normals, viewdirs, ray_normals, nullptr, g_pbr, g_diff, visibility, nullptr};
-    const size_t smem = (3 * (((size_t)3 * He * We + 3) & ~(size_t)3) + 64 * FRS_LISTED_WAVES) * sizeof(float);
-    // (the texture gradient is flushed once per workgroup: a quarter of the forward's grid keeps that under the kernel's own time)
-    int grid = frs_listed_grid(n_invalid);
-    grid = grid > 64 ? 64 + (grid - 64) / 4 : grid;
-    if (smem > 65536)
-        R3DG_HIP(hipFuncSetAttribute((const void*)shade_backward_frs_listed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)smem));
-    shade_backward_frs_listed_kernel<<<grid, 64 * FRS_LISTED_WAVES, smem, s>>>(
-        n_invalid, invalid_list, K, src, incidents, env, He, We, zsamples, frs_area(uniform_area), d_base, d_rough, d_view, d_inc,
-        d_env, gmax, gmax_n);
-    check_launch(s, false, "shade_backward_frs_listed_kernel");
-}
-
-void launch_shade_build_split(hipStream_t s, int P, int K, const int* perm, const float* normals, const float* incidents,
-                              const float* visibility, const float* dirs, const float* zsamples, float uniform_area, float* lt,
-                              float* vis_t, float* consts)
-{
-    if (P == 0) return;
-    shade_build_split_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, K, perm, normals, incidents, visibility, dirs, zsamples,
-                                                           frs_area(uniform_area), reinterpret_cast<float4*>(lt), vis_t, consts);
-    check_launch(s, false, "shade_build_split_kernel");
-}
-
-void launch_shade_forward_split(hipStream_t s, int P, int K, const int* perm, const float* base_color, const float* roughness,
-                                const float* normals, const float* viewdirs, const float* lt, const float* vis_t,
-                                const float* consts, const float* zsamples, const float* tr, const float* env_fp, int He, int We,
-                                float* out)
-{
-    if (P == 0) return;
-    // sample range split into parts (shading_split.hpp): ~12+ waves per SIMD in the launch, parts a multiple of 4 samples long
-    const int waves = (P + 63) / 64;
-    int parts = (12 * 4 * shade_cus() + waves - 1) / waves;
-    parts = parts < 1 ? 1 : (parts > 8 ? 8 : parts);
-    int Kp = ((K + parts - 1) / parts + 3) & ~3;
-    parts = (K + Kp - 1) / Kp;
-    float4* partial = reinterpret_cast<float4*>(stream_scratch(s, 1, (size_t)parts * P * 3 * sizeof(float4)));
-    const dim3 grid((P + 255) / 256, parts);
-    shade_forward_split_kernel<<<grid, 256, 0, s>>>(P, K, Kp, perm, base_color, roughness, normals, viewdirs,
-                                                   reinterpret_cast<const float4*>(lt), vis_t, zsamples, tr,
-                                                   reinterpret_cast<const float4*>(env_fp), He, We, partial);
-    shade_split_combine_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, K, parts, perm, base_color, partial, consts, out);
-    check_launch(s, false, "shade_forward_split_kernel");
-}
-
-void launch_shade_env_footprints(hipStream_t s, int He, int We, const float* env, float* fp)
-{
-    const int n = (He + 1) * (We + 1);
-    shade_env_footprints_kernel<<<(n + 255) / 256, 256, 0, s>>>(He, We, env, reinterpret_cast<float4*>(fp));
-    check_launch(s, false, "shade_env_footprints_kernel");
-}
-
-void launch_shade_build_transport(hipStream_t s, int P, int K, int M, const float* normals, const float* incidents,
-                                  const float* visibility, const float* dirs, const float* areas, float uniform_area,
-                                  float* radiance_to_transport, float* consts)
-{
-    if (P == 0) return;
-    shade_build_transport_kernel<<<(P + TR_WAVES - 1) / TR_WAVES, 64 * TR_WAVES, 0, s>>>(
-        P, K, M, normals, incidents, visibility, dirs, areas, uniform_area, radiance_to_transport, consts);
-    check_launch(s, false, "shade_build_transport_kernel");
-}
-
-void launch_shade_forward_transport(hipStream_t s, int P, int K, const float* base_color, const float* roughness,
-                                    const float* normals, const float* viewdirs, const float* transport, const float* consts,
-                                    const float* zsamples, const float* dirs, float* out)
-{
-    if (P == 0) return;
-    shade_forward_transport_kernel<<<(P + TR_WAVES - 1) / TR_WAVES, 64 * TR_WAVES, 0, s>>>(
-        P, K, base_color, roughness, normals, viewdirs, transport, consts, zsamples, dirs, out);
-    check_launch(s, false, "shade_forward_transport_kernel");
-}
-
 
 }  // namespace r3dg

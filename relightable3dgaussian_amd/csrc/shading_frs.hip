@@ -2,7 +2,8 @@
 // are the Fibonacci set rotated to each Gaussian's normal -- what GaussianModel.update_visibility produces
 // (scene/gaussian_model.py:312-342: sample_incident_rays(normal, False, K) = fibonacci_sphere_sampling(random_rotate=False),
 // utils/graphics_utils.py:9-37; d_k = normalize(R(n) z_k), R = rotation_between_z, utils/sh_utils.py:36-68).
-// Included by shading.hip (after the general kernels, whose per-sample code it reuses).
+// This unit holds the kernels and their launchers; the per-sample code it shares with the general kernels (shading.hip) is
+// shading_lookup.hpp / shading_sample.hpp.
 //
 // Why.  The general kernels evaluate the 16 SH basis functions at every cached direction and contract them with the 48
 // incident-light coefficients -- forward: once; backward: twice (value and sign of the local light, then the gradient) --
@@ -30,7 +31,13 @@
 // d_k = R z_k / |R z_k| every per-sample dot product is a product against the z table (see FrsFrame below), the half vector
 // drops out of the GGX terms, and the lookup record is 8 bytes (frs_pack_axis): 12 B per sample, ~20 VALU instructions fewer
 // per sample in the forward and ~45 in the backward.
-#pragma once
+#include "shading_host.hpp"
+#include <cmath>
+#include <map>
+#include <mutex>
+#include <tuple>
+#include "wave_reduce.hpp"
+#include "shading_sample.hpp"
 #include "sh_rotation_tables.hpp"
 
 namespace r3dg {
@@ -42,22 +49,6 @@ constexpr int FRS_G = 16;                    // Gaussians per wave step (the N d
 constexpr float FRS_MAX_DEFECT = 2e-5f;      // max |R R^T - I| for which a Gaussian takes the rotated path
 constexpr int FRS_TAB_LDS_MAX_K = 128;       // backward: the Y_i(z_k) tables live in LDS up to this many samples (16 KB)
 
-// rotation_between_z(n) (utils/sh_utils.py:36-68), fp32 operation for operation as sampling.rotation_between_z
-__device__ __forceinline__ void frs_rotation(const float n0, const float n1, const float n2, float (&R)[9])
-{
-    const float v1 = -n1, v2 = n0, cp = fmaxf(n2 + 1.f, 1e-7f);
-    const bool regular = n2 + 1.f > 0.f;
-    R[0] = regular ? 1.f + (-v2 * v2) / cp : -1.f;
-    R[1] = regular ? v1 * v2 / cp : 0.f;
-    R[2] = regular ? v2 : 0.f;
-    R[3] = R[1];
-    R[4] = regular ? 1.f + (-v1 * v1) / cp : -1.f;
-    R[5] = regular ? -v1 : 0.f;
-    R[6] = regular ? -v2 : 0.f;
-    R[7] = regular ? v1 : 0.f;
-    R[8] = regular ? 1.f + (-v2 * v2 - v1 * v1) / cp : -1.f;
-}
-
 // valid[g] = 1 when R(n_g) is orthonormal to FRS_MAX_DEFECT (then normalize(R z_k) is a rigid copy of the z set)
 __global__ void __launch_bounds__(256)
 frs_classify_kernel(int P, const float* __restrict__ ray_normals, uint8_t* __restrict__ valid)
@@ -65,7 +56,7 @@ frs_classify_kernel(int P, const float* __restrict__ ray_normals, uint8_t* __res
     const int g = blockIdx.x * 256 + threadIdx.x;
     if (g >= P) return;
     float R[9];
-    frs_rotation(ray_normals[3 * (size_t)g], ray_normals[3 * (size_t)g + 1], ray_normals[3 * (size_t)g + 2], R);
+    rotation_between_z(ray_normals[3 * (size_t)g], ray_normals[3 * (size_t)g + 1], ray_normals[3 * (size_t)g + 2], R);
     float defect = 0.f;
 #pragma unroll
     for (int a = 0; a < 3; a++)
@@ -187,7 +178,7 @@ frs_rotate_kernel(int P, const float* __restrict__ ray_normals, const float* __r
         row[4 * q] = v.x; row[4 * q + 1] = v.y; row[4 * q + 2] = v.z; row[4 * q + 3] = v.w;
     }
     float R[9];
-    frs_rotation(ray_normals[3 * (size_t)g], ray_normals[3 * (size_t)g + 1], ray_normals[3 * (size_t)g + 2], R);
+    rotation_between_z(ray_normals[3 * (size_t)g], ray_normals[3 * (size_t)g + 1], ray_normals[3 * (size_t)g + 2], R);
     // band 0 (the constant) is rotation invariant
     frs_rotate_band<1, 3, BACK>(R, kShRotPoints1, kShRotAinv1, row);
     frs_rotate_band<4, 5, BACK>(R, kShRotPoints2, kShRotAinv2, row);
@@ -291,7 +282,7 @@ frs_incident_chain_kernel(int P, const float* __restrict__ ray_normals, const ui
     }
     float R[9];
     const int gc = live ? g : g0;
-    frs_rotation(ray_normals[3 * (size_t)gc], ray_normals[3 * (size_t)gc + 1], ray_normals[3 * (size_t)gc + 2], R);
+    rotation_between_z(ray_normals[3 * (size_t)gc], ray_normals[3 * (size_t)gc + 1], ray_normals[3 * (size_t)gc + 2], R);
     const bool rotated = valid == nullptr || valid[gc] != 0;
     __builtin_amdgcn_wave_barrier();
     // ---- rotation back, thread per Gaussian; the world-frame gradient row replaces the rotated one in the LDS row
@@ -422,7 +413,7 @@ frs_build_taps_kernel(int P, int K, const float* __restrict__ ray_normals, const
     if (i >= (size_t)P * K) return;
     const int g = (int)(i / (size_t)K), k = (int)(i - (size_t)g * K);
     float R[9];
-    frs_rotation(ray_normals[3 * (size_t)g], ray_normals[3 * (size_t)g + 1], ray_normals[3 * (size_t)g + 2], R);
+    rotation_between_z(ray_normals[3 * (size_t)g], ray_normals[3 * (size_t)g + 1], ray_normals[3 * (size_t)g + 2], R);
     const float zx = zsamples[3 * k], zy = zsamples[3 * k + 1], zz = zsamples[3 * k + 2];
     float dx = R[0] * zx + R[1] * zy + R[2] * zz, dy = R[3] * zx + R[4] * zy + R[5] * zz, dz = R[6] * zx + R[7] * zy + R[8] * zz;
     const float len = fmaxf(sqrtf(dx * dx + dy * dy + dz * dz), 1e-12f);
@@ -657,7 +648,7 @@ shade_forward_frs_kernel(int P, int K, FrsSrc src, const float* __restrict__ env
         FrsFrame F;
         {
             float R[9];
-            frs_rotation(rn0, rn1, rn2, R);
+            rotation_between_z(rn0, rn1, rn2, R);
             frs_frame(F, R, G.n[0], G.n[1], G.n[2], G.V[0], G.V[1], G.V[2], q);
         }
         const float fd[3] = {G.base[0] / kPi, G.base[1] / kPi, G.base[2] / kPi};
@@ -824,7 +815,7 @@ shade_backward_frs_kernel(int P, int K, FrsSrc src, const float* __restrict__ en
         FrsFrame F;
         {
             float R[9];
-            frs_rotation(rn0, rn1, rn2, R);
+            rotation_between_z(rn0, rn1, rn2, R);
             frs_frame(F, R, G.n[0], G.n[1], G.n[2], G.V[0], G.V[1], G.V[2], q);
         }
         const float fd[3] = {G.base[0] / kPi, G.base[1] / kPi, G.base[2] / kPi};
@@ -966,7 +957,7 @@ shade_backward_frs_kernel(int P, int K, FrsSrc src, const float* __restrict__ en
             if (q == 0) {
                 constexpr float C1 = 0.4886025119029199f;
                 float R[9];
-                frs_rotation(rn0, rn1, rn2, R);
+                rotation_between_z(rn0, rn1, rn2, R);
                 const float cx = -dvq[3] / C1, cy = -dvq[1] / C1, cz = dvq[2] / C1;            // sum_k gLoV_k s_k z_k (ray frame)
                 float dV[3];
 #pragma unroll
@@ -1049,7 +1040,7 @@ shade_forward_frs_listed_kernel(int n_list, const int* __restrict__ list, int K,
         GaussFwd G;
         gauss_setup(G, u);
         float R[9];
-        frs_rotation(u[58], u[59], u[60], R);
+        rotation_between_z(u[58], u[59], u[60], R);
         float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         for (int kb = 0; kb < K; kb += 64) {
             const int k = kb + lane, kc = min(k, K - 1);
@@ -1108,7 +1099,7 @@ shade_backward_frs_listed_kernel(int n_list, const int* __restrict__ list, int K
         GaussFwd G;
         gauss_setup(G, u);
         float R[9];
-        frs_rotation(u[58], u[59], u[60], R);
+        rotation_between_z(u[58], u[59], u[60], R);
         float gp[3], gd[3];
 #pragma unroll
         for (int c = 0; c < 3; c++) {
@@ -1206,6 +1197,223 @@ shade_backward_frs_listed_kernel(int n_list, const int* __restrict__ list, int K
             if (v64 != 0) atomicAdd(&d_env[i], (float)((double)v64 * (double)inv));
         }
     }
+}
+
+// ---- launchers -----------------------------------------------------------------------------------------------------------
+size_t shade_frs_table_floats(int K) { return (size_t)((K + 15) / 16) * 512; }
+
+void launch_shade_frs_build_tables(hipStream_t s, int K, const float* zsamples, float* tables)
+{
+    const int nblk = (K + 15) / 16;
+    frs_build_tables_kernel<<<(nblk * 512 + 255) / 256, 256, 0, s>>>(K, nblk, zsamples, tables);
+    check_launch(s, false, "frs_build_tables_kernel");
+}
+
+void launch_shade_frs_classify(hipStream_t s, int P, const float* ray_normals, uint8_t* valid)
+{
+    if (P == 0) return;
+    frs_classify_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, ray_normals, valid);
+    check_launch(s, false, "frs_classify_kernel");
+}
+
+void launch_shade_frs_build_taps(hipStream_t s, int P, int K, const float* ray_normals, const float* zsamples, int He, int We,
+                                 uint32_t* taps)
+{
+    const size_t n = (size_t)P * K;
+    if (n == 0) return;
+    frs_build_taps_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(P, K, ray_normals, zsamples, He, We, taps);
+    check_launch(s, false, "frs_build_taps_kernel");
+}
+
+// can the fixed-ray-set kernels take this configuration?  (everything else goes through the general kernels)
+bool shade_frs_supported(int K, int M, int He, int We)
+{
+    return M == 16 && K >= 4 && (K % 4) == 0 && He <= 511 && We <= 511 &&
+           (size_t)He * We * (16 + 24) <= (size_t)ENV_LDS_MAX * 4;
+}
+
+// dynamic LDS of the two kernels: the texture as float4 texels (+ its 3 x 64-bit gradient accumulators), the per-wave staging
+// areas of the next group's per-Gaussian data, the backward's table words when they fit
+static size_t frs_forward_lds_bytes(int He, int We)
+{
+    return ((size_t)He * We * 4 + (size_t)FRS_WAVES * FRS_ST_FWD) * sizeof(float);
+}
+static size_t frs_backward_lds_bytes(int K, int He, int We)
+{
+    const size_t ntexel = (size_t)He * We, nblk = (size_t)(K + 15) / 16;
+    return (((10 * ntexel + 3) & ~(size_t)3) + (size_t)FRS_WAVES * FRS_ST_BWD + (K <= FRS_TAB_LDS_MAX_K ? nblk * 512 : 0)) *
+           sizeof(float);
+}
+
+static int frs_grid(int P, const void* kernel, size_t smem)
+{
+    // resident workgroups per CU of (kernel, LDS size): asked once per device (the attribute / occupancy calls take the
+    // runtime's locks on every launch otherwise)
+    static std::mutex mu;
+    static std::map<std::tuple<int, const void*, size_t>, int> cache;
+    int dev = 0;
+    R3DG_HIP(hipGetDevice(&dev));
+    int nb = 0;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = cache.find(std::make_tuple(dev, kernel, smem));
+        if (it != cache.end()) {
+            nb = it->second;
+        } else {
+            if (smem > 65536)
+                R3DG_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+            R3DG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 64 * FRS_WAVES, smem));
+            hipFuncAttributes fa;
+            R3DG_HIP(hipFuncGetAttributes(&fa, kernel));
+            const int by_vgpr = 512 / (((fa.numRegs + 7) / 8) * 8);   // waves per SIMD = 256-thread blocks per CU
+            nb = nb < by_vgpr ? nb : by_vgpr;
+            nb = nb > 0 ? (nb < 8 ? nb : 8) : 1;
+            cache[std::make_tuple(dev, kernel, smem)] = nb;
+        }
+    }
+    const int want = ((P + FRS_G - 1) / FRS_G + FRS_WAVES - 1) / FRS_WAVES;
+    const int cap = persistent_cus() * nb;
+    return want < cap ? (want > 0 ? want : 1) : cap;
+}
+
+// A fixed-ray-set call is three groups of launches, timed as three stages by the C ABI (capi_shading.hip) so that the profile's
+// "shade_forward" / "shade_backward" rows are ONE kernel each:
+//   aux     the coefficient rotation (forward: incidents -> cprime, kept for the backward; backward: dcprime -> d_inc), the
+//           max |upstream gradient| reduction when the caller has none
+//   main    the MFMA kernel for the Gaussians on the rotated path
+//   listed  the wave-per-Gaussian kernels for the listed rest
+void launch_shade_frs_forward_aux(hipStream_t s, int P, const float* incidents, const float* ray_normals, float* cprime)
+{
+    if (P == 0) return;
+    frs_rotate_kernel<false><<<(P + 255) / 256, 256, 0, s>>>(P, ray_normals, incidents, cprime, nullptr);
+    check_launch(s, false, "frs_rotate_kernel");
+}
+
+void launch_shade_frs_forward_main(hipStream_t s, int P, int K, const float* base_color, const float* roughness,
+                                   const float* normals, const float* viewdirs, const float* env, int He, int We,
+                                   const float* visibility, float uniform_area, const uint32_t* taps, const float* ray_normals,
+                                   const float* tables, const uint8_t* valid, const float* cprime, bool leave_room, float* out,
+                                   float* feat)
+{
+    if (P == 0) return;
+    const size_t smem = frs_forward_lds_bytes(He, We);
+    int grid = frs_grid(P, (const void*)shade_forward_frs_kernel, smem);
+    // beside the instance ordering (fused iteration) ONE workgroup per CU: the ordering chain (projection -> binning -> tile sort) is
+    // the longer of the two concurrent paths and every wave this kernel keeps resident slows it -- measured per CU cap: 1 -> 618-627,
+    // 2 -> 598-610, 3 -> 597-607 it/s (this kernel alone 0.21 / 0.195 / 0.21 ms; a high-priority ordering stream: no effect)
+    // That holds while this kernel is the SHORTER path.  With more samples it becomes the longer one and the cap costs more
+    // than it buys: 300k x 384 samples 339 (one per CU) / 365 (two) / 365 (three) it/s, 2M x 64 samples 152 / 158 / 155 -- two
+    // per CU above 40 M samples per launch.  (R3DG_OPT_SHADE_FWD_BLOCKS_PER_CU > 0 replaces the choice for A/B runs)
+    if (leave_room) {
+        const int by_size = (long long)P * K > 40000000ll ? 2 : 1;
+        const int per_cu = opt(R3DG_OPT_SHADE_FWD_BLOCKS_PER_CU) > 0 ? opt(R3DG_OPT_SHADE_FWD_BLOCKS_PER_CU) : by_size;
+        grid = grid > per_cu * persistent_cus() ? per_cu * persistent_cus() : grid;
+    }
+    const FrsSrc src = {base_color, roughness, normals, viewdirs, ray_normals, cprime, nullptr, nullptr, visibility, taps};
+    shade_forward_frs_kernel<<<grid, 64 * FRS_WAVES, smem, s>>>(P, K, src, env, He, We, frs_area(uniform_area), tables, valid, out,
+                                                                feat);
+    check_launch(s, false, "shade_forward_frs_kernel");
+}
+
+// grid of the listed kernels: one wave per Gaussian up to a few hundred waves, grid-stride beyond
+static int frs_listed_grid(int n_list)
+{
+    const int want = (n_list + FRS_LISTED_WAVES - 1) / FRS_LISTED_WAVES;
+    const int cap = persistent_cus();
+    return want < cap ? (want > 0 ? want : 1) : cap;
+}
+
+void launch_shade_frs_forward_listed(hipStream_t s, int K, const float* base_color, const float* roughness,
+                                     const float* normals, const float* viewdirs, const float* incidents, const float* env, int He,
+                                     int We, const float* visibility, const float* ray_normals, const float* zsamples,
+                                     float uniform_area, const int* invalid_list, int n_invalid, float* out, float* feat)
+{
+    if (n_invalid <= 0) return;
+    const FrsSrc src = {base_color, roughness, normals, viewdirs, ray_normals, nullptr, nullptr, nullptr, visibility, nullptr};
+    const size_t smem = ((((size_t)3 * He * We + 3) & ~(size_t)3) + 64 * FRS_LISTED_WAVES) * sizeof(float);
+    shade_forward_frs_listed_kernel<<<frs_listed_grid(n_invalid), 64 * FRS_LISTED_WAVES, smem, s>>>(
+        n_invalid, invalid_list, K, src, incidents, env, He, We, zsamples, frs_area(uniform_area), out, feat);
+    check_launch(s, false, "shade_forward_frs_listed_kernel");
+}
+
+// (before _main) -> the words the main kernel scales its fixed-point texture accumulation by
+const unsigned int* launch_shade_frs_backward_aux(hipStream_t s, int P, const float* g_pbr, const float* g_diff,
+                                                  const float* block_absmax, int n_block_absmax, int* gmax_n)
+{
+    return shade_upstream_absmax(s, P, g_pbr, g_diff, block_absmax, n_block_absmax, gmax_n);
+}
+
+void launch_shade_frs_backward_main(hipStream_t s, int P, int K, const float* base_color, const float* roughness,
+                                    const float* normals, const float* viewdirs, const float* env, int He, int We,
+                                    const float* visibility, float uniform_area, const uint32_t* taps, const float* ray_normals,
+                                    const float* tables, const uint8_t* valid, const float* cprime, float* dcp, const float* g_pbr,
+                                    const float* g_diff, float* d_base, float* d_rough, float* d_view, float* d_env,
+                                    const unsigned int* gmax, int gmax_n)
+{
+    if (P == 0) return;
+    const bool tab_lds = K <= FRS_TAB_LDS_MAX_K;
+    const size_t smem = frs_backward_lds_bytes(K, He, We);
+    const FrsSrc src = {base_color, roughness, normals, viewdirs, ray_normals, cprime, g_pbr, g_diff, visibility, taps};
+    if (tab_lds) {
+        const int grid = frs_grid(P, (const void*)shade_backward_frs_kernel<true>, smem);
+        shade_backward_frs_kernel<true><<<grid, 64 * FRS_WAVES, smem, s>>>(
+            P, K, src, env, He, We, frs_area(uniform_area), tables, valid, d_base, d_rough, d_view, dcp, d_env, gmax, gmax_n);
+    } else {
+        const int grid = frs_grid(P, (const void*)shade_backward_frs_kernel<false>, smem);
+        shade_backward_frs_kernel<false><<<grid, 64 * FRS_WAVES, smem, s>>>(
+            P, K, src, env, He, We, frs_area(uniform_area), tables, valid, d_base, d_rough, d_view, dcp, d_env, gmax, gmax_n);
+    }
+    check_launch(s, false, "shade_backward_frs_kernel");
+}
+
+// gradient back to the unrotated coefficients.  valid == nullptr: every row of d_inc is written; valid != nullptr: only the rows
+// on the rotated path are written (the listed Gaussians' rows come from their own kernel, possibly on another stream)
+void launch_shade_frs_backward_rotate(hipStream_t s, int P, const float* ray_normals, const float* dcp, float* d_inc,
+                                      const uint8_t* valid)
+{
+    if (P == 0) return;
+    frs_rotate_kernel<true><<<(P + 255) / 256, 256, 0, s>>>(P, ray_normals, dcp, d_inc, valid);
+    check_launch(s, false, "frs_rotate_kernel");
+}
+
+void launch_shade_frs_incident_chain(hipStream_t s, int P, const float* ray_normals, const uint8_t* valid, const float* dcp,
+                                     float* d_inc, float* incidents, float* exp_avg, float* exp_avg_sq, float* cprime, float lr,
+                                     float lr_tail, float beta1, float beta2, float eps, int step, float grad_scale,
+                                     const float* skip_flag, int listed_in_dcprime)
+{
+    if (P == 0) return;
+    // (bias corrections exactly as launch_adam forms them, adam.hip)
+    const double b1 = 1.0 - pow((double)beta1, (double)step), b2 = 1.0 - pow((double)beta2, (double)step);
+    FrsAdam a = {lr, lr_tail, beta1, beta2, eps, (float)b1, (float)(1.0 / sqrt(b2)), grad_scale, 1.f - beta1, 1.f - beta2};
+    // 49 KB of LDS per workgroup = three per CU: measured against two (56 KB) and one (81 KB) per CU, which are gentler on the
+    // activation / projection kernels running beside it but make the chain the longer path: 805 / 797 / 771 it/s
+    const size_t lds = 4 * 64 * FRS_CHAIN_LD * sizeof(float);
+    // (49 KB of dynamic LDS: under the 64 KB every launch may ask for, so no per-device function attribute is needed)
+    frs_incident_chain_kernel<<<(P + 255) / 256, 256, lds, s>>>(P, ray_normals, valid, dcp, d_inc, incidents, exp_avg, exp_avg_sq,
+                                                                cprime, a, skip_flag, listed_in_dcprime);
+    check_launch(s, false, "frs_incident_chain_kernel");
+}
+
+void launch_shade_frs_backward_listed(hipStream_t s, int K, const float* base_color, const float* roughness,
+                                      const float* normals, const float* viewdirs, const float* incidents, const float* env, int He,
+                                      int We, const float* visibility, const float* ray_normals, const float* zsamples,
+                                      float uniform_area, const int* invalid_list, int n_invalid, const float* g_pbr,
+                                      const float* g_diff, float* d_base, float* d_rough, float* d_view, float* d_inc, float* d_env,
+                                      const unsigned int* gmax, int gmax_n)
+{
+    if (n_invalid <= 0) return;
+    const FrsSrc src = {base_color, roughness, normals, viewdirs, ray_normals, nullptr, g_pbr, g_diff, visibility, nullptr};
+    const size_t smem = (3 * (((size_t)3 * He * We + 3) & ~(size_t)3) + 64 * FRS_LISTED_WAVES) * sizeof(float);
+    // (the texture gradient is flushed once per workgroup: a quarter of the forward's grid keeps that under the kernel's own time)
+    int grid = frs_listed_grid(n_invalid);
+    grid = grid > 64 ? 64 + (grid - 64) / 4 : grid;
+    if (smem > 65536)
+        R3DG_HIP(hipFuncSetAttribute((const void*)shade_backward_frs_listed_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)smem));
+    shade_backward_frs_listed_kernel<<<grid, 64 * FRS_LISTED_WAVES, smem, s>>>(
+        n_invalid, invalid_list, K, src, incidents, env, He, We, zsamples, frs_area(uniform_area), d_base, d_rough, d_view, d_inc,
+        d_env, gmax, gmax_n);
+    check_launch(s, false, "shade_backward_frs_listed_kernel");
 }
 
 }  // namespace r3dg

@@ -1,7 +1,10 @@
-// Per-sample / per-Gaussian arithmetic of the shading integral shared by the kernels of shading.hip: SH basis, the GGX
+// Per-sample / per-Gaussian arithmetic of the shading integral shared by every shading unit: SH basis, the GGX
 // set-up of one Gaussian, the local-light sum.  Plain C++ apart from the `__device__ __forceinline__` markers and float4, so
 // that tests/emu (a lock-step CPU emulation of simple kernels, test infrastructure) can compile the same source.
 #pragma once
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>      // (the CPU emulation includes its own definitions of the markers and float4 first)
+#endif
 
 namespace r3dg {
 

@@ -1,6 +1,8 @@
 // The relight frame under a light that turns with every frame: "split transport" cache + per-frame kernel with the lat-long
-// lookup inside (see the banner below).  Included by shading.hip only (it uses the lookup helpers defined there).
+// lookup inside (see the banner below): the cache builder, the footprint builder, the per-frame kernel and its combine pass.
+// Included by shading_relight.hip, which holds the launchers.
 #pragma once
+#include "shading_lookup.hpp"
 
 namespace r3dg {
 
@@ -23,21 +25,6 @@ namespace r3dg {
 // =====================================================================================================================
 constexpr int SPLIT_CONSTS = 4;        // per Gaussian: mean local light 3 | mean visibility
 
-__device__ __forceinline__ void tr_rotation(const float n0, const float n1, const float n2, float (&R)[9])
-{
-    const float v1 = -n1, v2 = n0, cp = fmaxf(n2 + 1.f, 1e-7f);
-    const bool regular = n2 + 1.f > 0.f;
-    R[0] = regular ? 1.f + (-v2 * v2) / cp : -1.f;
-    R[1] = regular ? v1 * v2 / cp : 0.f;
-    R[2] = regular ? v2 : 0.f;
-    R[3] = R[1];
-    R[4] = regular ? 1.f + (-v1 * v1) / cp : -1.f;
-    R[5] = regular ? -v1 : 0.f;
-    R[6] = regular ? -v2 : 0.f;
-    R[7] = regular ? v1 : 0.f;
-    R[8] = regular ? 1.f + (-v2 * v2 - v1 * v1) / cp : -1.f;
-}
-
 // thread = Gaussian perm[i] (sorted order), loop over its K samples; dirs == nullptr: directions regenerated from the normal
 // (normalize(R(n) z_k), as update_visibility generated them); visibility [P,K] in the caller's layout
 __global__ void __launch_bounds__(256)
@@ -57,7 +44,7 @@ shade_build_split_kernel(int P, int K, const int* __restrict__ perm, const float
     }
     const float nx = normals[3 * (size_t)g], ny = normals[3 * (size_t)g + 1], nz = normals[3 * (size_t)g + 2];
     float R[9];
-    tr_rotation(nx, ny, nz, R);
+    rotation_between_z(nx, ny, nz, R);
     float loc_sum[3] = {0.f, 0.f, 0.f}, vis_sum = 0.f;
     for (int k = 0; k < K; k++) {
         float dx, dy, dz;
@@ -144,7 +131,7 @@ shade_forward_split_kernel(int P, int K, int Kp, const int* __restrict__ perm, c
     float M[9], Np[3], Vp[3];
     {
         float R[9];
-        tr_rotation(G.n[0], G.n[1], G.n[2], R);
+        rotation_between_z(G.n[0], G.n[1], G.n[2], R);
         if (tr != nullptr) {
 #pragma unroll
             for (int r = 0; r < 3; r++) {

@@ -1,6 +1,8 @@
-// The relight frame's opt-in transport cache: builder + per-frame kernel (see the banner below).  Included by shading.hip
-// (after shading_math.hpp) and, unchanged, by the CPU emulation in tests/emu.
+// The relight frame's opt-in transport cache: builder + per-frame kernel (see the banner below).  Included by
+// shading_relight.hip, which holds the launchers, and, unchanged, by the CPU emulation in tests/emu -- so it depends on
+// shading_math.hpp alone.
 #pragma once
+#include "shading_math.hpp"
 
 namespace r3dg {
 
@@ -21,6 +23,7 @@ namespace r3dg {
 constexpr int TR_WAVES = 4;
 constexpr int TR_CONSTS = 16;     // floats per Gaussian: diffuse_light 3 | incident light 3 | local 3 | global 3 | visibility 1 | pad
 
+// (common.hpp's wave_sum, restated: the CPU emulation compiles this header and cannot include the HIP-only common.hpp)
 __device__ __forceinline__ float wave_sum64(float x)
 {
 #pragma unroll

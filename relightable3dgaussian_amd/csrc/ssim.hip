@@ -23,14 +23,6 @@ __constant__ float kSsimWin[11] = {1.028380124e-03f, 7.598758209e-03f, 3.6000773
                                    2.130055279e-01f, 2.660117149e-01f, 2.130055279e-01f, 1.093606874e-01f,
                                    3.600077331e-02f, 7.598758209e-03f, 1.028380124e-03f};
 
-__device__ __forceinline__ float block_sum_256s(float v, float* s_part)
-{
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return s_part[0] + s_part[1] + s_part[2] + s_part[3];
-}
-
 // Both kernels: one 32x32 output tile per 256-thread workgroup.  Horizontal pass: a work item = (row of the 42-row
 // halo region, group of 4 adjacent columns): 14 LDS reads per map feed 4 outputs.  Vertical pass: a work item = (column,
 // group of 4 adjacent rows), exactly one per thread.
@@ -171,7 +163,7 @@ ssim_forward_kernel(int W, int H, int C, SsimBatch batch)
             pc[2 * HW + off] = 2.f * A * inv;
         }
     }
-    const float tot = block_sum_256s(ssim_sum, s_part);
+    const float tot = block_sum_256(ssim_sum, s_part);
     if (threadIdx.x == 0 && sum != nullptr) atomicAdd(sum_slot(sum), tot);
 }
 

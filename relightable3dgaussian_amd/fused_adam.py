@@ -1,4 +1,4 @@
-"""The one-launch Adam of the fused iterations (r3dg_adam_step, csrc/stage2_glue.hip): torch.optim.Adam's arithmetic over a
+"""The one-launch Adam of the fused iterations (r3dg_adam_step, csrc/adam.hip): torch.optim.Adam's arithmetic over a
 fixed set of tensors, every group -- or a chosen subset of them -- in ONE kernel launch."""
 import ctypes as C
 

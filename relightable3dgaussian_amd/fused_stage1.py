@@ -1,4 +1,4 @@
-"""Fused stage-1 (plain 3DGS + normals) training iteration with densification: the glue kernels of csrc/stage2_glue.hip
+"""Fused stage-1 (plain 3DGS + normals) training iteration with densification: the glue kernels of csrc/stage1_glue.hip
 around the rasterizer, no autograd graph, one-launch Adam (fused_adam.FusedAdam)."""
 import collections
 

@@ -1,6 +1,6 @@
 """Fused stage-2 training iteration: the same computation as train_step.Stage2Step + loss.backward()
 + Adam, but with the ~250 elementwise PyTorch launches around the hot ops replaced by the streaming HIP kernels of
-csrc/stage2_glue.hip and without an autograd graph: forward, loss, backward and optimizer are explicit calls in order.
+csrc/stage2_glue.hip, smooth.hip and adam.hip and without an autograd graph: forward, loss, backward and optimizer are explicit calls in order.
 
     GaussianModel activations + viewdirs,     r3dg_stage2_activate_with        (scene/gaussian_model.py:183-232, neilf.py:74-76,
       softplus of the env texture, sum reset                                      direct_light_map.py:18-27)
@@ -253,7 +253,7 @@ class FusedStage2Step(FusedStepBase):
             # fibonacci_sphere_sampling gives every sample the area 2 pi: then the area cache need not be read at all
             lo, hi = float(self.incident_areas.min()), float(self.incident_areas.max())
             self._uniform_area = lo if lo == hi else None
-            # fixed-ray-set kernels (csrc/shading_frs.hpp) when the cache IS the Fibonacci set of the snapshot normals --
+            # fixed-ray-set kernels (csrc/shading_frs.hip) when the cache IS the Fibonacci set of the snapshot normals --
             # checked here, once per visibility update -- and fits their limits; otherwise (caches handed in from elsewhere,
             # other K, R3DG_SHADE_FRS=0) the general kernels
             self._frs_built, self._taps = None, None

@@ -202,7 +202,7 @@ def shade_forward_split(split, base_color, roughness, normals, viewdirs, env_tra
 
 
 class FixedRaySet:
-    """State of the fixed-ray-set shading kernels (include/r3dg_hip.h "fixed ray set", csrc/shading_frs.hpp) for ONE
+    """State of the fixed-ray-set shading kernels (include/r3dg_hip.h "fixed ray set", csrc/shading_frs.hip) for ONE
     visibility update: the normals the cached directions were generated from (12 bytes per Gaussian -- the kernels read NO
     per-sample direction), the z set and its Y_i(z_k) tables, which Gaussians take the rotated path, the 8-byte lookup
     records of the current texture size, scratch for the rotated coefficients.  `forward` / `backward` compute what

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE ONLY: the relight transport-cache kernels (csrc/shading_math.hpp, csrc/shading_transport.hpp -- the
-// very files shading.hip compiles for gfx950) run through the lock-step CPU emulation of hip_emu.hpp.
+// very files shading_relight.hip compiles for gfx950) run through the lock-step CPU emulation of hip_emu.hpp.
 //   g++ -std=c++20 -O1 -pthread -shared -fPIC -I relightable3dgaussian_amd/csrc tests/emu/transport_emu.cpp -o libtransport_emu.so
 #include "hip_emu.hpp"
 #include "shading_math.hpp"

@@ -1,4 +1,4 @@
-"""Fused stage-2 iteration (csrc/stage2_glue.hip + fused_step.py) against the plain-PyTorch/autograd restatement of the
+"""Fused stage-2 iteration (csrc/stage2_glue.hip, smooth.hip, adam.hip + fused_step.py) against the plain-PyTorch/autograd restatement of the
 reference's Python glue (train_step.Stage2Step: gaussian_renderer/neilf.py:15-318, scene/gaussian_model.py:183-232) and
 torch.optim.Adam.  fp32 tolerances: the two paths evaluate the same formulas in different association orders, the
 reductions inside the HIP ops use float atomics."""

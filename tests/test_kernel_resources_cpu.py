@@ -15,9 +15,9 @@ from relightable3dgaussian_amd import build as B
 HOT = {
     "rasterizer_render_fwd.hip": [r"render_forward_wave_kernel"],
     "rasterizer_render_bwd.hip": [r"render_backward_wave_kernel", r"render_backward_features_kernel"],
-    "shading.hip": [r"shade_forward_frs_kernel", r"shade_backward_frs_kernel", r"shade_forward_transport_kernel",
-                    r"shade_forward_split_kernel"],
-    "stage2_glue.hip": [r"s2_smooth_stream_kernel"],
+    "shading_frs.hip": [r"shade_forward_frs_kernel", r"shade_backward_frs_kernel"],
+    "shading_relight.hip": [r"shade_forward_transport_kernel", r"shade_forward_split_kernel"],
+    "smooth.hip": [r"s2_smooth_stream_kernel"],
 }
 
 

@@ -223,7 +223,7 @@ def _frs_args(inp):
 
 @pytest.mark.parametrize("P,K,He", [(2500, 64, 16), (1000, 384, 16), (333, 100, 16), (50, 8, 8), (17, 32, 16), (4097, 16, 4)])
 def test_fixed_ray_set_kernels_equal_the_general_kernels(P, K, He):
-    """shading_ops.FixedRaySet (csrc/shading_frs.hpp: rotated SH coefficients, every per-sample product against the z table on
+    """shading_ops.FixedRaySet (csrc/shading_frs.hip: rotated SH coefficients, every per-sample product against the z table on
     the matrix cores, 4 lanes per Gaussian, NO direction stream) vs the general kernels on the cached directions: the training
     outputs of the forward and all five gradients of the backward.  P not a multiple of 16, K not a multiple of 16 or 64,
     Gaussians off the rotated path (wave-per-Gaussian kernels that regenerate their directions).
@@ -548,7 +548,7 @@ def test_fixed_ray_set_side_streams_and_early_rotation_change_nothing():
 @pytest.mark.parametrize("poison", [float("nan"), float("inf"), float("-inf")])
 @pytest.mark.parametrize("path,row", [("general", 10), ("frs", 10), ("frs", 2)])
 def test_non_finite_upstream_gradient_is_propagated_not_hidden(poison, path, row):
-    """csrc/shading.hip is built with -ffast-math, which lets the compiler assume that no float is inf / nan -- so every decision
+    """The shading units (csrc/shading*.hip) are built with -ffast-math, which lets the compiler assume that no float is inf / nan -- so every decision
     on finiteness in it works on bit patterns (the max |upstream gradient| word that scales the fixed-point texture
     accumulation carries +inf as "not finite": the kernels then accumulate the texture gradient with float atomics).  The
     contract, as torch.autograd gives it to the reference (neilf.py:339-371 under loss.backward()): one Gaussian with a
@@ -586,7 +586,7 @@ def test_non_finite_upstream_gradient_is_propagated_not_hidden(poison, path, row
 
 
 def test_fixed_ray_set_tables_hold_the_basis_in_the_two_mfma_layouts():
-    """r3dg_shade_frs_build_tables vs the layout its consumers assume (csrc/shading_frs.hpp): per 16-sample block, slots 0..3 =
+    """r3dg_shade_frs_build_tables vs the layout its consumers assume (csrc/shading_frs.hip): per 16-sample block, slots 0..3 =
     A operand of the local-light product (lane (r, q): Yz[16 b + r][4 s + q]), slots 4..7 = A operand of the gradient
     product (lane (i, q): Yz[16 b + 4 q + v][i]); rows beyond K are zero."""
     from oracle import shading

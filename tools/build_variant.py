@@ -30,7 +30,7 @@ def build_variant(name, src, replacements=(), extra_flags=(), count=None):
     for rep in replacements:
         old, new = rep[0], rep[1]
         n = rep[2] if len(rep) > 2 and rep[2] is not None else 1
-        fname = rep[3] if len(rep) > 3 else src              # (a header of csrc/ the source includes, e.g. "shading_frs.hpp")
+        fname = rep[3] if len(rep) > 3 else src              # (a header of csrc/ the source includes, e.g. "shading_lookup.hpp")
         text = texts.get(fname) or open(os.path.join(B.CSRC, fname)).read()
         if text.count(old) != n:
             raise RuntimeError("variant %s: %r occurs %d times in %s, expected %d" % (name, old[:60], text.count(old), fname, n))

@@ -21,11 +21,11 @@ from relightable3dgaussian_amd import build as B   # noqa: E402
 # (file, substring of the demangled kernel name): the template instances the default bench launches
 KERNELS = [
     ("shading.hip", "shade_backward_kernel<true, true, true, false>"),
-    ("shading.hip", "shade_backward_frs_kernel"),
-    ("shading.hip", "shade_forward_frs_kernel"),
+    ("shading_frs.hip", "shade_backward_frs_kernel"),
+    ("shading_frs.hip", "shade_forward_frs_kernel"),
     ("shading.hip", "shade_forward_row_kernel<7, true, 1, true, false>"),
     ("shading.hip", "shade_forward_row_kernel<19, false, 2, true, false>"),
-    ("shading.hip", "shade_forward_transport_kernel"),
+    ("shading_relight.hip", "shade_forward_transport_kernel"),
     ("rasterizer_render_fwd.hip", "render_forward_wave_kernel<16, 4>"),
     ("rasterizer_render_bwd.hip", "render_backward_wave_kernel<4, true>"),
 ]

@@ -48,7 +48,7 @@ for K, He in CASES:
         torch.cuda.synchronize()
         pr = _lib.profile_read(); L.r3dg_profile_enable(0)
         res["backward (cached taps)"] = pr["shade_backward"][0] / max(pr["shade_backward"][1], 1)
-    # the fixed-ray-set kernels on the same caches (csrc/shading_frs.hpp): coefficient rotation + MFMA kernel (+ the
+    # the fixed-ray-set kernels on the same caches (csrc/shading_frs.hip): coefficient rotation + MFMA kernel (+ the
     # wave-per-Gaussian
     # kernels on the few Gaussians off the rotated path) in one profiled stage each
     if so.FixedRaySet.supported(K, 16, He, 2 * He):

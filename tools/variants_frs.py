@@ -11,7 +11,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-H = "shading_frs.hpp"
+SRC = "shading_frs.hip"
 
 
 def _head(path):
@@ -28,14 +28,14 @@ SB_BWD = "            __builtin_amdgcn_sched_barrier(0);\n            f32x4 l[3]
 FWD_SIG = "__global__ void __launch_bounds__(64 * FRS_WAVES, 3)\nshade_forward_frs_kernel("
 VARIANTS = {
     # the committed kernels (git HEAD) beside the working tree's: same box, same run
-    "frs_head": lambda: [(_cur("shading.hip"), _head("shading.hip"), None, "shading.hip"), (_cur(H), _head(H), None, H)],
+    "frs_head": lambda: [(_cur(SRC), _head(SRC))],
 }
 
 
 def build():
     from tools.build_variant import build_variant
     for name, reps in VARIANTS.items():
-        print(name, build_variant(name, "shading.hip", reps()))
+        print(name, build_variant(name, SRC, reps()))
 
 
 def run(out):
