@@ -783,8 +783,8 @@ enum r3dg_option {
     R3DG_OPT_BINNING_BLOCK_K,           /* direct binning: Gaussians per workgroup / 1024 (1..4, default 2) */
     R3DG_OPT_STAGE_SH_ROWS,             /* per-Gaussian kernels move SH / dL_dsh rows through LDS (1, default) or walk them in HBM (0) */
     R3DG_OPT_SHADE_FWD_BLOCKS_PER_CU,   /* persistent workgroups per CU of the general shading forward; 0 = as many as fit (default) */
-    R3DG_OPT_TRACE_FORMULATION,         /* visibility trace: 4 = phase-separated persistent waves (default), 3 = persistent waves,
-                                         * 2 = packed records, 1 = wave-cooperative packets, 0 = one fixed ray per thread */
+    R3DG_OPT_TRACE_FORMULATION,         /* visibility trace: 1 = packed records, phase-separated persistent waves (default),
+                                         * 0 = one fixed ray per thread over the reference's tables */
     R3DG_OPT_TRACE_REFILL,              /* idle lanes at which a persistent trace wave refills (default 16) */
     R3DG_OPT_TRACE_NODE_WEIGHT,         /* vote weights of the phased trace */
     R3DG_OPT_TRACE_LEAF_WEIGHT,

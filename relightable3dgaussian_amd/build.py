@@ -26,9 +26,12 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno
 # shading units: VALU-bound transcendental-heavy float math; fp32 tolerance is 1e-4, so reciprocal/sqrt approximations
 # (v_rcp_f32, v_sqrt_f32: 1 ulp) replace the IEEE division/sqrt expansions
 SHADING_FLAGS = ["-ffast-math", "-fno-slp-vectorize"]
+# LBVH units: Morton codes decide the tree topology, slab comparisons decide integer hit counts -> as the CPU oracle computes them
+BVH_FLAGS = ["-ffp-contract=off"]
 EXTRA = {
     "rasterizer_preprocess.hip": ["-ffp-contract=off"],
-    "bvh.hip": ["-ffp-contract=off"],
+    "bvh_build.hip": BVH_FLAGS,
+    "bvh_trace.hip": BVH_FLAGS,
     "simple_knn.hip": ["-ffp-contract=off"],
     "densify.hip": ["-ffp-contract=off"],         # clone / split / prune decisions are fp32 comparisons
     "shading.hip": SHADING_FLAGS,

@@ -52,7 +52,7 @@ class RayTracer:
     def _records_for(self, means3D, symm_inv, opacity, normals):
         if self.tree.shape[0] != 2 * means3D.shape[0] - 1 or means3D.shape[0] == 0:
             return None
-        if _lib.get_option("TRACE_FORMULATION") < 2:         # (experiments: the formulations that walk the reference's tables)
+        if _lib.get_option("TRACE_FORMULATION") == 0:        # (experiments: the kernel that walks the reference's tables)
             return None
         arrays = (means3D, symm_inv, opacity, normals)
         key = tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in arrays)

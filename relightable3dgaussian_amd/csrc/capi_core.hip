@@ -25,10 +25,9 @@ constexpr OptionRow kOptions[] = {
     {R3DG_OPT_BINNING_BLOCK_K, 2, 1, 4},    // (measured at 2M Gaussians too: 2 / 3 / 4 -> 163 / 156 / 161 it/s, no trend)
     {R3DG_OPT_STAGE_SH_ROWS, 1, 0, 1},      // 1 = SH / dL_dsh rows through LDS, 0 = direct per-thread walks
     {R3DG_OPT_SHADE_FWD_BLOCKS_PER_CU, 0, 0, 8},    // persistent row blocks per CU, 0 = all that fit
-    // 4 = 3 + phase-separated bodies, 3 = packed records + persistent waves, 2 = packed records, 1 = wave-cooperative,
-    // 0 = round-1 kernel
-    {R3DG_OPT_TRACE_FORMULATION, 4, 0, 4},
-    {R3DG_OPT_TRACE_REFILL, REFILL_MIN_IDLE, 1, 64},
+    // 1 = packed records, phase-separated persistent waves; 0 = thread per ray over the reference's tables
+    {R3DG_OPT_TRACE_FORMULATION, 1, 0, 1},
+    {R3DG_OPT_TRACE_REFILL, 16, 1, 64},     // a wave pulls new rays when at least this many lanes are idle (or all of them)
     {R3DG_OPT_TRACE_NODE_WEIGHT, 1, 1, 15},
     {R3DG_OPT_TRACE_LEAF_WEIGHT, 1, 1, 15},
     // CUs the persistent kernels (shading forward / backward, visibility trace) leave unoccupied so that a collective running

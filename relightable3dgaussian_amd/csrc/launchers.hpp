@@ -6,10 +6,6 @@
 
 namespace r3dg {
 
-// Idle lanes at which a wave of the persistent visibility trace pulls new rays (bvh.hip trace_opacity_persistent_kernel):
-// the constant the non-phased kernel is compiled with AND the default of R3DG_OPT_TRACE_REFILL (capi_core.hip kOptions).
-constexpr int REFILL_MIN_IDLE = 16;      // refill when at least this many lanes are idle (or the whole wave is)
-
 // CUs a persistent grid may fill: the device's CUs minus the R3DG_OPT_RESERVE_CUS left to a collective running beside it on
 // another stream, at least 1 (capi_core.hip; library-internal, not part of the exported surface)
 __attribute__((visibility("hidden"))) int persistent_cus();
@@ -211,8 +207,9 @@ void launch_relight_compose(hipStream_t s, int W, int H, float fx, float fy, flo
                             const float* feature, const int* n_contrib, float* pbr_env, float* render_env, float* env_only);
 size_t knn_temp_bytes(size_t P);
 void knn_dist2(hipStream_t s, int P, const float* pts, float* dists, void* temp);
-size_t bvh_build_temp_bytes(size_t P);
+size_t bvh_build_temp_bytes(size_t P);                  // bvh_build.hip
 void bvh_build(hipStream_t s, int P, int32_t* nodes, float* aabbs, uint64_t* morton, void* temp);
+// bvh_trace.hip
 void bvh_trace_count(hipStream_t s, int num_rays, const int32_t* nodes, const float* aabbs, const float* rays_o,
                      const float* rays_d, int32_t* counts, int* overflow);
 void bvh_trace_fill(hipStream_t s, int num_rays, const int32_t* nodes, const float* aabbs, const float* rays_o,

@@ -54,7 +54,7 @@ def update_visibility(xyz, scales, rotations, opacity, normal, sample_num, group
     chunk = max(1, P // ((sample_num - 1) // 24 + 1))
     # The bundles are traced in MORTON order of their origin Gaussian (the leaf order of the tree just built): consecutive
     # ray blocks then start next to each other and walk the same subtrees, which is what the trace kernel's per-XCD L2s
-    # need (csrc/bvh.hip).  Results are scattered back to the caller's order; values are those of any other order.
+    # need (csrc/bvh_trace.hip).  Results are scattered back to the caller's order; values are those of any other order.
     order = getattr(tracer, "tree", None)
     order = order[P - 1:, 3].long() if (order is not None and P > 1) else torch.arange(P, device=xyz.device)
     dirs_all, areas_all = [], []

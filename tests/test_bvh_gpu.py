@@ -120,9 +120,9 @@ def test_trace_bvh_hit_lists_are_consistent(P, seed, K):
 
 @pytest.mark.parametrize("P,seed,K", [(7, 3, 16), (5000, 5, 64), (60_000, 6, 16)])
 def test_trace_formulations_give_identical_results(P, seed, K):
-    """R3DG_OPT_TRACE_FORMULATION: 0 thread-per-ray over the reference's tables, 2 packed 64-byte records, 3 persistent waves with
-    per-XCD queues, 4 (default) phase-separated bodies with the current node in a register -- same per-ray visit order and
-    arithmetic, so transmittance and hit counts are bit-identical (incl. a ray count that is not a multiple of 64)."""
+    """R3DG_OPT_TRACE_FORMULATION: 0 thread-per-ray over the reference's tables, 1 (default) packed 64-byte records walked by
+    persistent waves with per-XCD queues, phase-separated bodies and the current node in a register -- same per-ray visit order
+    and arithmetic, so transmittance and hit counts are bit-identical (incl. a ray count that is not a multiple of 64)."""
     from bvh_tracing import RayTracer
     from relightable3dgaussian_amd import _lib
     sc, dirs, cinv, rays_o = _bvh_case(P, seed, K=K, dup=True)
@@ -132,17 +132,16 @@ def test_trace_formulations_give_identical_results(P, seed, K):
     L = _lib.lib()
     got = {}
     try:
-        for mode in (0, 2, 3, 4):
+        for mode in (0, 1):
             _lib.set_option("TRACE_FORMULATION", mode)
             res = rt.trace_visibility(o, d, sc["xyz"].to(DEV), cinv.to(DEV), sc["opacity"][:, 0].contiguous().to(DEV),
                                       sc["normal"].to(DEV))
             torch.cuda.synchronize()
             got[mode] = (res["visibility"].clone(), res["contribute"].clone())
     finally:
-        _lib.set_option("TRACE_FORMULATION", 4)
-    for mode in (2, 3, 4):
-        assert torch.equal(got[mode][0], got[0][0]), "visibility differs in mode %d" % mode
-        assert torch.equal(got[mode][1], got[0][1]), "hit counts differ in mode %d" % mode
+        _lib.set_option("TRACE_FORMULATION", 1)
+    assert torch.equal(got[1][0], got[0][0]), "visibility differs in mode 1"
+    assert torch.equal(got[1][1], got[0][1]), "hit counts differ in mode 1"
     # the COUNTING instantiation of the default kernel (R3DG_OPT_TRACE_COUNT_VISITS, bench.py's node-visits/s): same results; every
     # ray takes at least the root's node step (P > 1), a leaf step per accepted Gaussian at least, and the sums are the
     # traversal's, i.e. the same on a second run
@@ -155,13 +154,13 @@ def test_trace_formulations_give_identical_results(P, seed, K):
             res = rt.trace_visibility(o, d, sc["xyz"].to(DEV), cinv.to(DEV), sc["opacity"][:, 0].contiguous().to(DEV),
                                       sc["normal"].to(DEV))
             counts.append(tuple(bvh_ops.VISITS))
-            assert torch.equal(res["visibility"], got[4][0]) and torch.equal(res["contribute"], got[4][1])
+            assert torch.equal(res["visibility"], got[1][0]) and torch.equal(res["contribute"], got[1][1])
     finally:
         _lib.set_option("TRACE_COUNT_VISITS", 0)
         bvh_ops.VISITS[:] = [0, 0, 0]
     nodes, leaves, rays = counts[0]
     assert counts[0] == counts[1] and rays == P * (K - 1)
-    assert nodes >= rays and leaves >= int(got[4][1].sum()) and nodes < 2000 * rays
+    assert nodes >= rays and leaves >= int(got[1][1].sum()) and nodes < 2000 * rays
 
 
 @pytest.mark.parametrize("P", [2, 700, 70_000])

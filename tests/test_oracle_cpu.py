@@ -239,10 +239,12 @@ def test_hip_library_exports_every_declared_symbol():
         "TILE_ORDER", "CULL", "TILE_BINNING", "BINNING_BLOCK_K", "STAGE_SH_ROWS", "SHADE_FWD_BLOCKS_PER_CU", "TRACE_FORMULATION",
         "TRACE_REFILL", "TRACE_NODE_WEIGHT", "TRACE_LEAF_WEIGHT", "RESERVE_CUS", "TRACE_COUNT_VISITS", "BWD_LEAN")
     assert _lib.get_option("TILE_BINNING") == 2 and _lib.get_option("CULL") == 1 and _lib.get_option("RESERVE_CUS") == 0
+    assert _lib.get_option("TRACE_FORMULATION") == 1
     _lib.set_option("RESERVE_CUS", 8)
     assert _lib.get_option("RESERVE_CUS") == 8
     _lib.set_option("RESERVE_CUS", 0)
-    for bad in ((len(_lib.OPTIONS), 0), (-1, 0), (_lib.OPTIONS.index("TILE_BINNING"), 3), (_lib.OPTIONS.index("CULL"), -1)):
+    for bad in ((len(_lib.OPTIONS), 0), (-1, 0), (_lib.OPTIONS.index("TILE_BINNING"), 3), (_lib.OPTIONS.index("CULL"), -1),
+                (_lib.OPTIONS.index("TRACE_FORMULATION"), 2)):
         assert lib.r3dg_set_option(*bad) != 0
     assert _lib.get_option("TILE_BINNING") == 2 and lib.r3dg_bounded_forward_supported(800, 800) == 1
     assert lib.r3dg_bounded_forward_supported(2560, 1664) == 0 and lib.r3dg_shade_frs_supported(64, 16, 16, 32) == 1
