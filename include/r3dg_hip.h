@@ -646,6 +646,43 @@ int r3dg_relight_compose(void* stream, int width, int height, float focal_x, flo
                          const float* d_image, const float* d_opacity, const float* d_feature,
                          const int32_t* d_n_contrib, float* d_pbr_env, float* d_render_env, float* d_env_only);
 
+/* ---- evaluation of held-out views (eval_nvs.py:49-82, eval_relighting_syn4.py:140-224; evaluate.py) ---------------------
+ * r3dg_relight_capture: the capture maps of an eval frame (neilf.py:146-182, what --capture_list and the evaluation scripts
+ *   read) from the rasterizer's raw S=28 feature image d_feature [28,H,W] (channel layout: r3dg_relight_pack_features),
+ *   d_opacity [H,W] and d_n_contrib [H,W] in one pass: x = feature / max(opacity, 1e-5) * (n_contrib > 0);
+ *     d_base_color, d_diffuse, d_specular, d_lights, d_local_lights, d_global_lights [3,H,W] = rgb_to_srgb(x) with its clip,
+ *     d_normal [3,H,W], d_roughness, d_visibility [1,H,W] = x, d_depth_var [1,H,W] = depth2 - depth^2,
+ *     d_pbr [3,H,W] = srgb(pbr * opacity + (1 - opacity) * background).
+ *   Any output may be NULL (its channels are then not read).  d_background [3] is required by d_pbr and by d_mask; d_mask
+ *   [H,W] (may be NULL): every map but d_depth_var is composited as map * mask + (1 - mask) * background
+ *   (eval_relighting_syn4.py:161-167; one-channel maps take background[0], the normal is composited as rendered).
+ * r3dg_eval_image_metrics: PSNR and SSIM of d_pred against d_gt, both [C,H,W] with 1 <= C <= 3.  With d_mask [H,W] both
+ *   images are first composited as x * mask + fill * (1 - mask) (eval_relighting_syn4.py:161-186) while they are loaded --
+ *   d_fill (may be NULL = 0) is a colour [C] (fill_is_image == 0) or an image [C,H,W] (!= 0, the env_only fill of :169,186).
+ *   d_tile_sums: scratch, 2 * C * ceil(W/32) * ceil(H/32) doubles (one (squared error, SSIM sum) pair per workgroup of the
+ *   SSIM tiling; added up in a fixed order by one workgroup: no float atomics, two runs give the same bits).  d_row
+ *   (R3DG_EVAL_ROW doubles, one row of the caller's metrics table) receives [0..2] the per-channel mean squared error,
+ *   [3] the sum of the SSIM map, [4] psnr = mean_c 20 log10(1 / sqrt(mse_c)) (utils/image_utils.py:24-29),
+ *   [5] ssim = [3] / (C H W) (utils/loss_utils.py:39-63), [6] C.
+ * r3dg_eval_median_ratio: the albedo scale of eval_relighting_syn4.py:201 -- per channel the LOWER median (index (n-1)/2 of
+ *   the sorted values, as torch.median) of d_gt / clamp(d_pred, 1e-6, 1) over the n pixels with d_mask > 0 (NULL = all);
+ *   images [3,H,W] with non-negative d_gt.  8-bit radix select on the float bit patterns, four passes, the digit picked on
+ *   the device.  d_state: scratch, R3DG_EVAL_MEDIAN_STATE_WORDS uint32.  d_row (R3DG_EVAL_ROW doubles) receives [0..2] the
+ *   medians and [3] n; n == 0 gives NaN medians and a count of 0.
+ * None of the three synchronises or reads anything back; images of 2^31 pixels and more are rejected. */
+#define R3DG_EVAL_ROW 8
+#define R3DG_EVAL_MEDIAN_STATE_WORDS 1024
+int r3dg_relight_capture(void* stream, int width, int height, const float* d_feature, const float* d_opacity,
+                         const int32_t* d_n_contrib, const float* d_background, const float* d_mask, float* d_pbr,
+                         float* d_base_color, float* d_roughness, float* d_normal, float* d_visibility, float* d_diffuse,
+                         float* d_specular, float* d_lights, float* d_local_lights, float* d_global_lights,
+                         float* d_depth_var);
+int r3dg_eval_image_metrics(void* stream, int width, int height, int channels, const float* d_pred, const float* d_gt,
+                            const float* d_mask, const float* d_fill, int fill_is_image, double* d_tile_sums,
+                            double* d_row);
+int r3dg_eval_median_ratio(void* stream, int width, int height, const float* d_pred, const float* d_gt,
+                           const float* d_mask, uint32_t* d_state, double* d_row);
+
 /* ---- densification bookkeeping -------------------------------------------------------------------
  * r3dg_densify_accumulate: GaussianModel.add_densification_stats (scene/gaussian_model.py:931-937) + the max-radii
  *   update of train.py:164-165, one pass.  The visibility filter is radii > 0 (render.py / neilf.py `visibility_filter`).

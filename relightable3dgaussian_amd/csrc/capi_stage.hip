@@ -1,5 +1,5 @@
 // C ABI of the training-iteration glue (include/r3dg_hip.h): stage-1 / stage-2 activations, feature packing and losses,
-// SSIM, Adam, relighting, densification.  Thin wrappers: argument checks, stage timing, one launcher each.
+// SSIM, Adam, relighting, evaluation, densification.  Thin wrappers: argument checks, stage timing, one launcher each.
 #include "capi_internal.hpp"
 
 using namespace r3dg;
@@ -399,6 +399,53 @@ int r3dg_relight_compose(void* stream_, int width, int height, float focal_x, fl
         StageTimer t((hipStream_t)stream_, ST_RELIGHT_COMPOSE);
         launch_relight_compose((hipStream_t)stream_, width, height, focal_x, focal_y, cx, cy, viewmatrix, light_transform,
                                envmap, He, We, image, opacity, feature, n_contrib, pbr_env, render_env, env_only);
+        return R3DG_OK;
+    });
+}
+
+// The three evaluation entry points run between iterations, not inside one: they are left out of the per-stage timing, whose
+// stages describe a training iteration or a relight frame.
+int r3dg_relight_capture(void* stream_, int width, int height, const float* feature, const float* opacity,
+                         const int32_t* n_contrib, const float* background, const float* mask, float* pbr,
+                         float* base_color, float* roughness, float* normal, float* visibility, float* diffuse,
+                         float* specular, float* lights, float* local_lights, float* global_lights, float* depth_var)
+{
+    if (width < 0 || height < 0) return invalid("relight_capture: bad shape");
+    if ((long long)width * height == 0) return R3DG_OK;
+    if ((long long)width * height >= (1ll << 31)) return invalid("relight_capture: image too large");
+    if (!feature || !opacity || !n_contrib) return invalid("relight_capture: null buffer");
+    if ((pbr || mask) && !background) return invalid("relight_capture: the pbr map and the mask need a background");
+    const CaptureMaps maps = {pbr, base_color, roughness, normal, visibility, diffuse, specular, lights, local_lights,
+                              global_lights, depth_var};
+    return guarded([&]() -> int {
+        launch_relight_capture((hipStream_t)stream_, width, height, feature, opacity, n_contrib, background, mask, maps);
+        return R3DG_OK;
+    });
+}
+
+int r3dg_eval_image_metrics(void* stream_, int width, int height, int channels, const float* pred, const float* gt,
+                            const float* mask, const float* fill, int fill_is_image, double* tile_sums, double* row)
+{
+    if (width < 1 || height < 1 || channels < 1 || channels > 3) return invalid("eval_image_metrics: bad shape");
+    if ((long long)width * height >= (1ll << 31)) return invalid("eval_image_metrics: image too large");
+    if (!pred || !gt || !tile_sums || !row) return invalid("eval_image_metrics: null buffer");
+    if (fill && !mask) return invalid("eval_image_metrics: a fill needs a mask");
+    return guarded([&]() -> int {
+        launch_eval_image_metrics((hipStream_t)stream_, width, height, channels, pred, gt, mask, fill, fill_is_image, tile_sums,
+                                  row);
+        return R3DG_OK;
+    });
+}
+
+int r3dg_eval_median_ratio(void* stream_, int width, int height, const float* pred, const float* gt, const float* mask,
+                           uint32_t* state, double* row)
+{
+    if (width < 0 || height < 0) return invalid("eval_median_ratio: bad shape");
+    if ((long long)width * height >= (1ll << 31)) return invalid("eval_median_ratio: image too large");
+    if (!state || !row) return invalid("eval_median_ratio: null buffer");
+    if ((long long)width * height != 0 && (!pred || !gt)) return invalid("eval_median_ratio: null image");
+    return guarded([&]() -> int {
+        launch_eval_median_ratio((hipStream_t)stream_, width, height, pred, gt, mask, state, row);
         return R3DG_OK;
     });
 }

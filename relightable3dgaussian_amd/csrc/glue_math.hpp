@@ -1,4 +1,5 @@
-// Scalar helpers of the glue kernels (stage2_glue.hip, stage1_glue.hip, smooth.hip): the sRGB curve, sigmoid, sign,
+// Scalar helpers of the glue kernels (stage2_glue.hip, stage1_glue.hip, smooth.hip, relight.hip, eval_capture.hip): the sRGB
+// curve, sigmoid, sign,
 // F.normalize and its backward, the adjoint weight of the replicate-padded Sobel stencil.
 #pragma once
 #include "common.hpp"
@@ -52,6 +53,16 @@ __device__ __forceinline__ float srgb_clip_derivative(float x)
     const float curve = lin ? 12.92f * x : 1.055f * srgb_pow(xs, 1.f / 2.4f) - 0.055f;
     if (!(curve >= 0.f && curve <= 1.f)) return 0.f;
     return lin ? 12.92f : 1.055f / 2.4f * srgb_pow(xs, 1.f / 2.4f - 1.f);
+}
+
+// the same curve as the relight / eval frame's kernels write it (relight.hip, eval_capture.hip): one comparison, no derivative
+__device__ __forceinline__ float srgb_of(float x)
+{
+    // rgb_to_srgb (utils/graphics_utils.py:207-213), clip=True
+    // (x^(1/2.4) as v_log_f32 * y -> v_exp_f32, ~4 ulp: the library powf is ~155 instructions per channel of every pixel)
+    const float p = __builtin_amdgcn_exp2f((1.0f / 2.4f) * __builtin_amdgcn_logf(fmaxf(x, 0.0031308f)));
+    const float y = x > 0.0031308f ? p * 1.055f - 0.055f : 12.92f * x;
+    return fminf(fmaxf(y, 0.f), 1.f);
 }
 
 // sum_d [clamp(q + d, 0, n-1) == p] * k[d+1]: weight with which position q's replicate-padded 1-D stencil reads position p

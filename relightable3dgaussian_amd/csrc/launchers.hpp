@@ -205,6 +205,21 @@ void launch_relight_pack(hipStream_t s, int P, const float* xyz, const float* vi
 void launch_relight_compose(hipStream_t s, int W, int H, float fx, float fy, float cx, float cy, const float* viewmatrix,
                             const float* tr, const float* env, int He, int We, const float* image, const float* opacity,
                             const float* feature, const int* n_contrib, float* pbr_env, float* render_env, float* env_only);
+// eval_capture.hip: the capture maps of an eval frame, each [3,HW] or [1,HW]; NULL = not wanted
+struct CaptureMaps {
+    float *pbr, *base_color, *roughness, *normal, *visibility, *diffuse, *specular, *lights, *local_lights, *global_lights,
+        *depth_var;
+};
+void launch_relight_capture(hipStream_t s, int W, int H, const float* feature, const float* opacity, const int* n_contrib,
+                            const float* background, const float* mask, const CaptureMaps& maps);
+// ssim.hip: the value-only SSIM tiling; tile_sums [C * ceil(W/32) * ceil(H/32)][2]
+void launch_eval_metric_tiles(hipStream_t s, int W, int H, int C, const float* pred, const float* gt, const float* mask,
+                              const float* fill, int fill_is_image, double* tile_sums);
+// eval_metrics.hip
+void launch_eval_image_metrics(hipStream_t s, int W, int H, int C, const float* pred, const float* gt, const float* mask,
+                               const float* fill, int fill_is_image, double* tile_sums, double* row);
+void launch_eval_median_ratio(hipStream_t s, int W, int H, const float* pred, const float* gt, const float* mask,
+                              uint32_t* state, double* row);
 size_t knn_temp_bytes(size_t P);
 void knn_dist2(hipStream_t s, int P, const float* pts, float* dists, void* temp);
 size_t bvh_build_temp_bytes(size_t P);                  // bvh_build.hip

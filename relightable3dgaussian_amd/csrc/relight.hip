@@ -13,6 +13,7 @@
 //                                    render_env = image + (1 - opacity) * srgb(env)
 //                                    env_only   = srgb(env)
 // Parity target: the PyTorch restatement in relightable3dgaussian_amd/relight.py (frame_reference).
+#include "glue_math.hpp"
 #include "launchers.hpp"
 #include "r3dg_hip.h"
 
@@ -46,15 +47,6 @@ relight_pack_features_kernel(int P, const float* __restrict__ xyz, const float* 
     float4* out = reinterpret_cast<float4*>(features + 28 * (size_t)i);      // 112-byte rows: 16-byte aligned
 #pragma unroll
     for (int q = 0; q < 7; q++) out[q] = make_float4(f[4 * q], f[4 * q + 1], f[4 * q + 2], f[4 * q + 3]);
-}
-
-__device__ __forceinline__ float srgb_of(float x)
-{
-    // rgb_to_srgb (utils/graphics_utils.py:207-213), clip=True
-    // (x^(1/2.4) as v_log_f32 * y -> v_exp_f32, ~4 ulp: the library powf is ~155 instructions per channel of every pixel)
-    const float p = __builtin_amdgcn_exp2f((1.0f / 2.4f) * __builtin_amdgcn_logf(fmaxf(x, 0.0031308f)));
-    const float y = x > 0.0031308f ? p * 1.055f - 0.055f : 12.92f * x;
-    return fminf(fmaxf(y, 0.f), 1.f);
 }
 
 struct RelightCam {

@@ -7,6 +7,10 @@
 //                         SSIM sum to *sum (one atomic per workgroup);
 //   ssim_backward_kernel  the window is symmetric, so dL/dx = scale * (W*dS/dmu1 + 2x W*dS/dE[x^2] + y W*dS/dE[xy])
 //                         with the same tiling over the three partial maps.
+//   eval_image_metrics_kernel   the forward kernel's tiling WITHOUT the partial-derivative writes, for scoring a held-out
+//                         view (evaluate.py): both images are composited onto a fill in the load stage (x * mask + fill * (1 - mask),
+//                         eval_relighting_syn4.py:161-186), and each workgroup writes its tile's sum of squared differences and
+//                         SSIM sum as two doubles -- no atomics; eval_metrics.hip adds them up in a fixed order.
 // HBM-bound streaming kernels: 5 map reads + 3 writes forward, 5 reads + 1 write backward per channel.
 #include "launchers.hpp"
 
@@ -41,10 +45,19 @@ struct SsimBatch {
     SsimImage im[2];
 };
 
-__global__ void __launch_bounds__(256)
-ssim_forward_kernel(int W, int H, int C, SsimBatch batch)
+// what the value-only (EVAL) variant composites in its load stage and where its tile totals go
+struct SsimEval {
+    const float* mask;     // [HW] or NULL (no compositing)
+    const float* fill;     // [C] colour / [C,HW] image or NULL (0)
+    int fill_is_image;
+    double* tile_sums;     // [workgroups][2]: sum of squared differences, SSIM sum
+};
+
+// One tile of the SSIM map.  EVAL = false: the training forward (partial derivatives written, the tile's sum added to I.sum).
+// EVAL = true: values only -- no partials, both images composited as they are loaded, totals written to E.tile_sums.
+template <bool EVAL>
+__device__ __forceinline__ void ssim_forward_tile(int W, int H, int C, const SsimImage I, const SsimEval E)
 {
-    const SsimImage I = batch.im[blockIdx.z / C];
     const float* __restrict__ x = I.x;
     const float* __restrict__ y = I.y;
     float* __restrict__ partials = I.partials;
@@ -73,7 +86,19 @@ ssim_forward_kernel(int W, int H, int C, SsimBatch batch)
             const int gy = by + r - SSIM_R, gx = bx + q - SSIM_R;
             const bool in = i < SSIM_E * SSIM_E && gx >= 0 && gx < W && gy >= 0 && gy < H;     // zero padding
             const size_t o = (size_t)(in ? gy : 0) * W + (in ? gx : 0);
-            const float vx = xc[o], vy = yc[o];
+            float vx = xc[o], vy = yc[o];
+            if constexpr (EVAL) {
+                if (E.mask != nullptr) {
+                    // x * mask + fill * (1 - mask), every operation rounded on its own as the PyTorch expression is
+#pragma clang fp contract(off)
+                    const float m = E.mask[o];
+                    const float f = E.fill == nullptr ? 0.f : (E.fill_is_image ? E.fill[c * HW + o] : E.fill[c]);
+                    const float fm = f * (1.f - m);
+                    const float xm = vx * m, ym = vy * m;
+                    vx = xm + fm;
+                    vy = ym + fm;
+                }
+            }
             xv[j] = in ? vx : 0.f;
             yv[j] = in ? vy : 0.f;
         }
@@ -87,6 +112,17 @@ ssim_forward_kernel(int W, int H, int C, SsimBatch batch)
         }
     }
     __syncthreads();
+    double sq_err = 0.0;        // EVAL: the thread's own four pixels, fp32 squares summed in double
+    if constexpr (EVAL) {
+        const int ex = threadIdx.x % SSIM_T, ey0 = (threadIdx.x / SSIM_T) * SSIM_B;
+#pragma unroll
+        for (int o = 0; o < SSIM_B; o++) {
+            if (bx + ex < W && by + ey0 + o < H) {
+                const float d = s_x[ey0 + o + SSIM_R][ex + SSIM_R] - s_y[ey0 + o + SSIM_R][ex + SSIM_R];
+                sq_err += (double)(d * d);
+            }
+        }
+    }
     float w[11];
 #pragma unroll
     for (int k = 0; k < 11; k++) w[k] = kSsimWin[k];
@@ -142,7 +178,7 @@ ssim_forward_kernel(int W, int H, int C, SsimBatch batch)
         }
     }
     float ssim_sum = 0.f;
-    float* pc = partials + (size_t)c * 3 * HW;
+    float* pc = EVAL ? nullptr : partials + (size_t)c * 3 * HW;
 #pragma unroll
     for (int o = 0; o < SSIM_B; o++) {
         const int py = by + ty0 + o;
@@ -156,15 +192,45 @@ ssim_forward_kernel(int W, int H, int C, SsimBatch batch)
             const float inv = 1.f / (C * D);
             const float ssim = A * B * inv;
             ssim_sum += ssim;
-            // partial derivatives of ssim w.r.t. mu1, E[x^2], E[xy] (treated as independent window averages)
-            const size_t off = (size_t)py * W + px;
-            pc[off] = 2.f * mu2 * (B - A) * inv - ssim * 2.f * mu1 * (D - C) * inv;
-            pc[HW + off] = -ssim / D;
-            pc[2 * HW + off] = 2.f * A * inv;
+            if constexpr (!EVAL) {
+                // partial derivatives of ssim w.r.t. mu1, E[x^2], E[xy] (treated as independent window averages)
+                const size_t off = (size_t)py * W + px;
+                pc[off] = 2.f * mu2 * (B - A) * inv - ssim * 2.f * mu1 * (D - C) * inv;
+                pc[HW + off] = -ssim / D;
+                pc[2 * HW + off] = 2.f * A * inv;
+            }
         }
     }
     const float tot = block_sum_256(ssim_sum, s_part);
-    if (threadIdx.x == 0 && sum != nullptr) atomicAdd(sum_slot(sum), tot);
+    if constexpr (!EVAL) {
+        if (threadIdx.x == 0 && sum != nullptr) atomicAdd(sum_slot(sum), tot);
+    } else {
+        // the squared error: butterfly over the wave, then the four waves in order -- the same order on every run
+        __shared__ double s_sq[4];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sq_err += __shfl_xor(sq_err, o, 64);
+        if ((threadIdx.x & 63) == 0) s_sq[threadIdx.x >> 6] = sq_err;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const size_t wg = blockIdx.x + (size_t)gridDim.x * (blockIdx.y + (size_t)gridDim.y * blockIdx.z);
+            E.tile_sums[2 * wg] = ((s_sq[0] + s_sq[1]) + s_sq[2]) + s_sq[3];
+            E.tile_sums[2 * wg + 1] = (double)tot;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256)
+ssim_forward_kernel(int W, int H, int C, SsimBatch batch)
+{
+    const SsimImage I = batch.im[blockIdx.z / C];
+    ssim_forward_tile<false>(W, H, C, I, SsimEval{});
+}
+
+// blockIdx.z = channel of ONE image pair
+__global__ void __launch_bounds__(256)
+eval_image_metrics_kernel(int W, int H, int C, SsimImage I, SsimEval E)
+{
+    ssim_forward_tile<true>(W, H, C, I, E);
 }
 
 __global__ void __launch_bounds__(256)
@@ -292,6 +358,16 @@ void launch_ssim_forward(hipStream_t s, int W, int H, int C, int n_images, const
     dim3 grid((W + SSIM_T - 1) / SSIM_T, (H + SSIM_T - 1) / SSIM_T, C * n_images);
     ssim_forward_kernel<<<grid, 256, 0, s>>>(W, H, C, b);
     check_launch(s, false, "ssim_forward_kernel");
+}
+
+void launch_eval_metric_tiles(hipStream_t s, int W, int H, int C, const float* pred, const float* gt, const float* mask,
+                              const float* fill, int fill_is_image, double* tile_sums)
+{
+    const SsimImage I = {pred, gt, nullptr, nullptr, nullptr, 0.f};
+    const SsimEval E = {mask, fill, fill_is_image, tile_sums};
+    dim3 grid((W + SSIM_T - 1) / SSIM_T, (H + SSIM_T - 1) / SSIM_T, C);
+    eval_image_metrics_kernel<<<grid, 256, 0, s>>>(W, H, C, I, E);
+    check_launch(s, false, "eval_image_metrics_kernel");
 }
 
 void launch_ssim_backward(hipStream_t s, int W, int H, int C, int n_images, const float* const* x, const float* y,

@@ -5,7 +5,8 @@ row, the rasterizer forward and the environment composites.
 `RelightRenderer.frame` runs the whole frame through the C ABI -- activations + view directions (r3dg_stage2_activate),
 r3dg_shade_forward, r3dg_relight_pack_features, the rasterizer forward, r3dg_relight_compose -- five streaming passes
 around the two hot kernels where the reference (and `frame_reference` below, the parity target) spends a few dozen
-PyTorch elementwise launches.  Replicas only under multi-GPU: frames are independent, no collective.
+PyTorch elementwise launches.  The capture maps of neilf.py:146-182 (CAPTURE_MAPS) come from one more pass over the feature
+image, r3dg_relight_capture, when a caller asks for them.  Replicas only under multi-GPU: frames are independent, no collective.
 """
 import math
 
@@ -14,6 +15,12 @@ import torch.nn.functional as F
 
 from . import _lib, rasterizer_ops, sampling, shading_ops
 from .train_step import rgb_to_srgb, update_visibility   # noqa: F401  (rgb_to_srgb: part of this module's surface)
+
+
+# the maps render_view(is_training=False) derives from the feature image (neilf.py:146-182) and their channel counts
+CAPTURE_MAPS = {"pbr": 3, "base_color": 3, "roughness": 1, "normal": 3, "visibility": 1, "diffuse": 3, "specular": 3, "lights": 3,
+                "local_lights": 3, "global_lights": 3, "depth_var": 1}
+COMPOSITES = ("pbr_env", "render_env", "env_only")
 
 
 def _shs_of(model):
@@ -53,8 +60,11 @@ class RelightRenderer:
     SH colour (`shs` or `features_dc`/`features_rest`) and incident light (`incidents` or `incidents_dc`/`_rest`) --
     bench_core.GaussianParams and fused_step.FusedStage2Step both do.  `envmap` [He,We,3] HDR (EnvLight.envmap)."""
 
-    def __init__(self, model, envmap, sample_num, process_group=None, cache="transport", regenerate_dirs=True):
-        """`cache` -- what is kept between frames while the light does not change:
+    def __init__(self, model, envmap, sample_num, process_group=None, cache="transport", regenerate_dirs=True,
+                 base_color_scale=None):
+        """`base_color_scale` [3] (None: nothing changes): multiplies the ACTIVATED base colour before shading and packing, as
+        GaussianModel.get_base_color does with the per-scene albedo scale that eval_relighting_syn4.py:96-103 sets.
+        `cache` -- what is kept between frames while the light does not change:
         "transport" (default): the whole view-independent part of the integral -- per sample (local + global light) x area
             x n.d, per Gaussian diffuse_light and the mean light / visibility columns -- so that a frame evaluates only the
             GGX lobe (r3dg_shade_forward_transport; 12 bytes and ~80 instructions per sample).  Valid while parameters,
@@ -81,6 +91,9 @@ class RelightRenderer:
         self.base_color, self.roughness = d(model.base_color), d(model.roughness)
         self.shs, self.incidents = d(_shs_of(model)), d(_incidents_of(model))
         self.envmap = d(envmap)
+        self.base_color_scale = None
+        if base_color_scale is not None:
+            self.base_color_scale = torch.as_tensor(base_color_scale, dtype=torch.float32).to(self.xyz.device).reshape(3).clone()
         if self.envmap.dim() != 3 or self.envmap.shape[2] != 3:
             raise RuntimeError("envmap must be [He,We,3]")
         for t in (self.xyz, self.envmap):
@@ -200,6 +213,8 @@ class RelightRenderer:
                 self.a_opacity.data_ptr(), self.a_normal.data_ptr(), self.a_base.data_ptr(), self.a_rough.data_ptr(),
                 self.a_viewdirs.data_ptr(), None, None)
         _lib.check(st, "stage2_activate")
+        if self.base_color_scale is not None:
+            self.a_base.mul_(self.base_color_scale)
 
     def _shade_cached(self, L, stream, P, He, We, tr, taps):
         _lib.check(L.r3dg_shade_forward_cached(
@@ -212,10 +227,14 @@ class RelightRenderer:
             self.shade_out.data_ptr()), "shade_forward")
 
     @torch.no_grad()
-    def frame(self, cam, bg, env_transform=None, outputs=("pbr_env",)):
+    def frame(self, cam, bg, env_transform=None, outputs=("pbr_env",), mask=None, capture_background=None):
         """-> dict with the rasterizer's public outputs ("render", "opacity", "depth", "feature", "pseudo_normal",
-        "num_rendered", "num_contrib", "radii") and the requested composites out of "pbr_env", "render_env", "env_only"
-        (neilf.py:203-207), each [3,H,W]."""
+        "num_rendered", "num_contrib", "radii") and the requested `outputs`: the composites "pbr_env", "render_env", "env_only"
+        (neilf.py:203-207), each [3,H,W], and the capture maps of CAPTURE_MAPS (neilf.py:146-182: "pbr", "base_color",
+        "roughness", "normal", "visibility", "diffuse", "specular", "lights", "local_lights", "global_lights", "depth_var";
+        [3,H,W] or [1,H,W]), which one r3dg_relight_capture launch serves.  `capture_background` [3] (default: `bg`) is the
+        colour under "pbr"; with `mask` [H,W] every capture map but depth_var is composited as map * mask + (1 - mask) *
+        capture_background (eval_relighting_syn4.py:161-167)."""
         L = _lib.lib()
         P, dev = self.P, self.dev
         H, W = cam.image_height, cam.image_width
@@ -255,9 +274,9 @@ class RelightRenderer:
             R, n_contrib, image, opacity, depth, feature, pseudo_normal, sxyz, weights, radii = fw[:10]
             res = dict(num_rendered=R, num_contrib=n_contrib, render=image, opacity=opacity, depth=depth, feature=feature,
                        pseudo_normal=pseudo_normal, surface_xyz=sxyz, radii=radii)
-            want = {k: torch.empty(3, H, W, dtype=torch.float32, device=dev) for k in outputs}
+            want = {k: torch.empty(3, H, W, dtype=torch.float32, device=dev) for k in outputs if k not in CAPTURE_MAPS}
             for k in want:
-                if k not in ("pbr_env", "render_env", "env_only"):
+                if k not in COMPOSITES:
                     raise RuntimeError("unknown relight output %r" % k)
             if want:
                 g = lambda k: want[k].data_ptr() if k in want else None
@@ -266,6 +285,17 @@ class RelightRenderer:
                     _lib.ptr(tr), self.envmap.data_ptr(), He, We, image.data_ptr(), opacity.data_ptr(),
                     feature.data_ptr(), n_contrib.data_ptr(), g("pbr_env"), g("render_env"), g("env_only")),
                     "relight_compose")
+            maps = {k: torch.empty(CAPTURE_MAPS[k], H, W, dtype=torch.float32, device=dev) for k in outputs if k in CAPTURE_MAPS}
+            if maps:
+                g = lambda k: maps[k].data_ptr() if k in maps else None
+                cbg = torch.as_tensor(bg if capture_background is None else capture_background,
+                                      dtype=torch.float32).to(dev).reshape(3).contiguous()
+                m = None if mask is None else torch.as_tensor(mask, dtype=torch.float32).to(dev).reshape(H, W).contiguous()
+                _lib.check(L.r3dg_relight_capture(
+                    stream(), W, H, feature.data_ptr(), opacity.data_ptr(), n_contrib.data_ptr(), cbg.data_ptr(), _lib.ptr(m),
+                    g("pbr"), g("base_color"), g("roughness"), g("normal"), g("visibility"), g("diffuse"), g("specular"),
+                    g("lights"), g("local_lights"), g("global_lights"), g("depth_var")), "relight_capture")
+                want.update(maps)
             res.update(want)
         return res
 
@@ -309,6 +339,8 @@ def frame_reference(renderer, cam, bg, env_transform=None, exact_activations=Fal
         normal = F.normalize(r.normal, dim=-1, eps=1e-3)
         opacity_a, scales, rot = torch.sigmoid(r.opacity), torch.exp(r.scaling), F.normalize(r.rotation)
         viewdirs = F.normalize(cam.camera_center - r.xyz, dim=-1)
+        if getattr(r, "base_color_scale", None) is not None:
+            base_color = base_color * r.base_color_scale
     tr = None if env_transform is None else env_transform.to(r.dev, torch.float32).contiguous()
     pbr, diffuse, rest = shading_ops.shade(base_color, roughness, normal, viewdirs, r.incidents, r.envmap, r.visibility,
                                            r.incident_dirs, r.incident_areas, tr)
@@ -323,7 +355,7 @@ def frame_reference(renderer, cam, bg, env_transform=None, exact_activations=Fal
     _, n_contrib, image, opacity, depth, feature, pn, sxyz, weights, radii = outs
     feat = feature / opacity.clamp_min(1e-5) * (n_contrib > 0)
     env_rgb = env_directions(cam, r.envmap, tr)
-    return dict(render=image, opacity=opacity, feature=feature, num_rendered=outs[0],
+    return dict(render=image, opacity=opacity, feature=feature, num_rendered=outs[0], num_contrib=n_contrib,
                 pbr_env=rgb_to_srgb(feat[2:5] * opacity + (1 - opacity) * env_rgb),
                 render_env=image + (1 - opacity) * rgb_to_srgb(env_rgb), env_only=rgb_to_srgb(env_rgb))
 
