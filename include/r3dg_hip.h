@@ -601,6 +601,51 @@ int r3dg_stage1_activate_backward(void* stream, int P, const float* d_xyz, const
                                   float* d_g_xyz, float* d_g_scaling, float* d_g_rotation, float* d_g_opacity,
                                   float* d_g_normal);
 
+/* Loss terms of the reference's OptimizationParams that no run script switches on (csrc/supervision.hip): the MVS depth / normal
+ * supervision of stage 2 and the depth-smoothness and per-Gaussian terms of stage 1.  All maps [C,H,W] fp32; throughout
+ * X = feature_X / max(opacity, 1e-5) * (n_contrib > 0) with the quotient rule and clamp convention of r3dg_stage2_loss's normal
+ * term.  Each call ADDS to gradient buffers the existing kernels wrote and runs behind them; a zero weight switches its term
+ * off, and with every weight zero the call returns without a launch.
+ * r3dg_supervision_count: *d_count (one uint32, WRITTEN) = number of pixels with (image_mask != 0) == (gt_depth > 0), the
+ *   ~sur_mask of neilf.py:243-247; d_gt_depth [HW], d_image_mask [HW] (NULL = all ones).  Integer adds only: the same bits on
+ *   every run.  Depends on the view alone, not on the render.
+ * r3dg_stage2_supervision: the two image-space terms of neilf.py:241-249 and :266-273 on the S=16 training feature image:
+ *     w_depth / count * sum_sel |depth - gt_depth|          depth = map 0, sel as counted above, count = *d_count
+ *   + w_normal_mvs * sum_c (normal_c dm - mvs_normal_c dm)^2   normal = maps 5..7, dm = (gt_depth > 0); the weight carries the
+ *                                                              1 / (3 H W) of F.mse_loss
+ *   sign(0) = 0 as in PyTorch's L1 backward.  count == 0: the depth term is zero in value and gradient (PyTorch returns NaN, the
+ *   mean over nothing: the one deliberate difference).  d_mvs_normal [3,HW] (may be NULL when w_normal_mvs == 0), d_count (may
+ *   be NULL when w_depth == 0).  d_dL_dopacity [HW] is ADDED to; of d_dL_dfeature [16,HW] map 0 is WRITTEN (w_depth != 0) and
+ *   maps 5..7 (w_normal_mvs != 0) are written (accumulate_normal == 0) or added to (!= 0: an earlier kernel wrote them), as
+ *   r3dg_stage2_smooth_fused does; d_sums2[0] += sum_sel |depth - gt_depth|, d_sums2[1] += the squared-difference sum (two
+ *   quantities of R3DG_SUM_SLOTS floats, unweighted).
+ * r3dg_stage1_depth_smooth: lambda_depth_smooth * first_order_edge_aware_loss(depth, gt) (render.py:175-179), depth = map 3 of
+ *   the S=5 image, Sobel / 8 with replicate padding as the normal-smoothness term of r3dg_stage1_loss; the weight carries the
+ *   1 / (3 H W).  Call after r3dg_stage1_loss: map 3 of d_dL_dfeature [5,HW] and d_dL_dopacity are ADDED to; d_edge_scratch
+ *   [2*HW] floats; *d_sum (R3DG_SUM_SLOTS floats) += the unweighted sum.
+ * r3dg_stage1_gaussian_terms: the per-Gaussian terms of render.py:181-197 and :215-219, each weight carrying the 1 / P:
+ *     w_point_entropy sum_p w_p (-o log(o + 1e-10) - (1 - o) log(1 - o + 1e-10))
+ *   + w_orientation   sum_p min(w_p, 1) max(n_p . d_p, 0),  d = normalize(xyz - campos)   (the caller gates it on the iteration)
+ *   + w_scaling       sum_p sum_axis |s - mean_axis s|                                    (the caller applies the schedule)
+ *   d_weights [P] = the rasterizer's blend weights (a constant), d_opacity [P], d_normal [P,3], d_scales [P,3]: ACTIVATED values.
+ *   Call between the rasterizer backward and r3dg_stage1_activate_backward; ADDED to: d_dL_dopacity [P], d_dL_dscales [P,3],
+ *   d_dL_dmeans3D [P,3] (orientation, through d) and columns 0..2 of d_dL_dfeatures [P,5] (orientation: the feature row's normal
+ *   columns are the activated normal).  d_sums3[0..2] += the three unweighted sums (R3DG_SUM_SLOTS floats each; one add per
+ *   wave).  Buffers of a term whose weight is zero may be NULL. */
+int r3dg_supervision_count(void* stream, int width, int height, const float* d_gt_depth, const float* d_image_mask,
+                           uint32_t* d_count);
+int r3dg_stage2_supervision(void* stream, int width, int height, const float* d_opacity, const float* d_feature,
+                            const int32_t* d_n_contrib, const float* d_gt_depth, const float* d_mvs_normal,
+                            const float* d_image_mask, const uint32_t* d_count, float w_depth, float w_normal_mvs,
+                            int accumulate_normal, float* d_dL_dopacity, float* d_dL_dfeature, float* d_sums2);
+int r3dg_stage1_depth_smooth(void* stream, int width, int height, const float* d_opacity, const float* d_feature,
+                             const int32_t* d_n_contrib, const float* d_gt, float w_depth_smooth, float* d_edge_scratch,
+                             float* d_dL_dopacity, float* d_dL_dfeature, float* d_sum);
+int r3dg_stage1_gaussian_terms(void* stream, int P, const float* d_weights, const float* d_opacity, const float* d_normal,
+                               const float* d_scales, const float* d_xyz, const float* d_campos, float w_point_entropy,
+                               float w_orientation, float w_scaling, float* d_dL_dopacity, float* d_dL_dfeatures,
+                               float* d_dL_dscales, float* d_dL_dmeans3D, float* d_sums3);
+
 /* Learnable environment texture (DirectLightMap, scene/direct_light_map.py:18-27): env = softplus(raw), [He,We,3].
  * g_raw = (dL_denv + w_tv * dTV(env)/denv) * softplus'(raw) with TV = mean (d/dh)^2 + mean (d/dw)^2 (tv_loss, utils/loss_utils.py:113-117: the env-smoothness term,
  * neilf.py:294-300); *tv_sum (may be NULL) += TV(env).  consume != 0: dL_denv is zeroed after it was read, so the

@@ -7,7 +7,7 @@ import torch
 from . import _lib, densify, rasterizer_ops
 from .fused_adam import FusedAdam
 from .fused_base import SUM_SLOTS, FusedStepBase, _in_context, _world_of, grad_slab, learning_rates
-from .train_step import LAMBDA_DSSIM, STAGE1_WEIGHTS, depth_var_weight
+from .train_step import LAMBDA_DSSIM, STAGE1_WEIGHTS, depth_var_weight, scaling_weight
 
 
 class FusedStage1Step(FusedStepBase):
@@ -18,7 +18,8 @@ class FusedStage1Step(FusedStepBase):
 
     _opt_order = ("xyz", "normal", "scaling", "rotation", "opacity", "shs")
 
-    def __init__(self, params, lr=1e-4, lr_rest_scale=1.0, process_group=None, lrs=None, loss_weights=None, bounded=True):
+    def __init__(self, params, lr=1e-4, lr_rest_scale=1.0, process_group=None, lrs=None, loss_weights=None, bounded=True,
+                 iterations=30_000):
         """`bounded`: as FusedStage2Step -- after the first iteration (and again after every densify / prune, which changes
         the count) the rasterizer forward runs without the host read-back of num_rendered; a dropped view updates nothing
         and adds nothing to the densification statistics.
@@ -26,12 +27,17 @@ class FusedStage1Step(FusedStepBase):
         GaussianModel.training_setup (gaussian_model.py:465-472; fused_base.learning_rates).
         `loss_weights`: overrides of train_step.STAGE1_WEIGHTS (the lambdas of script/run_nerf.sh:7-14).
         `self.iteration` (the reference's 1-based iteration, advanced by __call__) drives the depth-variance schedule
-        (render.py:202)."""
+        (render.py:202), the orientation term's gate (:191) and, with `iterations` (the run's length, OptimizationParams.iterations),
+        the scaling term's schedule (:218).  The terms no run script uses -- depth_smooth, point_entropy, orientation, scaling
+        (csrc/supervision.hip) -- are 0 by default; nothing of them is allocated or launched then."""
         super().__init__(params, self._opt_order[:-1], process_group, *_world_of(process_group), bounded, order_stream=None)
         self.w = dict(STAGE1_WEIGHTS)
         if loss_weights:
             self.w.update(loss_weights)
-        self.iteration = 0
+        self.iteration, self.iterations = 0, int(iterations)
+        # the terms beside r3dg_stage1_loss: their sum slots follow the six of that kernel (depth smoothness | point entropy,
+        # orientation, scaling)
+        self._extra_terms = any(self.w[k] != 0.0 for k in ("depth_smooth", "point_entropy", "orientation", "scaling"))
         rate, tail = learning_rates(lr, lrs, lr_rest_scale)
         two_rates = dict(lr_tail=tail("shs"), period=3 * self.M, split=3)
         self.opt = FusedAdam([dict(param=getattr(self, k), lr=rate(k), **(two_rates if k == "shs" else {})) for k in self._opt_order])
@@ -47,7 +53,7 @@ class FusedStage1Step(FusedStepBase):
         self.a_scales, self.a_rot = torch.empty(P, 3, **f), torch.empty(P, 4, **f)
         self.a_opacity, self.a_normal = torch.empty(P, 1, **f), torch.empty(P, 3, **f)
         self.features = torch.empty(P, 5, **f)
-        self.sums = torch.zeros(6, SUM_SLOTS, **f)          # (R3DG_SUM_SLOTS floats each) l1, normal mse, mask entropy, SSIM(image), edge-aware normal, sqrt depth var
+        self.sums = torch.zeros(10 if self._extra_terms else 6, SUM_SLOTS, **f)          # (R3DG_SUM_SLOTS floats each) l1, normal mse, mask entropy, SSIM(image), edge-aware normal, sqrt depth var
         # the overflow flag of the bounded forward at the end: reduced with the gradients
         order = ("shs", "xyz", "normal", "scaling", "rotation", "opacity", "flag")
         self.grad_flat, self.grads, _ = grad_slab(order, {k: getattr(self, k) for k in order[:-1]}, self.dev)
@@ -114,6 +120,14 @@ class FusedStage1Step(FusedStepBase):
         self._drain()
         self.grads["opacity"].zero_()
 
+    def _extra_weights(self, N):
+        """The weights of the four terms of csrc/supervision.hip, each divided by the element count of its mean: depth smoothness,
+        point entropy, orientation (0 until iteration > orientation_from_iter, render.py:191), scaling (its schedule, :218)."""
+        w, P = self.w, max(self.P, 1)
+        gate = self.iteration > w["orientation_from_iter"]
+        return (w["depth_smooth"] / (3.0 * N), w["point_entropy"] / P, w["orientation"] / P if gate else 0.0,
+                scaling_weight(w["scaling"], self.iteration, self.iterations) / P)
+
     def _weights(self, N):
         """The five weights of r3dg_stage1_loss / loss(), each already divided by the element count of its mean."""
         w = self.w
@@ -168,14 +182,28 @@ class FusedStage1Step(FusedStepBase):
                 n_contrib.data_ptr(), gt_c.data_ptr(), _lib.ptr(mask_c), w_l1, w_ent, w_nrm, w_smooth, w_var,
                 g[18:21].data_ptr(), g[21:27].data_ptr(), g[0:3].data_ptr(), g[3:4].data_ptr(), g[4:9].data_ptr(),
                 self.sums.data_ptr()), "stage1_loss")
+            w_ds, w_pe, w_or, w_sc = self._extra_weights(N) if self._extra_terms else (0.0, 0.0, 0.0, 0.0)
+            if w_ds != 0.0:
+                # behind the loss kernel: adds to the depth map's gradient and the opacity gradient it wrote
+                edge = torch.empty((2, H, W), dtype=torch.float32, device=dev)
+                _lib.check(L.r3dg_stage1_depth_smooth(
+                    stream(), W, H, opacity.data_ptr(), feature.data_ptr(), n_contrib.data_ptr(), gt_c.data_ptr(), w_ds,
+                    edge.data_ptr(), g[3:4].data_ptr(), g[4:9].data_ptr(), self.sums[6].data_ptr()), "stage1_depth_smooth")
             bw = rasterizer_ops.rasterize_gaussians_backward(
                 bg, self.xyz, self.features, radii, empty, self.a_scales, self.a_rot, 1.0, empty, vm,
                 cam.full_proj_transform, cam.tanfovx, cam.tanfovy, g[0:3], g[3:4], empty, g[4:9],        # (empty: no depth gradient)
                 self.shs, 3, campos, geom, R, binning, img, True, False, dL_dsh_out=self.grads["shs"],
                 # the normal maps carry the two normal terms, depth / depth^2 the variance term
-                active_features=(0, 1, 2, 3, 4) if w_var != 0.0 else (0, 1, 2))
+                active_features=(0, 1, 2, 3, 4) if w_var != 0.0 else ((0, 1, 2, 3) if w_ds != 0.0 else (0, 1, 2)))
             dL_dmeans2D, _dcol, dL_dopacity, dL_dmeans3D, dL_dfeatures, _dcov, _dsh, dL_dscales, dL_drot = bw
             gr = self.grads
+            if w_pe != 0.0 or w_or != 0.0 or w_sc != 0.0:
+                # between the rasterizer backward and the chain rule: adds to the activated-space gradients the latter consumes
+                _lib.check(L.r3dg_stage1_gaussian_terms(
+                    stream(), P, weights.data_ptr(), self.a_opacity.data_ptr(), self.a_normal.data_ptr(),
+                    self.a_scales.data_ptr(), self.xyz.data_ptr(), campos.data_ptr(), w_pe, w_or, w_sc, dL_dopacity.data_ptr(),
+                    dL_dfeatures.data_ptr(), dL_dscales.data_ptr(), dL_dmeans3D.data_ptr(), self.sums[7].data_ptr()),
+                    "stage1_gaussian_terms")
             _lib.check(L.r3dg_stage1_activate_backward(
                 stream(), P, self.xyz.data_ptr(), self.scaling.data_ptr(), self.rotation.data_ptr(),
                 self.opacity.data_ptr(), self.normal.data_ptr(), vm.data_ptr(), dL_dfeatures.data_ptr(),
@@ -194,7 +222,8 @@ class FusedStage1Step(FusedStepBase):
         N = self._N
         lam = LAMBDA_DSSIM
         w_l1, w_ent, w_nrm, w_smooth, w_var = self._weights(N)
-        w = torch.tensor([w_l1, w_nrm, w_ent, -lam * self.w["l1"] / (3.0 * N), w_smooth, w_var], device=self.dev)
+        w = torch.tensor([w_l1, w_nrm, w_ent, -lam * self.w["l1"] / (3.0 * N), w_smooth, w_var] +
+                         (list(self._extra_weights(N)) if self._extra_terms else []), device=self.dev)
         return (self.sums.sum(1) * w).sum() + lam * self.w["l1"]
 
     @_in_context

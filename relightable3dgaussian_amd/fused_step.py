@@ -10,7 +10,8 @@ csrc/stage2_glue.hip, smooth.hip and adam.hip and without an autograd graph: for
     rasterize                                 r3dg_rasterize_forward_*         (r3dg_rasterization.py:75-113)
     pseudo normals + sRGB-mapped PBR image    r3dg_stage2_normals_srgb
     SSIM of the image and the PBR image       r3dg_ssim_forward_pair / r3dg_ssim_backward_pair
-    image-space loss terms + their gradients  r3dg_stage2_loss (+ r3dg_stage2_smooth_fused)  (neilf.py:212-318)
+    image-space loss terms + their gradients  r3dg_stage2_loss (+ r3dg_stage2_smooth_fused, + r3dg_stage2_supervision when the
+                                              MVS depth / normal terms are on)  (neilf.py:212-318)
     rasterize backward                        r3dg_rasterize_backward_*
     feature grads -> shading upstream grads   r3dg_stage2_unpack_gradients
     shading backward                          r3dg_shade_frs_backward / r3dg_shade_backward_cached
@@ -44,7 +45,7 @@ from .train_step import FROZEN_GEOMETRY_GROUPS, LAMBDA_DSSIM, STAGE2_WEIGHTS, up
 PARAM_NAMES = ("xyz", "normal", "scaling", "rotation", "opacity", "shs", "base_color", "roughness", "incidents", "env")
 
 # what the phases of forward_backward see of the view (`main` / `raw`: the caller's stream, looked up ONCE: 10 us of Python each)
-_View = collections.namedtuple("_View", "cam bg gt mask H W N vm campos main raw order_stream")
+_View = collections.namedtuple("_View", "cam bg gt mask H W N vm campos main raw order_stream gt_depth mvs_normal")
 
 
 class FusedStage2Step(FusedStepBase):
@@ -66,6 +67,9 @@ class FusedStage2Step(FusedStepBase):
         it in `dropped_steps`.
         `loss_weights`: overrides of train_step.STAGE2_WEIGHTS (the lambdas of script/run_nerf.sh:20-39);
         train_step.STAGE2_WEIGHTS_SYN4 adds the three edge-aware smoothness terms of script/run_syn4.sh / run_dtu.sh.
+        `depth` / `normal_mvs_depth` (lambda_depth / lambda_normal_mvs_depth, neilf.py:241-249, :266-273; 0 by default) switch on
+        the supervision by the view's MVS depth map and normals, which forward_backward / __call__ then take as `gt_depth` /
+        `mvs_normal` (csrc/supervision.hip); with both at 0 nothing of it is allocated or launched.
         FROZEN GEOMETRY: a group whose learning rate(s) are 0 gets no Adam launch; when ALL of xyz, normal, scaling,
         rotation, opacity and shs are frozen (run_syn4.sh:27-33, run_dtu.sh:29-35) the iteration also skips what only they
         would consume -- the alpha-gradient half of the tile backward and the whole per-Gaussian geometry backward
@@ -100,7 +104,11 @@ class FusedStage2Step(FusedStepBase):
         self.features = torch.empty(P, 16, **f)
         # unweighted sums: l1, pbr l1, normal mse, light l1, TV(env), SSIM(image), SSIM(pbr), and the three edge-aware
         # smoothness sums (base colour, roughness, diffuse light)
-        self.sums = torch.zeros(10, SUM_SLOTS, **f)       # R3DG_SUM_SLOTS floats per quantity (include/r3dg_hip.h)
+        # (+ with an MVS term on: the depth L1 sum over the selected pixels, the squared MVS-normal difference sum)
+        self._supervised = self.w["depth"] != 0.0 or self.w["normal_mvs_depth"] != 0.0
+        self.sums = torch.zeros(12 if self._supervised else 10, SUM_SLOTS, **f)   # R3DG_SUM_SLOTS floats per quantity (include/r3dg_hip.h)
+        self._sup_counts = {}                       # id(gt_depth) -> (gt_depth, image mask, their versions, the device count)
+        self._sup_count_cur = None                  # the count the last forward_backward's depth term divided by
         self.d_pbr, self.d_diffuse = torch.empty(P, 3, **f), torch.empty(P, 3, **f)
         self._absmax = torch.zeros((P + 255) // 256, **f)       # block maxima of |d_pbr|, |d_diffuse| (unpack kernel)
         # flat gradient slab: [shs 3M | xyz3 normal3 scaling3 rotation4 opacity1 base3 rough1 per Gaussian, env texture |
@@ -303,9 +311,12 @@ class FusedStage2Step(FusedStepBase):
         return self._early_stream()
 
     @_in_context
-    def forward_backward(self, cam, bg, gt, early_adam=False, image_mask=None, split_geometry=None, chain_incidents=False):
+    def forward_backward(self, cam, bg, gt, early_adam=False, image_mask=None, split_geometry=None, chain_incidents=False,
+                         gt_depth=None, mvs_normal=None):
         """One forward + loss + backward; gradients land in self.grads.  Returns the rasterizer's 10 public outputs.
         `image_mask` [1,H,W]: the view's object mask (Camera.image_mask; None = all ones) of the normal and smoothness terms.
+        `gt_depth` [1,H,W], `mvs_normal` [3,H,W]: the view's MVS depth map and the normals derived from it (Camera.depth /
+        Camera.normal); required by the `depth` / `normal_mvs_depth` terms (both need the depth map), ignored without them.
         `early_adam` (single-GPU whole iterations only, see __call__): the SH colour coefficients, whose gradient is final
         after the rasterizer backward, get their Adam update on a side stream UNDER the shading backward (an HBM-bound,
         register-light kernel next to a VALU-bound one); optimizer_step() then updates the remaining groups.
@@ -316,9 +327,12 @@ class FusedStage2Step(FusedStepBase):
         the rotated frame for the chain kernel that optimizer_step launches -- a caller of a bare forward_backward reads
         grads["incidents"] in the world frame, always."""
         H, W = cam.image_height, cam.image_width
+        if self._supervised and (gt_depth is None or (self.w["normal_mvs_depth"] != 0.0 and mvs_normal is None)):
+            raise RuntimeError("FusedStage2Step: the depth / normal_mvs_depth terms need gt_depth%s" % (
+                "" if self.w["normal_mvs_depth"] == 0.0 else " and mvs_normal"))
         main = torch.cuda.current_stream(self.dev)
         v = _View(cam, bg, gt, image_mask, H, W, H * W, cam.world_view_transform.contiguous(), cam.camera_center.contiguous(),
-                  main, main.cuda_stream, None if self.serial_streams else self._order_stream)
+                  main, main.cuda_stream, None if self.serial_streams else self._order_stream, gt_depth, mvs_normal)
         with torch.cuda.device(self.dev):
             pending, env_c, flag_cur, use_bounded, rotated_for = self._front_end(v)
             taps, packed = self._shade_forward(v, env_c, rotated_for)
@@ -461,8 +475,33 @@ class FusedStage2Step(FusedStepBase):
             active += ([8, 9, 10] if w_bc != 0.0 else []) + ([11] if w_r != 0.0 else [])
             if w_ls != 0.0:
                 active += [12, 13, 14] + ([5, 6, 7] if self.w["normal"] == 0.0 else [])
+        if self._supervised:
+            # the MVS terms behind both: map 0 is theirs alone, the normal maps are added to when a kernel above wrote them
+            w_d, w_nm = self.w["depth"], self.w["normal_mvs_depth"] / (3.0 * N)
+            depth_c = v.gt_depth.contiguous()
+            mvs_c = None if w_nm == 0.0 else v.mvs_normal.contiguous()
+            self._sup_count_cur = self._supervision_count(v, depth_c, mask_c) if w_d != 0.0 else None
+            _lib.check(L.r3dg_stage2_supervision(v.raw, W, H, opacity.data_ptr(), feature.data_ptr(), n_contrib.data_ptr(),
+                depth_c.data_ptr(), _lib.ptr(mvs_c), _lib.ptr(mask_c), _lib.ptr(self._sup_count_cur), w_d, w_nm,
+                1 if 5 in active else 0, g[3:4].data_ptr(), g[4:20].data_ptr(), self.sums[10].data_ptr()), "stage2_supervision")
+            active += ([0] if w_d != 0.0 else []) + ([5, 6, 7] if w_nm != 0.0 and 5 not in active else [])
         self.last_active_features = sorted(set(active))
         return g, active
+
+    def _supervision_count(self, v, depth_c, mask_c):
+        """The number of pixels the depth term averages over (r3dg_supervision_count), on the device.  It depends on the view's
+        depth map and object mask alone, so it is computed once per (depth map, mask) pair and kept for as long as both tensors
+        are unchanged (held here, so a new tensor can never pass for a dropped one at the same address)."""
+        key = id(v.gt_depth)
+        hit = self._sup_counts.get(key)
+        mv = None if v.mask is None else v.mask._version
+        if hit is not None and hit[0] is v.gt_depth and hit[1] is v.mask and hit[2] == (v.gt_depth._version, mv):
+            return hit[3]
+        count = torch.empty(1, dtype=torch.int32, device=self.dev)
+        _lib.check(_lib.lib().r3dg_supervision_count(v.raw, v.W, v.H, depth_c.data_ptr(), _lib.ptr(mask_c), count.data_ptr()),
+                   "supervision_count")
+        self._sup_counts[key] = (v.gt_depth, v.mask, (v.gt_depth._version, mv), count)
+        return count
 
     def _raster_backward(self, v, fw, g, active, split_geometry):
         """-> (dL_dfeatures, ALL outputs of the geometry backward or None with frozen geometry, the stream the geometry backward
@@ -472,8 +511,9 @@ class FusedStage2Step(FusedStepBase):
         R, radii, geom, binning, img = fw[0], fw[9], fw[10], fw[11], fw[12]
         geo_stream = None
         if self.frozen_geometry:
-            # nothing but the feature gradients is consumed (the normal maps' gradient belongs to the frozen normal)
-            active = [a for a in active if a not in (5, 6, 7)]
+            # nothing but the feature gradients is consumed (the normal maps' gradient belongs to the frozen normal, the depth
+            # map's to the frozen positions: the MVS terms then only show in loss(), as in the reference)
+            active = [a for a in active if a not in (0, 5, 6, 7)]
             dL_dfeatures = rasterizer_ops.rasterize_gaussians_backward_features(
                 self.P, 16, v.H, v.W, g[4:20], geom, R, binning, img, active_features=sorted(active))
             bw = None
@@ -636,6 +676,11 @@ class FusedStage2Step(FusedStepBase):
                           -self.w["l1"] * lam / (3.0 * N), -self.w["pbr"] * lam / (3.0 * N),
                           self.w["base_color_smooth"] / (3.0 * N), self.w["roughness_smooth"] / (3.0 * N),
                           self.w["light_smooth"] / (3.0 * N)], device=self.dev)
+        if self._supervised:
+            # the depth term is a mean over the pixels r3dg_supervision_count selected (none: the term is zero)
+            count = 0 if self._sup_count_cur is None else int(self._sup_count_cur.item())
+            w = torch.cat([w, torch.tensor([self.w["depth"] / count if count else 0.0, self.w["normal_mvs_depth"] / (3.0 * N)],
+                                           device=self.dev)])
         return (self.sums.sum(1) * w).sum() + lam * (self.w["l1"] + self.w["pbr"])
 
     @_in_context
@@ -738,11 +783,12 @@ class FusedStage2Step(FusedStepBase):
                 self._pre_rotated = None           # (see optimizer_step)
 
     @_in_context
-    def __call__(self, cam, bg, gt, image_mask=None):
+    def __call__(self, cam, bg, gt, image_mask=None, gt_depth=None, mvs_normal=None):
         # the SH group's Adam under the shading backward: pays while the group's 64 bytes x 48 per Gaussian mostly live in the
         # 256 MB last-level cache (300k Gaussians: 58 us of Adam for 31 us of slower shading backward); streamed from HBM it
         # costs the latency-sensitive shading kernel nearly its whole duration (2M: 0.99 ms of Adam for +0.85 ms, 159 vs 163 it/s)
         early = os.environ.get("R3DG_EARLY_ADAM", "1" if self.P <= 1_000_000 else "0") != "0" and not self.serial_streams
-        outs = self.forward_backward(cam, bg, gt, early_adam=early, image_mask=image_mask, chain_incidents=True)
+        outs = self.forward_backward(cam, bg, gt, early_adam=early, image_mask=image_mask, chain_incidents=True,
+                                     gt_depth=gt_depth, mvs_normal=mvs_normal)
         self.optimizer_step()
         return outs

@@ -44,7 +44,10 @@ class Schedule(types.SimpleNamespace):
                          scaling_lr=0.005, rotation_lr=0.001, percent_dense=0.001, densification_interval=100,
                          opacity_reset_interval=3000, densify_from_iter=500, densify_until_iter=10_000,
                          densify_grad_threshold=0.0002, densify_grad_normal_threshold=2e-9, normal_densify_from_iter=0,
-                         min_opacity=0.005)
+                         min_opacity=0.005,
+                         # the loss terms no run script switches on (arguments/__init__.py:109-123)
+                         lambda_depth_smooth=0.0, lambda_point_entropy=0.0, lambda_orientation=0.0,
+                         lambda_orientation_from_iter=5000, lambda_scaling=0.0)
         self.__dict__.update(kw)
 
 
@@ -86,10 +89,18 @@ def train_stage1(init, cameras, images, background, extent, schedule=None, itera
     (iteration, "replayed_views", [the iterations they were dropped in]) -- at most `poll_interval` iterations late."""
     sch = schedule or Schedule()
     n_iter = sch.iterations if iterations is None else iterations
+    # the schedule's lambda_* fields (0 by default: the step is then built exactly as without them) under the caller's explicit
+    # `loss_weights`; the scaling term's schedule needs the run's length
+    extra = {k: getattr(sch, "lambda_" + k) for k in ("depth_smooth", "point_entropy", "orientation", "scaling")
+             if getattr(sch, "lambda_" + k, 0.0) != 0.0}
+    if extra:
+        extra["orientation_from_iter"] = sch.lambda_orientation_from_iter
+        loss_weights = dict(extra, **(loss_weights or {}))
+    more = dict(iterations=sch.iterations) if (loss_weights or {}).get("scaling", 0.0) != 0.0 else {}
     step = FusedStage1Step(init, lr=sch.sh_lr, lr_rest_scale=1.0 / 20.0, process_group=process_group,
                            lrs=dict(xyz=sch.position_lr_init * extent, normal=sch.normal_lr, scaling=sch.scaling_lr,
                                     rotation=sch.rotation_lr, opacity=sch.opacity_lr, shs=sch.sh_lr),
-                           loss_weights=loss_weights)
+                           loss_weights=loss_weights, **more)
     step.enable_densification()
     gen = torch.Generator(device=step.dev).manual_seed(seed)
     history = []

@@ -151,7 +151,10 @@ def first_order_edge_aware_loss(data, img):
 
 # script/run_nerf.sh:7-14 (stage 1): --lambda_normal_render_depth 0.01 --lambda_normal_smooth 0.01 --lambda_mask_entropy 0.1
 # --lambda_depth_var 1e-2; lambda_dssim 0.2 (arguments/__init__.py:125)
-STAGE1_WEIGHTS = dict(l1=1.0, mask_entropy=0.1, normal_render_depth=0.01, normal_smooth=0.01, depth_var=1e-2)
+# The terms no run script switches on keep the reference's defaults (arguments/__init__.py:109-123): depth_smooth,
+# point_entropy, orientation (from iteration orientation_from_iter on) and scaling are 0
+STAGE1_WEIGHTS = dict(l1=1.0, mask_entropy=0.1, normal_render_depth=0.01, normal_smooth=0.01, depth_var=1e-2,
+                      depth_smooth=0.0, point_entropy=0.0, orientation=0.0, orientation_from_iter=5000, scaling=0.0)
 
 
 def depth_var_weight(lambda_depth_var, iteration):
@@ -159,9 +162,36 @@ def depth_var_weight(lambda_depth_var, iteration):
     return lambda_depth_var * min(math.pow(10, iteration / 5000), 100)
 
 
-def stage1_loss(outs, gt, image_mask=None, weights=None, iteration=0):
+def scaling_weight(lambda_scaling, iteration, iterations):
+    """render.py:218: lambda_scaling - 0.99 * lambda_scaling * min(1, 4 * iteration / iterations)."""
+    return lambda_scaling - 0.99 * lambda_scaling * min(1, 4 * iteration / iterations)
+
+
+def stage1_gaussian_terms(w, blend_weights, opacity, normal, scales, xyz, campos, iteration=0, iterations=30_000):
+    """The per-Gaussian terms of calculate_loss (render.py:181-197, :215-219), weighted: point entropy, orientation (gated on
+    the iteration) and scaling (with its schedule).  `blend_weights` [P,1]: the rasterizer's weights output, a constant;
+    `opacity` [P,1], `normal` [P,3], `scales` [P,3]: activated (GaussianModel.get_*); directions = normalize(xyz - campos)
+    (render.py:85-86)."""
+    loss = xyz.new_zeros(())
+    if w["point_entropy"] > 0:
+        ws = blend_weights.detach().reshape(-1, 1)
+        loss = loss + w["point_entropy"] * (ws * (-opacity * torch.log(opacity + 1e-10)
+                                                  - (1 - opacity) * torch.log(1 - opacity + 1e-10))).mean()
+    if w["orientation"] > 0 and iteration > w["orientation_from_iter"]:
+        ws = blend_weights.detach().reshape(-1, 1).clamp_max(1)
+        directions = F.normalize(xyz - campos, dim=-1)
+        loss = loss + w["orientation"] * (ws * (normal * directions).sum(-1, keepdim=True).clamp_min(0.0)).mean()
+    if w["scaling"] > 0:
+        term = (scales - scales.mean(dim=-1, keepdim=True)).abs().sum(-1).mean()
+        loss = loss + scaling_weight(w["scaling"], iteration, iterations) * term
+    return loss
+
+
+def stage1_loss(outs, gt, image_mask=None, weights=None, iteration=0, gaussians=None, iterations=30_000):
     """calculate_loss of gaussian_renderer/render.py:137-223 on the rasterizer's 10 public outputs (render_view :107-115):
-    the parity target of fused_step.FusedStage1Step (plain PyTorch, autograd)."""
+    the parity target of fused_step.FusedStage1Step (plain PyTorch, autograd).  `gaussians` (needed by the per-Gaussian
+    terms, see stage1_gaussian_terms): dict(opacity, normal, scales, xyz, campos) of activated tensors; `iterations`: the
+    run's length, for the scaling term's schedule."""
     w = dict(STAGE1_WEIGHTS)
     if weights:
         w.update(weights)
@@ -178,9 +208,16 @@ def stage1_loss(outs, gt, image_mask=None, weights=None, iteration=0):
         loss = loss + w["normal_render_depth"] * F.mse_loss(normal * m, pseudo_normal.detach() * m)
     if w["normal_smooth"] > 0:
         loss = loss + w["normal_smooth"] * first_order_edge_aware_loss(normal, gt)
+    if w["depth_smooth"] > 0:
+        loss = loss + w["depth_smooth"] * first_order_edge_aware_loss(r_depth, gt)
     if w["depth_var"] > 0:
         var = r_depth2 - r_depth.square()
         loss = loss + depth_var_weight(w["depth_var"], iteration) * var.clamp_min(1e-6).sqrt().mean()
+    if w["point_entropy"] > 0 or w["orientation"] > 0 or w["scaling"] > 0:
+        if gaussians is None:
+            raise RuntimeError("stage1_loss: the per-Gaussian terms need `gaussians`")
+        loss = loss + stage1_gaussian_terms(w, weights_, gaussians["opacity"], gaussians["normal"], gaussians["scales"],
+                                            gaussians["xyz"], gaussians["campos"], iteration, iterations)
     return loss
 
 
@@ -190,8 +227,10 @@ def stage1_loss(outs, gt, image_mask=None, weights=None, iteration=0):
 #   script/run_syn4.sh:22-42   + lambda_base_color_smooth 1, lambda_roughness_smooth 0.5, lambda_light_smooth 1; every geometry
 #   script/run_dtu.sh:24-45      rate (position, normal, sh, opacity, scaling, rotation) 0: only base colour, roughness,
 #                                incident light and the environment texture train
+# depth / normal_mvs_depth: lambda_depth / lambda_normal_mvs_depth (neilf.py:241-249, :266-273), the supervision by a view's
+# MVS depth map and the normals derived from it (Camera.depth / Camera.normal); 0 in every run script
 STAGE2_WEIGHTS = dict(l1=1.0, pbr=1.0, normal=0.0, light=0.01, env_smooth=0.01, base_color_smooth=0.0, roughness_smooth=0.0,
-                      light_smooth=0.0)
+                      light_smooth=0.0, depth=0.0, normal_mvs_depth=0.0)
 STAGE2_WEIGHTS_SYN4 = dict(STAGE2_WEIGHTS, base_color_smooth=1.0, roughness_smooth=0.5, light_smooth=1.0)
 # parameter groups the frozen-geometry schedules leave at learning rate 0 (run_syn4.sh:27-33 / run_dtu.sh:29-35)
 FROZEN_GEOMETRY_GROUPS = ("xyz", "normal", "scaling", "rotation", "opacity", "shs")
@@ -213,6 +252,29 @@ def stage2_smoothness(feat, gt, image_mask, w, maps_are_srgb=False):
         loss = loss + w["roughness_smooth"] * first_order_edge_aware_loss(feat[11:12] * m, gt)
     if w["light_smooth"] != 0.0:
         loss = loss + w["light_smooth"] * first_order_edge_aware_loss(curve(feat[12:15]) * m, feat[5:8])
+    return loss
+
+
+def stage2_supervision(feat, gt_depth, mvs_normal, image_mask, w):
+    """The two MVS terms of calculate_loss on the divided feature maps `feat` [16,H,W]: lambda_depth * L1 of the rendered
+    depth against `gt_depth` [1,H,W] over ~sur_mask -- the pixels where the object mask and the depth map's validity agree
+    (neilf.py:241-249) -- and lambda_normal_mvs_depth * mse(normal * dm, mvs_normal * dm), dm = (gt_depth > 0) (:266-273).
+    `image_mask` [1,H,W] or None (all ones).  With no selected pixel the depth term is NaN, as in the reference (the fused
+    iteration gives zero there)."""
+    loss = feat.new_zeros(())
+    if w["depth"] != 0.0 or w["normal_mvs_depth"] != 0.0:
+        if gt_depth is None:
+            raise RuntimeError("the depth / normal_mvs_depth terms need gt_depth")
+    if w["depth"] != 0.0:
+        depth_mask = gt_depth > 0
+        im = torch.ones_like(depth_mask) if image_mask is None else image_mask.bool()
+        sel = ~torch.logical_xor(im, depth_mask)
+        loss = loss + w["depth"] * F.l1_loss(feat[0:1][sel], gt_depth[sel])
+    if w["normal_mvs_depth"] != 0.0:
+        if mvs_normal is None:
+            raise RuntimeError("the normal_mvs_depth term needs mvs_normal")
+        dm = (gt_depth > 0).to(feat.dtype)
+        loss = loss + w["normal_mvs_depth"] * F.mse_loss(feat[5:8] * dm, mvs_normal * dm)
     return loss
 
 
@@ -327,7 +389,7 @@ class Stage2Step:
                                       rotations=p.get_rotation(), features=features)
         return outs, diffuse_light, env
 
-    def __call__(self, cam, bg, gt, image_mask=None):
+    def __call__(self, cam, bg, gt, image_mask=None, gt_depth=None, mvs_normal=None):
         outs, diffuse_light, env = self.render(cam, bg)
         num_rendered, n_contrib, image, opacity, depth, feature, pseudo_normal, xyz, weights, radii = outs
         mask = n_contrib > 0
@@ -341,6 +403,7 @@ class Stage2Step:
             m = 1.0 if image_mask is None else image_mask
             loss = loss + w["normal"] * F.mse_loss(r_normal * m, pseudo_normal.detach() * m)
         loss = loss + stage2_smoothness(feat, gt, image_mask, w)                                       # neilf.py:275-292
+        loss = loss + stage2_supervision(feat, gt_depth, mvs_normal, image_mask, w)                    # neilf.py:241-249, 266-273
         mean_light = diffuse_light.mean(-1, keepdim=True).expand_as(diffuse_light)
         loss = loss + w["light"] * F.l1_loss(diffuse_light, mean_light)                              # lambda_light
         loss = loss + w["env_smooth"] * tv_loss(env.permute(2, 0, 1))                                # lambda_env_smooth
