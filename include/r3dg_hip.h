@@ -827,6 +827,29 @@ int r3dg_bvh_pack_traversal(void* stream, int num_gaussians, const int32_t* d_no
 int r3dg_bvh_trace_opacity_packed(void* stream, int64_t num_rays, int num_gaussians, void* d_records, const float* d_rays_o,
                                   const float* d_rays_d, int32_t* d_num_contributes, float* d_rendered_opacity,
                                   int32_t* d_stack_overflow);
+
+/* A visibility update without host-side tensor work (train_step.update_visibility_device; GaussianModel.update_visibility,
+ * scene/gaussian_model.py:312-342, is what it restates).
+ * r3dg_bvh_prepare_leaves: one launch for everything r3dg_bvh_build and the trace need from the activated Gaussians
+ *   (d_scales [P,3] activated, d_rotations [P,4] raw or normalised, d_means3D [P,3]): d_nodes int32[2P-1,5] and d_aabbs
+ *   float[2P-1,6] initialised as bvh/__init__.py:29-57 prepares them (nodes -1, counts 0 internal / 1 leaf, internal boxes
+ *   +-100000, the 3-sigma oriented box of the eight signed corners in the leaf rows P-1..) -- BIT-IDENTICAL to the PyTorch
+ *   operations of that file, so the tree built from them is the same tree -- and d_covs3D_inv float[P,6], the inverse
+ *   covariance 6-vector of GaussianModel.get_inverse_covariance (same formula, fp32 rounding of its own).
+ * r3dg_bvh_trace_bundles: the trace of r3dg_bvh_trace_opacity_packed over rays the kernel generates itself: for every Morton
+ *   leaf slot i in [leaf_lo, leaf_hi) (row P-1+i of d_nodes: object id g) and every k < K the ray with direction
+ *   d = normalize(rotation_between_z(normal_g) z_k) (utils/sh_utils.py:36-68, graphics_utils.py:9-37; d_zsamples [K,3] = the
+ *   Fibonacci set around +z; mean and normal of g are read from d_records, what r3dg_bvh_pack_traversal wrote) and origin
+ *   mean_g + d * origin_offset (RayTracer.trace_visibility: 0.05).  The transmittance goes to d_visibility[g*K + k], the hit
+ *   count to d_num_contributes[g*K + k] (NULL: not wanted), d to d_dirs_out[g,k,:] (NULL: not wanted; [P,K,3]) -- the caller's
+ *   row order; rows of leaves outside [leaf_lo, leaf_hi) are untouched, so ranks or calls that split the slots fill one buffer.
+ *   Each result is bit-identical to r3dg_bvh_trace_opacity_packed given that origin and direction.  *d_stack_overflow as above;
+ *   num_gaussians * K must fit an int; one trace at a time per d_records.  P == 0 or an empty range: nothing is launched. */
+int r3dg_bvh_prepare_leaves(void* stream, int P, const float* d_means3D, const float* d_scales, const float* d_rotations,
+                            int32_t* d_nodes, float* d_aabbs, float* d_covs3D_inv);
+int r3dg_bvh_trace_bundles(void* stream, int num_gaussians, int K, void* d_records, const int32_t* d_nodes,
+                           const float* d_zsamples, int leaf_lo, int leaf_hi, float origin_offset, float* d_visibility,
+                           int32_t* d_num_contributes, float* d_dirs_out, int32_t* d_stack_overflow);
 /* Measurement ("report rays/s and node-visits/s"): with R3DG_OPT_TRACE_COUNT_VISITS = 1 the phased trace counts
  * its node steps (one slab test of both children of a node, trace.cu:228-246) and leaf steps (one Gaussian evaluated,
  * :247-276); r3dg_bvh_trace_visits synchronises `stream` and returns the two sums of the LAST trace over `d_records` in

@@ -49,6 +49,16 @@ class RayTracer:
         # ray bundles chunk by chunk against the same arrays: packed once, owned by this tracer)
         self._records = self._records_key = self._records_ref = None
 
+    @classmethod
+    def from_device_leaves(cls, means3D, scales, rotations):
+        """The same tracer with the leaf tables prepared by ONE kernel (bvh_ops.prepare_leaves) instead of leaf_boxes' PyTorch
+        launches: tree, boxes and Morton codes are identical.  The kernel's inverse covariance [P,6] is kept in `covs_inv`."""
+        self = cls.__new__(cls)
+        nodes, aabbs, self.covs_inv = bvh_ops.prepare_leaves(means3D, scales, rotations)
+        self.tree, self.aabb, self.morton = bvh_ops.create_bvh(means3D, scales, rotations, nodes, aabbs)
+        self._records = self._records_key = self._records_ref = None
+        return self
+
     def _records_for(self, means3D, symm_inv, opacity, normals):
         if self.tree.shape[0] != 2 * means3D.shape[0] - 1 or means3D.shape[0] == 0:
             return None

@@ -29,6 +29,56 @@ def create_bvh(means3D, scales, rotations, nodes, aabbs):
     return nodes, aabbs, mortons
 
 
+def prepare_leaves(means3D, scales, rotations):
+    """-> (nodes int32[2P-1,5], aabbs float32[2P-1,6], covs_inv float32[P,6]) in ONE launch (r3dg_bvh_prepare_leaves): the tables
+    bvh.leaf_boxes prepares for create_bvh, bit for bit, and train_step.inverse_covariance's 6-vector."""
+    L = _lib.lib()
+    P = means3D.shape[0]
+    dev = means3D.device
+    if P < 1:
+        raise RuntimeError("prepare_leaves: needs at least one Gaussian")
+    t = [x.contiguous() for x in (means3D, scales, rotations)]
+    if any(x.dtype != torch.float32 or not x.is_cuda for x in t) or t[1].shape != (P, 3) or t[2].shape != (P, 4):
+        raise RuntimeError("prepare_leaves: means3D [P,3], scales [P,3], rotations [P,4] must be float32 CUDA(HIP) tensors")
+    nodes = torch.empty((2 * P - 1, 5), dtype=torch.int32, device=dev)
+    aabbs = torch.empty((2 * P - 1, 6), dtype=torch.float32, device=dev)
+    covs_inv = torch.empty((P, 6), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.r3dg_bvh_prepare_leaves(_lib.current_stream(), P, *[x.data_ptr() for x in t], nodes.data_ptr(),
+                                             aabbs.data_ptr(), covs_inv.data_ptr()), "prepare_leaves")
+    return nodes, aabbs, covs_inv
+
+
+def trace_bundles(records, nodes, zsamples, visibility, leaf_lo=0, leaf_hi=None, origin_offset=0.05, contributes=None,
+                  dirs_out=None):
+    """The visibility trace over rays generated in the kernel (r3dg_bvh_trace_bundles): for the Morton leaf slots
+    [leaf_lo, leaf_hi) of the tree `nodes` (`records` = trace_records(...) of it) the K = zsamples.shape[0] rays of each
+    slot's Gaussian g -- directions: the Fibonacci set of g's normal, origins: mean + direction * origin_offset -- written IN
+    PLACE to row g of `visibility` [P,K] (float32), `contributes` [P,K] (int32, optional) and `dirs_out` [P,K,3] (float32,
+    optional).  Rows of other leaves are untouched.  -> the stack-overflow counter (int32[1], on the device)."""
+    L = _lib.lib()
+    P, K = (nodes.shape[0] + 1) // 2, zsamples.shape[0]
+    dev = visibility.device
+    leaf_hi = P if leaf_hi is None else leaf_hi
+    for name, t, dtype, n in (("visibility", visibility, torch.float32, P * K), ("contributes", contributes, torch.int32, P * K),
+                              ("dirs_out", dirs_out, torch.float32, 3 * P * K)):
+        if t is not None and (t.dtype != dtype or t.numel() != n or not t.is_contiguous() or not t.is_cuda):
+            raise RuntimeError("trace_bundles: %s must be a contiguous %s CUDA(HIP) tensor of %d elements" % (name, dtype, n))
+    if zsamples.dtype != torch.float32 or zsamples.dim() != 2 or zsamples.shape[1] != 3 or not zsamples.is_contiguous():
+        raise RuntimeError("trace_bundles: zsamples must be a contiguous float32 [K,3] tensor")
+    if nodes.dtype != torch.int32 or not nodes.is_contiguous() or nodes.shape[1] != 5:
+        raise RuntimeError("trace_bundles: nodes must be the contiguous int32 [2P-1,5] table")
+    if records.numel() < int(L.r3dg_bvh_trace_records_bytes(P)):
+        raise RuntimeError("trace_bundles: records are not the packed records of this tree")
+    overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.r3dg_bvh_trace_bundles(_lib.current_stream(), P, K, records.data_ptr(), nodes.data_ptr(), zsamples.data_ptr(),
+                                            int(leaf_lo), int(leaf_hi), float(origin_offset), visibility.data_ptr(),
+                                            _lib.ptr(contributes), _lib.ptr(dirs_out), overflow.data_ptr()), "trace_bundles")
+    trace_bundles.last_overflow = overflow
+    return overflow
+
+
 def trace_records(nodes, aabbs, means3D, covs3D, opacities, normals):
     """The tree and the per-Gaussian arrays packed into 64-byte traversal records (r3dg_bvh_pack_traversal), for
     trace_bvh_opacity(..., records=...): pack once, trace many ray chunks.  Valid while the six tensors are unchanged."""

@@ -284,6 +284,85 @@ range_boxes_kernel(int P, const int2* __restrict__ ranges, const float* __restri
     if (*nonzero_count_seen == 0) nodes[5 * (size_t)idx + 4] = last - r.x + 1;
 }
 
+// ---- leaf preparation: what the host side of RayTracer does in ~40 PyTorch launches before the build, in one ----------------------
+// One thread per Gaussian: the node-table initialisation and the leaf boxes of bvh.leaf_boxes (bvh/__init__.py:29-57) and the
+// inverse covariance of train_step.inverse_covariance (gaussian_model.py:257-260).
+// BIT-EXACT (with -ffp-contract=off): nodes and aabbs.  Every product, sum, division and square root below is the one PyTorch
+// operation bvh.build_rotation / bvh.leaf_boxes run at that place, in their order: the quaternion is divided by
+// sqrt(((r0 r0 + r1 r1) + r2 r2) + r3 r3), the matrix entries are 1 - 2 (a + b) and 2 (a -+ b), a corner is
+// ((mean + (+-R[:,0]) (3 s0)) + (+-R[:,1]) (3 s1)) + (+-R[:,2]) (3 s2) -- a sign commutes with a product exactly -- and min / max
+// give the same bits in any order.  The Morton codes and the tree built from these boxes are then those of RayTracer(...).
+// NOT bit-exact: the inverse covariance R diag(1/s^2) R^T.  PyTorch normalises with F.normalize and multiplies with a batched
+// GEMM whose summation order is the BLAS library's: a handful of fp32 roundings.  Here the formula is evaluated in double from
+// the fp32 inputs and rounded once (54 double operations per Gaussian, once per visibility update), so every entry is the
+// nearest float to the exact value (tests/test_visibility_refresh_gpu.py compares both with a float64 evaluation).
+__global__ void __launch_bounds__(256)
+bvh_prepare_leaves_kernel(int P, const float* __restrict__ means, const float* __restrict__ scales,
+                          const float* __restrict__ rotations, int32_t* __restrict__ nodes, float* __restrict__ aabbs,
+                          float* __restrict__ covs_inv)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P) return;
+    if (i < P - 1) {                                                // internal row i
+        int32_t* n = nodes + 5 * (size_t)i;
+        n[0] = n[1] = n[2] = n[3] = -1;
+        n[4] = 0;
+        float* b = aabbs + 6 * (size_t)i;
+        b[0] = b[1] = b[2] = 100000.f;
+        b[3] = b[4] = b[5] = -100000.f;
+    }
+    const size_t row = (size_t)(P - 1 + i);                         // leaf row of Gaussian i (the build sorts them)
+    int32_t* n = nodes + 5 * row;
+    n[0] = n[1] = n[2] = n[3] = -1;
+    n[4] = 1;
+    const float r0 = rotations[4 * (size_t)i], r1 = rotations[4 * (size_t)i + 1], r2 = rotations[4 * (size_t)i + 2],
+                r3 = rotations[4 * (size_t)i + 3];
+    const float norm = sqrtf(r0 * r0 + r1 * r1 + r2 * r2 + r3 * r3);
+    const float w = r0 / norm, x = r1 / norm, y = r2 / norm, z = r3 / norm;
+    const float R[9] = {1.f - 2.f * (y * y + z * z), 2.f * (x * y - w * z), 2.f * (x * z + w * y),
+                        2.f * (x * y + w * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - w * x),
+                        2.f * (x * z - w * y), 2.f * (y * z + w * x), 1.f - 2.f * (x * x + y * y)};
+    const float s0 = scales[3 * (size_t)i], s1 = scales[3 * (size_t)i + 1], s2 = scales[3 * (size_t)i + 2];
+    const float sa = 3.f * s0, sb = 3.f * s1, sc = 3.f * s2;
+    float* b = aabbs + 6 * row;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const float m = means[3 * (size_t)i + a];
+        const float ca = R[3 * a] * sa, cb = R[3 * a + 1] * sb, cc = R[3 * a + 2] * sc;
+        float lo = 0.f, hi = 0.f;
+#pragma unroll
+        for (int c = 0; c < 8; c++) {
+            const float v = ((m + ((c & 4) ? -ca : ca)) + ((c & 2) ? -cb : cb)) + ((c & 1) ? -cc : cc);
+            lo = c == 0 ? v : fminf(lo, v);
+            hi = c == 0 ? v : fmaxf(hi, v);
+        }
+        b[a] = lo;
+        b[3 + a] = hi;
+    }
+    // L = R diag(1/s); S = L L^T, the upper triangle row by row, from the fp32 inputs in double and rounded once
+    const double q0 = r0, q1 = r1, q2 = r2, q3 = r3;
+    const double qn = fmax(sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3), 1e-12);          // F.normalize's eps
+    const double dw = q0 / qn, dx = q1 / qn, dy = q2 / qn, dz = q3 / qn;
+    const double D[9] = {1.0 - 2.0 * (dy * dy + dz * dz), 2.0 * (dx * dy - dw * dz), 2.0 * (dx * dz + dw * dy),
+                         2.0 * (dx * dy + dw * dz), 1.0 - 2.0 * (dx * dx + dz * dz), 2.0 * (dy * dz - dw * dx),
+                         2.0 * (dx * dz - dw * dy), 2.0 * (dy * dz + dw * dx), 1.0 - 2.0 * (dx * dx + dy * dy)};
+    const double i0 = 1.0 / (double)s0, i1 = 1.0 / (double)s1, i2 = 1.0 / (double)s2;
+    double L[9];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        L[3 * a] = D[3 * a] * i0;
+        L[3 * a + 1] = D[3 * a + 1] * i1;
+        L[3 * a + 2] = D[3 * a + 2] * i2;
+    }
+    float* c = covs_inv + 6 * (size_t)i;
+    int o = 0;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int d = a; d < 3; d++)
+            c[o++] = (float)(L[3 * a] * L[3 * d] + L[3 * a + 1] * L[3 * d + 1] + L[3 * a + 2] * L[3 * d + 2]);
+}
+
 // ---- host ----
 size_t bvh_build_temp_bytes(size_t P)
 {
@@ -299,6 +378,13 @@ size_t bvh_build_temp_bytes(size_t P)
     take(256);           // whole box
     take(sort_temp_bytes(P));
     return o + 256;
+}
+
+void bvh_prepare_leaves(hipStream_t s, int P, const float* means, const float* scales, const float* rotations, int32_t* nodes,
+                        float* aabbs, float* covs_inv)
+{
+    if (P <= 0) return;
+    bvh_prepare_leaves_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, means, scales, rotations, nodes, aabbs, covs_inv);
 }
 
 void bvh_build(hipStream_t s, int P, int32_t* nodes, float* aabbs, uint64_t* morton, void* temp)

@@ -6,6 +6,7 @@
 // The traversal stack holds 64 entries (reference: 32 with only a printf on overflow, trace.cuh:21-28); pushes beyond that
 // are dropped and counted in *overflow so callers can detect it.
 #include "launchers.hpp"
+#include "ray_set.hpp"
 
 namespace r3dg {
 
@@ -212,6 +213,55 @@ pack_traversal_kernel(int P, const int32_t* __restrict__ nodes, const float* __r
     }
 }
 
+// ---- where the phased kernel's rays come from ------------------------------------------------------------------------------------
+// A lane that refills asks its source for ray `idx` of the launch: origin, direction, and the row of the outputs the result
+// goes to.  Everything else of the kernel (queues, refill, voting, termination) does not know which source it has.
+// ArrayRays: one (rays_o, rays_d) row per ray, results in the same row -- the reference's interface.
+struct ArrayRays {
+    const float* __restrict__ rays_o;
+    const float* __restrict__ rays_d;
+    static constexpr bool optional_counts = false;
+    __device__ __forceinline__ int load(int idx, const TLeaf* __restrict__, float& ox, float& oy, float& oz, float& dx, float& dy,
+                                        float& dz) const
+    {
+        ox = rays_o[3 * (size_t)idx]; oy = rays_o[3 * (size_t)idx + 1]; oz = rays_o[3 * (size_t)idx + 2];
+        dx = rays_d[3 * (size_t)idx]; dy = rays_d[3 * (size_t)idx + 1]; dz = rays_d[3 * (size_t)idx + 2];
+        return idx;
+    }
+};
+// BundleRays: the K visibility rays of every Gaussian of the Morton leaf slots [leaf_lo, leaf_hi), generated here.  Ray idx of
+// the launch is sample k = idx % K of slot i = leaf_lo + idx / K: consecutive rays start at the same or at a neighbouring
+// Gaussian by construction (what update_visibility arranges with a gather of the origins by the leaf order).  The origin
+// Gaussian's mean and normal are in the packed leaf record tl[i]; the direction is sample k of the fixed ray set of that normal
+// (ray_set.hpp: the function the fixed-ray-set shading kernels regenerate their directions with), the origin
+// mean + direction * offset as a separate multiply and add (RayTracer.trace_visibility: rays_o + rays_d * 0.05 in PyTorch).
+// The result belongs to row g * K + k of the outputs, g the slot's object id: the caller's order, no scatter pass behind the
+// trace.  `dirs_out` (optional, [P,K,3]): the generated direction, for callers that need the tensor.
+struct BundleRays {
+    const int32_t* __restrict__ leaf_nodes;        // rows P-1.. of the node table: column 3 = object id of the slot
+    const float* __restrict__ zsamples;            // [K,3]
+    float* __restrict__ dirs_out;
+    int K, leaf_lo;
+    float offset;
+    static constexpr bool optional_counts = true;
+    __device__ __forceinline__ int load(int idx, const TLeaf* __restrict__ tl, float& ox, float& oy, float& oz, float& dx,
+                                        float& dy, float& dz) const
+    {
+        const int q = idx / K, k = idx - q * K, i = leaf_lo + q;
+        const TLeaf* __restrict__ leaf = tl + i;
+        float R[9];
+        rotation_between_z(leaf->n[0], leaf->n[1], leaf->n[2], R);
+        ray_set_direction(R, zsamples[3 * k], zsamples[3 * k + 1], zsamples[3 * k + 2], dx, dy, dz);
+        const float sx = dx * offset, sy = dy * offset, sz = dz * offset;
+        ox = leaf->mean[0] + sx; oy = leaf->mean[1] + sy; oz = leaf->mean[2] + sz;
+        const int row = leaf_nodes[5 * (size_t)i + 3] * K + k;
+        if (dirs_out != nullptr) {
+            dirs_out[3 * (size_t)row] = dx; dirs_out[3 * (size_t)row + 1] = dy; dirs_out[3 * (size_t)row + 2] = dz;
+        }
+        return row;
+    }
+};
+
 // ---- packed records, phase-separated persistent waves (R3DG_OPT_TRACE_FORMULATION = 1, default) -------------------------------
 // Persistent waves: 83 % of the visibility rays are occluded after a handful of leaves while the rest walk thousands of
 // nodes, so a fixed ray per thread leaves ~3/4 of the lanes idle.  Here a lane whose ray has finished pulls the next ray
@@ -229,10 +279,10 @@ pack_traversal_kernel(int P, const int32_t* __restrict__ nodes, const float* __r
 // COUNT (R3DG_OPT_TRACE_COUNT_VISITS, measurement builds of the same kernel): every lane counts the node steps (one slab test of
 // both children) and leaf steps (one Gaussian evaluated) of its rays; one 64-bit atomic pair per wave at the end, into words
 // 8..11 of the wave's own queue line (zeroed with the queue heads before the launch; read by r3dg_bvh_trace_visits).
-template <bool COUNT>
+// Rays: ArrayRays or BundleRays (above).  `ray` holds the OUTPUT row of the lane's current ray (< 0: idle).
+template <bool COUNT, class Rays>
 __global__ void __launch_bounds__(256)
-trace_opacity_phased_kernel(int num_rays, int P, const TNode* __restrict__ tn, const TLeaf* __restrict__ tl,
-                            const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+trace_opacity_phased_kernel(int num_rays, int P, const TNode* __restrict__ tn, const TLeaf* __restrict__ tl, const Rays rays,
                             int32_t* __restrict__ contributes, float* __restrict__ out, int* __restrict__ overflow,
                             int* __restrict__ queues /* 8 x 16 ints, zeroed */, int refill_min_idle, int node_weight,
                             int leaf_weight)
@@ -266,9 +316,7 @@ trace_opacity_phased_kernel(int num_rays, int P, const TNode* __restrict__ tn, c
                 if (ray < 0) {
                     const int idx = base + __popcll(idle & ((1ull << lane) - 1ull));
                     if (idx < q_hi) {
-                        ray = idx;
-                        ox = rays_o[3 * (size_t)idx]; oy = rays_o[3 * (size_t)idx + 1]; oz = rays_o[3 * (size_t)idx + 2];
-                        dx = rays_d[3 * (size_t)idx]; dy = rays_d[3 * (size_t)idx + 1]; dz = rays_d[3 * (size_t)idx + 2];
+                        ray = rays.load(idx, tl, ox, oy, oz, dx, dy, dz);
                         rx = refined_reciprocal(dx); ry = refined_reciprocal(dy); rz = refined_reciprocal(dz);
                         tame_ray = tame_direction(dx) && tame_direction(dy) && tame_direction(dz) && tame_coordinate(ox) &&
                                    tame_coordinate(oy) && tame_coordinate(oz);
@@ -375,7 +423,7 @@ trace_opacity_phased_kernel(int num_rays, int P, const TNode* __restrict__ tn, c
         if (stepped) {
             if (!finished && cur < 0 && sp > 0) cur = stack[--sp];
             if (finished || cur < 0) {
-                contributes[ray] = count;
+                if (!Rays::optional_counts || contributes != nullptr) contributes[ray] = count;
                 out[ray] = T;
                 ray = -1;
                 sp = 0;
@@ -566,14 +614,42 @@ void bvh_trace_opacity_packed(hipStream_t s, int num_rays, int P, void* records,
     R3DG_HIP(hipMemsetAsync(queues, 0, 8 * 64, s));
     const int cap = cus * 8;                                                    // 8 waves per SIMD, all resident
     const int grid = chunk * 8 < cap ? chunk * 8 : cap;
+    const ArrayRays rays = {rays_o, rays_d};
     if (opt(R3DG_OPT_TRACE_COUNT_VISITS))
-        trace_opacity_phased_kernel<true><<<grid, 256, 0, s>>>(num_rays, P, tn, tl, rays_o, rays_d, contributes, out,
-                                                              overflow, queues, opt(R3DG_OPT_TRACE_REFILL),
-                                                              opt(R3DG_OPT_TRACE_NODE_WEIGHT), opt(R3DG_OPT_TRACE_LEAF_WEIGHT));
+        trace_opacity_phased_kernel<true, ArrayRays><<<grid, 256, 0, s>>>(num_rays, P, tn, tl, rays, contributes, out, overflow,
+                                                                         queues, opt(R3DG_OPT_TRACE_REFILL),
+                                                                         opt(R3DG_OPT_TRACE_NODE_WEIGHT), opt(R3DG_OPT_TRACE_LEAF_WEIGHT));
     else
-        trace_opacity_phased_kernel<false><<<grid, 256, 0, s>>>(num_rays, P, tn, tl, rays_o, rays_d, contributes, out,
-                                                               overflow, queues, opt(R3DG_OPT_TRACE_REFILL),
-                                                               opt(R3DG_OPT_TRACE_NODE_WEIGHT), opt(R3DG_OPT_TRACE_LEAF_WEIGHT));
+        trace_opacity_phased_kernel<false, ArrayRays><<<grid, 256, 0, s>>>(num_rays, P, tn, tl, rays, contributes, out, overflow,
+                                                                          queues, opt(R3DG_OPT_TRACE_REFILL),
+                                                                          opt(R3DG_OPT_TRACE_NODE_WEIGHT), opt(R3DG_OPT_TRACE_LEAF_WEIGHT));
+}
+
+// the same trace with the rays generated in the kernel: the K rays of every Gaussian of the leaf slots [leaf_lo, leaf_hi) of the
+// tree `nodes` / `records` describe (BundleRays); results at rows g * K + k of out / contributes (NULL: not wanted) / dirs_out
+// (NULL: not wanted), rows of other leaves untouched
+void bvh_trace_bundles(hipStream_t s, int P, int K, void* records, const int32_t* nodes, const float* zsamples, int leaf_lo,
+                       int leaf_hi, float origin_offset, float* out, int32_t* contributes, float* dirs_out, int* overflow)
+{
+    if (P <= 0 || K <= 0 || leaf_hi <= leaf_lo) return;
+    char* rec = reinterpret_cast<char*>(records);
+    TNode* tn = reinterpret_cast<TNode*>(rec);
+    TLeaf* tl = reinterpret_cast<TLeaf*>(rec + (size_t)P * 64);
+    int* queues = reinterpret_cast<int*>(rec + (size_t)P * 128);
+    const int num_rays = (leaf_hi - leaf_lo) * K;                               // (<= P * K, which the caller checked)
+    const int nblk = (num_rays + 255) / 256, chunk = (nblk + 7) / 8;
+    const int cap = persistent_cus() * 8;
+    const int grid = chunk * 8 < cap ? chunk * 8 : cap;
+    R3DG_HIP(hipMemsetAsync(queues, 0, 8 * 64, s));
+    const BundleRays rays = {nodes + 5 * (size_t)(P - 1), zsamples, dirs_out, K, leaf_lo, origin_offset};
+    if (opt(R3DG_OPT_TRACE_COUNT_VISITS))
+        trace_opacity_phased_kernel<true, BundleRays><<<grid, 256, 0, s>>>(num_rays, P, tn, tl, rays, contributes, out, overflow,
+                                                                          queues, opt(R3DG_OPT_TRACE_REFILL),
+                                                                          opt(R3DG_OPT_TRACE_NODE_WEIGHT), opt(R3DG_OPT_TRACE_LEAF_WEIGHT));
+    else
+        trace_opacity_phased_kernel<false, BundleRays><<<grid, 256, 0, s>>>(num_rays, P, tn, tl, rays, contributes, out, overflow,
+                                                                           queues, opt(R3DG_OPT_TRACE_REFILL),
+                                                                           opt(R3DG_OPT_TRACE_NODE_WEIGHT), opt(R3DG_OPT_TRACE_LEAF_WEIGHT));
 }
 
 // node / leaf steps of the LAST counting trace over these records (sums over the eight queue lines; synchronises the stream)

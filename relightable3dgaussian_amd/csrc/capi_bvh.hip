@@ -35,6 +35,22 @@ int r3dg_bvh_build(void* stream_, int P, int32_t* nodes, float* aabbs, int64_t* 
     });
 }
 
+int r3dg_bvh_prepare_leaves(void* stream_, int P, const float* means3D, const float* scales, const float* rotations,
+                            int32_t* nodes, float* aabbs, float* covs3D_inv)
+{
+    if (P < 0) return invalid("bvh_prepare_leaves: bad P");
+    if (P == 0) return R3DG_OK;
+    if (!means3D || !scales || !rotations || !nodes || !aabbs || !covs3D_inv) return invalid("bvh_prepare_leaves: null buffer");
+    return guarded([&]() -> int {
+        hipStream_t stream = (hipStream_t)stream_;
+        StageTimer t(stream, ST_BVH_BUILD);
+        bvh_prepare_leaves(stream, P, means3D, scales, rotations, nodes, aabbs, covs3D_inv);
+        check_launch(stream, false, "bvh_prepare_leaves");
+        t.stop();
+        return R3DG_OK;
+    });
+}
+
 int r3dg_bvh_trace_opacity(void* stream_, int64_t num_rays, int num_gaussians, const int32_t* nodes, const float* aabbs,
                            const float* rays_o, const float* rays_d, const float* means3D, const float* covs3D,
                            const float* opacities, const float* normals, int32_t* num_contributes,
@@ -88,6 +104,27 @@ int r3dg_bvh_trace_opacity_packed(void* stream_, int64_t num_rays, int num_gauss
         bvh_trace_opacity_packed(stream, (int)num_rays, num_gaussians, records, rays_o, rays_d, num_contributes,
                                  rendered_opacity, stack_overflow);
         check_launch(stream, false, "bvh_trace_opacity_packed");
+        t.stop();
+        return R3DG_OK;
+    });
+}
+
+int r3dg_bvh_trace_bundles(void* stream_, int num_gaussians, int K, void* records, const int32_t* nodes, const float* zsamples,
+                           int leaf_lo, int leaf_hi, float origin_offset, float* visibility, int32_t* num_contributes,
+                           float* dirs_out, int32_t* stack_overflow)
+{
+    if (num_gaussians < 0) return invalid("bvh_trace_bundles: bad Gaussian count");
+    if (K <= 0) return invalid("bvh_trace_bundles: bad sample count");
+    if ((int64_t)num_gaussians * K > 0x7fffffffll) return invalid("bvh_trace_bundles: num_gaussians * K does not fit the ray index");
+    if (leaf_lo < 0 || leaf_hi < leaf_lo || leaf_hi > num_gaussians) return invalid("bvh_trace_bundles: bad leaf range");
+    if (num_gaussians == 0 || leaf_lo == leaf_hi) return R3DG_OK;
+    if (!records || !nodes || !zsamples || !visibility || !stack_overflow) return invalid("bvh_trace_bundles: null buffer");
+    return guarded([&]() -> int {
+        hipStream_t stream = (hipStream_t)stream_;
+        StageTimer t(stream, ST_BVH_TRACE);
+        bvh_trace_bundles(stream, num_gaussians, K, records, nodes, zsamples, leaf_lo, leaf_hi, origin_offset, visibility,
+                          num_contributes, dirs_out, stack_overflow);
+        check_launch(stream, false, "bvh_trace_bundles");
         t.stop();
         return R3DG_OK;
     });

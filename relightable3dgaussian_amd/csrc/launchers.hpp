@@ -224,6 +224,8 @@ size_t knn_temp_bytes(size_t P);
 void knn_dist2(hipStream_t s, int P, const float* pts, float* dists, void* temp);
 size_t bvh_build_temp_bytes(size_t P);                  // bvh_build.hip
 void bvh_build(hipStream_t s, int P, int32_t* nodes, float* aabbs, uint64_t* morton, void* temp);
+void bvh_prepare_leaves(hipStream_t s, int P, const float* means, const float* scales, const float* rotations, int32_t* nodes,
+                        float* aabbs, float* covs_inv);
 // bvh_trace.hip
 void bvh_trace_count(hipStream_t s, int num_rays, const int32_t* nodes, const float* aabbs, const float* rays_o,
                      const float* rays_d, int32_t* counts, int* overflow);
@@ -239,6 +241,8 @@ void bvh_pack_traversal(hipStream_t s, int P, const int32_t* nodes, const float*
 void bvh_trace_visits(hipStream_t s, int P, const void* records, unsigned long long out[2]);
 void bvh_trace_opacity_packed(hipStream_t s, int num_rays, int P, void* records, const float* rays_o, const float* rays_d,
                               int32_t* contributes, float* out, int* overflow);
+void bvh_trace_bundles(hipStream_t s, int P, int K, void* records, const int32_t* nodes, const float* zsamples, int leaf_lo,
+                       int leaf_hi, float origin_offset, float* out, int32_t* contributes, float* dirs_out, int* overflow);
 void launch_transpose_selftest(hipStream_t s, int N, int dpp, const float* in, float* out, int* chan, int* owner);
 
 }  // namespace r3dg

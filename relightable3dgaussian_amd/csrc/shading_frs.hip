@@ -414,6 +414,8 @@ frs_build_taps_kernel(int P, int K, const float* __restrict__ ray_normals, const
     const int g = (int)(i / (size_t)K), k = (int)(i - (size_t)g * K);
     float R[9];
     rotation_between_z(ray_normals[3 * (size_t)g], ray_normals[3 * (size_t)g + 1], ray_normals[3 * (size_t)g + 2], R);
+    // ray_set_direction (ray_set.hpp) written out: inlined from the helper, hipcc (-ffast-math) associates the sum under the
+    // square root in another order here and the last bit of a record's weight would move
     const float zx = zsamples[3 * k], zy = zsamples[3 * k + 1], zz = zsamples[3 * k + 2];
     float dx = R[0] * zx + R[1] * zy + R[2] * zz, dy = R[3] * zx + R[4] * zy + R[5] * zz, dz = R[6] * zx + R[7] * zy + R[8] * zz;
     const float len = fmaxf(sqrtf(dx * dx + dy * dy + dz * dz), 1e-12f);
@@ -1014,10 +1016,7 @@ __device__ __forceinline__ float frs_listed_record(int lane, int g, const FrsSrc
 __device__ __forceinline__ void frs_listed_direction(const float (&R)[9], const float* __restrict__ zsamples, int k, float& dx,
                                                      float& dy, float& dz)
 {
-    const float zx = zsamples[3 * k], zy = zsamples[3 * k + 1], zz = zsamples[3 * k + 2];
-    dx = R[0] * zx + R[1] * zy + R[2] * zz; dy = R[3] * zx + R[4] * zy + R[5] * zz; dz = R[6] * zx + R[7] * zy + R[8] * zz;
-    const float len = fmaxf(sqrtf(dx * dx + dy * dy + dz * dz), 1e-12f);
-    dx /= len; dy /= len; dz /= len;
+    ray_set_direction(R, zsamples[3 * k], zsamples[3 * k + 1], zsamples[3 * k + 2], dx, dy, dz);
 }
 
 __global__ void __launch_bounds__(64 * FRS_LISTED_WAVES)

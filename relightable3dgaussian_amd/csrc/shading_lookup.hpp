@@ -3,6 +3,7 @@
 // loads, and rotation_between_z.
 #pragma once
 #include "common.hpp"
+#include "ray_set.hpp"
 #include "shading_math.hpp"
 
 namespace r3dg {
@@ -150,22 +151,7 @@ __device__ __forceinline__ void env_fetch(const PackedTap& t, const float4* tex4
     }
 }
 
-// rotation_between_z(n) (utils/sh_utils.py:36-68), fp32 operation for operation as sampling.rotation_between_z: the rotation
-// that takes +z to n (the identity's negative when n_z + 1 <= 0)
-__device__ __forceinline__ void rotation_between_z(const float n0, const float n1, const float n2, float (&R)[9])
-{
-    const float v1 = -n1, v2 = n0, cp = fmaxf(n2 + 1.f, 1e-7f);
-    const bool regular = n2 + 1.f > 0.f;
-    R[0] = regular ? 1.f + (-v2 * v2) / cp : -1.f;
-    R[1] = regular ? v1 * v2 / cp : 0.f;
-    R[2] = regular ? v2 : 0.f;
-    R[3] = R[1];
-    R[4] = regular ? 1.f + (-v1 * v1) / cp : -1.f;
-    R[5] = regular ? -v1 : 0.f;
-    R[6] = regular ? -v2 : 0.f;
-    R[7] = regular ? v1 : 0.f;
-    R[8] = regular ? 1.f + (-v2 * v2 - v1 * v1) / cp : -1.f;
-}
+// rotation_between_z and the direction of a sample of the fixed ray set: ray_set.hpp (shared with the visibility trace)
 
 // ---- register-free prefetch: global -> LDS DMA (global_load_lds), double buffered per wave -----------------------------
 // Every wave owns two copies of {4 uniform records (4x64 floats), its 4 Gaussians' next 64 sample directions (4x64x3),

@@ -29,6 +29,7 @@ Beside this module: fused_adam (the one-launch Adam), fused_base (what the two i
 bucket all-reduces and their measurement), fused_stage1 (the stage-1 iteration with densification)."""
 import collections
 import contextlib
+import math
 import os
 
 import torch
@@ -40,7 +41,7 @@ from .fused_base import _STREAMS, SUM_SLOTS, FusedStepBase, _in_context, _world_
 from .fused_stage1 import FusedStage1Step                                                 # noqa: F401  (re-exported)
 from .grad_comm import BucketComm
 from .shading_ops import LEAVE_ROOM, TRAIN_OUTPUTS
-from .train_step import FROZEN_GEOMETRY_GROUPS, LAMBDA_DSSIM, STAGE2_WEIGHTS, update_visibility
+from .train_step import FROZEN_GEOMETRY_GROUPS, LAMBDA_DSSIM, STAGE2_WEIGHTS, update_visibility, update_visibility_device
 
 PARAM_NAMES = ("xyz", "normal", "scaling", "rotation", "opacity", "shs", "base_color", "roughness", "incidents", "env")
 
@@ -56,7 +57,7 @@ class FusedStage2Step(FusedStepBase):
     _opt_order = PARAM_NAMES
 
     def __init__(self, params, sample_num, lr=1e-4, lr_rest_scale=1.0, loss_weights=None, process_group=None, lrs=None,
-                 bounded=True):
+                 bounded=True, device_visibility=False):
         """`lrs`: optional per-group learning rates {xyz, normal, scaling, rotation, opacity, shs, shs_rest, base_color,
         roughness, incidents, incidents_rest, env} as GaussianModel.training_setup / DirectLightMap.training_setup set
         them (scene/gaussian_model.py:465-486, the stage-2 values of script/run_nerf.sh:25-31; fused_base.learning_rates).
@@ -74,7 +75,11 @@ class FusedStage2Step(FusedStepBase):
         rotation, opacity and shs are frozen (run_syn4.sh:27-33, run_dtu.sh:29-35) the iteration also skips what only they
         would consume -- the alpha-gradient half of the tile backward and the whole per-Gaussian geometry backward
         (r3dg_rasterize_backward_features instead), the geometry half of the activation chain rule, their all-reduce
-        buckets -- and their entries of `grads` stay zero."""
+        buckets -- and their entries of `grads` stay zero.
+        `device_visibility`: the visibility is traced by train_step.update_visibility_device (the rays are generated inside the
+        trace kernel) instead of update_visibility; while the fixed-ray-set shading kernels apply, `incident_dirs` and
+        `incident_areas` stay None -- no [P,K,3] tensor exists.  `refresh_visibility()` re-traces with the current parameters in
+        either mode."""
         unknown = set(loss_weights or ()) - set(STAGE2_WEIGHTS)
         if unknown:                                  # (before anything is created)
             raise RuntimeError("FusedStage2Step: unknown loss weights %s" % sorted(unknown))
@@ -174,10 +179,15 @@ class FusedStage2Step(FusedStepBase):
         # R3DG_DP_BUCKETS=1 (A/B, message size against overlap): ONE all-reduce of the whole gradient slab behind the backward
         # and one Adam launch behind it, instead of the three buckets A / C / B each sent the moment it is final
         self._single_bucket = self.dp and os.environ.get("R3DG_DP_BUCKETS", "3") == "1"
+        self.device_visibility = bool(device_visibility)
+        self.visibility_refreshes = 0               # refresh_visibility() calls so far (key of the direction-free lookup cache)
         with torch.no_grad(), self._ctx:
             self.refresh_activations()
-            self.visibility, self.incident_dirs, self.incident_areas, self.tracer = update_visibility(
-                self.xyz, self.a_scales, self.a_rot, self.a_opacity, self.a_normal, sample_num, group=process_group)
+            if self.device_visibility:
+                self._trace_on_device()
+            else:
+                self.visibility, self.incident_dirs, self.incident_areas, self.tracer = update_visibility(
+                    self.xyz, self.a_scales, self.a_rot, self.a_opacity, self.a_normal, sample_num, group=process_group)
             # the normals the ray set was generated from (the trained normal moves on; the cached directions do not)
             self._ray_normals = self.a_normal.clone()
         self._taps = self._taps_key = self._taps_size = self._taps_src = self._frs_built = self._uniform_area = None
@@ -243,6 +253,47 @@ class FusedStage2Step(FusedStepBase):
                 0 if zero is None else zero.numel())
         _lib.check(st, "stage2_activate")
 
+    def _frs_wanted(self):
+        """The fixed-ray-set kernels are switched on and take this K and SH degree (the texture size is asked per size: taps)."""
+        return os.environ.get("R3DG_SHADE_FRS", "1") != "0" and shading_ops.FixedRaySet.supported(self.K, self.M, 16, 32)
+
+    def _trace_on_device(self):
+        """visibility (+ the direction cache only where the general shading kernels will read it) of the CURRENT activations, by
+        train_step.update_visibility_device."""
+        self.visibility, self.incident_dirs, self.tracer = update_visibility_device(
+            self.xyz, self.a_scales, self.a_rot, self.a_opacity, self.a_normal, self.K, group=self.group,
+            want_dirs=not self._frs_wanted())
+        self.incident_areas = None if self.incident_dirs is None else torch.full(
+            (self.P, self.K, 1), 2 * math.pi, dtype=torch.float32, device=self.dev)
+
+    def _materialise_dirs(self):
+        """The direction / area caches of the snapshot normals for the general kernels, when a step that holds none meets a texture
+        size the fixed-ray-set kernels do not take (chunked like update_visibility)."""
+        from . import sampling
+        chunk = max(1, self.P // ((self.K - 1) // 24 + 1))
+        self.incident_dirs = torch.cat([sampling.fibonacci_sphere_sampling(self._ray_normals[o:o + chunk], self.K)[0]
+                                        for o in range(0, self.P, chunk)], 0)
+        self.incident_areas = torch.full((self.P, self.K, 1), 2 * math.pi, dtype=torch.float32, device=self.dev)
+
+    @_in_context
+    def refresh_visibility(self):
+        """Re-trace the visibility with the CURRENT parameters (the reference's commented-out "Every 1000 update visibility",
+        train.py:110-112), on the device path whichever way the step was constructed: deferred work is completed, the activations
+        are recomputed, the P x K rays are generated from the current normals and traced, the snapshot normals are replaced and
+        the ray set / lookup cache is rebuilt for the texture size in use.  Parameters, gradients, Adam moments and step counts
+        are untouched.  Data parallel: every rank calls it at the same iteration (one all-gather inside)."""
+        self.flush()
+        size = self._taps_size
+        with torch.no_grad():
+            self.refresh_activations()
+            self._trace_on_device()
+            self._ray_normals = self.a_normal.clone()
+        self.visibility_refreshes += 1
+        self._taps = self._taps_key = self._taps_size = self._taps_src = self._frs_built = self._frs = None
+        self._pre_rotated = None                    # (the rotated coefficients belonged to the old ray set)
+        if size is not None:
+            self.taps(*size)
+
     def taps(self, He, We):
         """The per-sample lookup cache of the general shading kernels for a He x We environment texture
         (shading_ops.build_taps: 12 bytes per sample, read beside the [P,K,3] directions) -- or None when the direction cache IS
@@ -254,6 +305,21 @@ class FusedStage2Step(FusedStepBase):
         # key of its own: only the lookup records depend on it, the ray set (P x K directions regenerated and classified, a host
         # read-back) does not
         src = self.incident_dirs
+        if src is None:
+            # no direction tensor (device_visibility / refresh_visibility): the ray set IS the Fibonacci set of the snapshot
+            # normals by construction -- nothing to regenerate and compare -- and it changes exactly when the visibility is re-traced
+            dir_key, size_key = ("device", self.visibility_refreshes), (He, We)
+            if self._taps_src is not None or self._taps_key != dir_key:
+                self._taps_key, self._taps_src, self._taps_size, self._taps = dir_key, None, None, None
+                self._uniform_area = float(torch.tensor(2 * math.pi, dtype=torch.float32))
+                self._frs_built = shading_ops.FixedRaySet(self._ray_normals, self.K) if self._frs_wanted() else None
+            if self._frs_built is None or not shading_ops.FixedRaySet.supported(self.K, self.M, He, We):
+                self._materialise_dirs()            # the general kernels after all: from here on as with a cached tensor
+                return self.taps(He, We)
+            if self._taps_size != size_key:
+                self._taps_size, self._frs = size_key, self._frs_built
+                self._frs.taps(He, We)
+            return None
         dir_key, size_key = (src._version, tuple(src.shape)), (He, We)
         fresh = self._taps_src is not src or self._taps_key != dir_key
         if fresh:

@@ -1,8 +1,12 @@
-"""Stage-1 training loop around the fused iteration: the densification schedule of the reference's train.py:158-175
+"""Training loops around the fused iterations.  Stage 1: the densification schedule of the reference's train.py:158-175
 (statistics every iteration, densify_and_prune every `densification_interval` after `densify_from_iter`, size threshold
 once past the first opacity reset, reset_opacity every `opacity_reset_interval`) and its from-scratch initialisation
 (`GaussianModel.create_from_pcd`, scene/gaussian_model.py:409-441: isotropic log-scale from the mean squared 3-NN
 distance via distCUDA2, identity rotations, opacity 0.1, SH dc from the point colours).
+
+Stage 2 (`train_stage2`): the fused stage-2 iteration with the per-group rates of GaussianModel.training_setup /
+DirectLightMap.training_setup and, optionally, a periodic re-trace of the visibility on the device -- the hook the reference
+keeps commented out (train.py:110-112, "Every 1000 update visibility").
 
 Only what the hot path needs: no dataset readers, logging, checkpoints or evaluation -- cameras and ground-truth images
 are whatever the caller hands in (synthetic.py in the tests and tools).  Data parallel: every rank runs this loop on its
@@ -14,7 +18,7 @@ import types
 
 import torch
 
-from .fused_step import FusedStage1Step
+from .fused_step import FusedStage1Step, FusedStage2Step
 from .knn_ops import distCUDA2
 
 C0 = 0.28209479177387814          # RGB2SH (utils/sh_utils.py:130-131)
@@ -41,7 +45,11 @@ class Schedule(types.SimpleNamespace):
         super().__init__(iterations=30_000, position_lr_init=0.00016, position_lr_final=0.0000016,
                          position_lr_delay_mult=0.01, position_lr_max_steps=30_000, normal_lr=0.01, sh_lr=0.0025,
                          opacity_lr=0.05,
-                         scaling_lr=0.005, rotation_lr=0.001, percent_dense=0.001, densification_interval=100,
+                         scaling_lr=0.005, rotation_lr=0.001,
+                         # stage 2 (arguments/__init__.py:87-96)
+                         env_lr=0.1, env_rest_lr=0.001, base_color_lr=0.01, roughness_lr=0.01, light_lr=0.001,
+                         light_rest_lr=0.0001, light_init=3.0, visibility_lr=0.0025, visibility_rest_lr=0.0025,
+                         percent_dense=0.001, densification_interval=100,
                          opacity_reset_interval=3000, densify_from_iter=500, densify_until_iter=10_000,
                          densify_grad_threshold=0.0002, densify_grad_normal_threshold=2e-9, normal_densify_from_iter=0,
                          min_opacity=0.005,
@@ -167,6 +175,70 @@ def train_stage1(init, cameras, images, background, extent, schedule=None, itera
         pending = set(getattr(step, "dropped_iterations", ()))
         for k in [k for k in view_of if k <= getattr(step, "_drop_polled", 0) and k not in pending]:
             del view_of[k]
+        if on_iteration is not None:
+            on_iteration(it, step)
+    return step, history
+
+
+def stage2_learning_rates(schedule, extent):
+    """The `lrs` of FusedStage2Step from a Schedule: the param_group rates of GaussianModel.training_setup
+    (scene/gaussian_model.py:465-486; a negative light_rest_lr means light_lr / 20, :476-477) and DirectLightMap.training_setup
+    (scene/direct_light_map.py:18-21).  The baked-visibility SH groups (visibility_lr) are not trained here."""
+    sch = schedule
+    light_rest = sch.light_lr / 20.0 if sch.light_rest_lr < 0 else sch.light_rest_lr
+    return dict(xyz=sch.position_lr_init * extent, normal=sch.normal_lr, scaling=sch.scaling_lr, rotation=sch.rotation_lr,
+                opacity=sch.opacity_lr, shs=sch.sh_lr, shs_rest=sch.sh_lr / 20.0, base_color=sch.base_color_lr,
+                roughness=sch.roughness_lr, incidents=sch.light_lr, incidents_rest=light_rest, env=sch.env_lr)
+
+
+def visibility_refresh_iterations(iterations, visibility_interval):
+    """The iterations after whose optimizer step train_stage2 re-traces the visibility: the multiples of `visibility_interval`
+    in [1, iterations]; none for an interval of 0 (the reference: one trace before the first iteration, train.py:110-112)."""
+    if visibility_interval < 0:
+        raise ValueError("visibility_interval must be >= 0")
+    if visibility_interval == 0:
+        return []
+    return list(range(visibility_interval, iterations + 1, visibility_interval))
+
+
+def train_stage2(restored_or_params, cameras, images, background, extent, sample_num, schedule=None, iterations=None,
+                 visibility_interval=0, masks=None, loss_weights=None, lrs=None, process_group=None, on_iteration=None,
+                 poll_interval=32):
+    """Runs `iterations` fused stage-2 iterations over the (camera, image) pairs in round-robin order.  Returns
+    (FusedStage2Step, history).  `restored_or_params`: the raw parameters of a stage-2 model -- checkpoint.restore(..., pbr=True)
+    with an `env` texture [1,He,We,3] added, or a bench_core.GaussianParams.  `sample_num`: rays per Gaussian.
+    Learning rates: stage2_learning_rates(schedule, extent) under the caller's `lrs` (the frozen-geometry scripts pass zeros:
+    run_syn4.sh:27-33); the xyz rate follows position_lr (gaussians.update_learning_rate, train.py:101) unless it is frozen.
+    `loss_weights`: overrides of train_step.STAGE2_WEIGHTS; `masks[v]` [1,H,W]: view v's object mask.
+    `visibility_interval` > 0: after the optimizer step of every iteration divisible by it the visibility is re-traced with the
+    current parameters (FusedStage2Step.refresh_visibility: on the device, no [P,K,3] tensor) and (iteration, "visibility", P)
+    is appended to the history; 0 never re-traces, which is the reference.  With an interval the step is also BUILT on the device
+    path (device_visibility=True); with 0 it is built exactly as FusedStage2Step builds itself by default.
+    The bounded forward's dropped views are polled every `poll_interval` iterations and at the end, and listed as
+    (iteration, "dropped_views", n) (see train_stage1; stage 2 has no replay)."""
+    sch = schedule or Schedule()
+    n_iter = sch.iterations if iterations is None else iterations
+    refresh_at = set(visibility_refresh_iterations(n_iter, visibility_interval))
+    rates = dict(stage2_learning_rates(sch, extent), **(lrs or {}))
+    step = FusedStage2Step(restored_or_params, sample_num, lr=sch.sh_lr, loss_weights=loss_weights,
+                           process_group=process_group, lrs=rates, device_visibility=visibility_interval > 0)
+    xyz_group = step.opt.groups[step._opt_order.index("xyz")]
+    xyz_scale = rates["xyz"] / (sch.position_lr_init * extent) if sch.position_lr_init * extent != 0.0 else 0.0
+    history = []
+    for it in range(1, n_iter + 1):
+        if "xyz" not in step.frozen:
+            # (a caller's own xyz rate scales the whole decay curve)
+            xyz_group["lr"] = xyz_scale * position_lr(it, sch.position_lr_init * extent, sch.position_lr_final * extent,
+                                                      sch.position_lr_delay_mult, sch.position_lr_max_steps)
+        v = (it - 1) % len(cameras)
+        step(cameras[v], background, images[v], image_mask=None if masks is None else masks[v])
+        if (poll_interval and it % poll_interval == 0) or it == n_iter:
+            dropped = step.poll_overflow()
+            if dropped:
+                history.append((it, "dropped_views", dropped))
+        if it in refresh_at:
+            step.refresh_visibility()
+            history.append((it, "visibility", step.P))
         if on_iteration is not None:
             on_iteration(it, step)
     return step, history

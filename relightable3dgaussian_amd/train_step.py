@@ -84,6 +84,58 @@ def update_visibility(xyz, scales, rotations, opacity, normal, sample_num, group
     return full, dirs_all, areas_all, tracer
 
 
+@torch.no_grad()
+def update_visibility_device(xyz, scales, rotations, opacity, normal, sample_num, group=None, want_dirs=False):
+    """update_visibility with the host-side tensor work moved into the kernels: -> (visibility[P,K,1], incident_dirs[P,K,3] or
+    None, tracer).  One launch prepares the leaf tables and the inverse covariance (RayTracer.from_device_leaves), the build and
+    the record packing are those of update_visibility, and ONE trace launch generates the P x K rays from the packed leaf records
+    (bvh_ops.trace_bundles: Morton order by construction, results in the caller's row order): no chunk loop, no [P,K,3]
+    direction or origin tensor, no gather or scatter.  The sample areas are 2 pi throughout (fibonacci_sphere_sampling).
+    `want_dirs`: also return the directions the kernel generated (callers whose K the fixed-ray-set shading kernels do not take).
+    Every ray's result is the existing trace's for ITS direction bit for bit; the directions agree with
+    sampling.fibonacci_sphere_sampling to a few ulp, so a ray that grazes a box or the 0.9 threshold may land on the other side.
+
+    Data parallel: the sharding of update_visibility -- rank r traces the leaf slots [r*per, (r+1)*per) into its own buffer, the
+    blocks travel in Morton order through ONE all-gather and an index copy places them.  The directions are a function of the
+    normals alone: under a group they are evaluated locally for all rows, in PyTorch."""
+    import torch.distributed as dist
+    world = rank = None
+    if dist.is_available() and dist.is_initialized():
+        world, rank = dist.get_world_size(group), dist.get_rank(group)
+    gather = bool(world) and (world > 1 or os.environ.get("R3DG_DP_SINGLE_RANK") == "1")
+    if not world or world == 1:
+        world, rank = 1, 0
+    from . import bvh_ops
+    P, K, dev = xyz.shape[0], int(sample_num), xyz.device
+    tracer = RayTracer.from_device_leaves(xyz, scales, rotations)
+    op = opacity[:, 0].contiguous()
+    arrays = (xyz, tracer.covs_inv, op, normal)
+    records = bvh_ops.trace_records(tracer.tree, tracer.aabb, *arrays)
+    # (the tracer owns them, as after a trace_visibility call with the same four tensors)
+    tracer._records, tracer._records_ref = records, arrays
+    tracer._records_key = tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in arrays)
+    zsamples = sampling.fibonacci_z_samples(K, dev)[0].t().contiguous()                    # [K,3]
+    vis = torch.empty(P, K, 1, dtype=torch.float32, device=dev)
+    dirs = torch.empty(P, K, 3, dtype=torch.float32, device=dev) if want_dirs else None
+    if not gather:
+        bvh_ops.trace_bundles(records, tracer.tree, zsamples, vis, 0, P, dirs_out=dirs)
+        return vis, dirs, tracer
+    per = -(-P // world)
+    lo, hi = min(P, rank * per), min(P, (rank + 1) * per)
+    bvh_ops.trace_bundles(records, tracer.tree, zsamples, vis, lo, hi)
+    order = tracer.tree[P - 1:, 3].long()
+    padded = torch.zeros(per, K, 1, dtype=torch.float32, device=dev)
+    padded[:hi - lo] = vis[order[lo:hi]]
+    gathered = torch.empty(world * per, K, 1, dtype=torch.float32, device=dev)
+    dist.all_gather(list(gathered.view(world, per, K, 1).unbind(0)), padded, group=group)
+    vis[order] = gathered[:P]
+    if want_dirs:
+        chunk = max(1, P // ((K - 1) // 24 + 1))
+        for off in range(0, P, chunk):
+            dirs[off:off + chunk] = sampling.fibonacci_sphere_sampling(normal[off:off + chunk], K)[0]
+    return vis, dirs, tracer
+
+
 LAMBDA_DSSIM = 0.2          # arguments/__init__.py:125
 
 
