@@ -257,6 +257,17 @@ int r3dg_shade_forward_transport(void* stream, int P, int K, const float* d_base
                                  const float* d_normals, const float* d_viewdirs, const float* d_transport,
                                  const float* d_consts, const float* d_zsamples, const float* d_incident_dirs,
                                  float* d_out);
+/* The same transport cache WITHOUT a stored direction: for callers whose samples are the fixed ray set -- d_k =
+ * normalize(R(n) z_k), z_k = d_zsamples [K,3], R = rotation_between_z (the rays r3dg_bvh_trace_bundles generates, csrc/ray_set.hpp)
+ * -- with the uniform area `uniform_area`.  One launch does what r3dg_shade_build_taps (with d_env_radiance) followed by
+ * r3dg_shade_build_transport does for those directions: per sample the direction is regenerated from d_normals, rotated by
+ * d_env_transform [3,3] (NULL = none), looked up in d_env [He,We,3] (lat-long, bilinear, zero padding) and turned into the
+ * transport above, which goes to d_transport [P*K*3] (a fresh buffer, nothing is read from it); d_consts [P*16] as above.
+ * Streams 4 B (visibility) in and 12 B out per sample where the two-kernel path moves 52 B.  M in {1, 4, 9, 16}, K > 0. */
+int r3dg_shade_build_transport_rayset(void* stream, int P, int K, int M, const float* d_normals, const float* d_incidents,
+                                      const float* d_visibility, const float* d_zsamples, float uniform_area,
+                                      const float* d_env, int He, int We, const float* d_env_transform,
+                                      float* d_transport, float* d_consts);
 /* Relighting under a light that TURNS WITH EVERY FRAME (relighting.py:160-161 with configs/nerf_syn_light or configs/tnt
  * light_transform.json) and static Gaussians: the "split transport" cache holds what does NOT depend on the light --
  *   d_lt [K,P,4]: per sample (max(SH_incident(d), 0) * a, a) with a = area * max(n . d, 0);  d_vis_t [K/4,P,4]: the visibility

@@ -26,6 +26,8 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno
 # shading units: VALU-bound transcendental-heavy float math; fp32 tolerance is 1e-4, so reciprocal/sqrt approximations
 # (v_rcp_f32, v_sqrt_f32: 1 ulp) replace the IEEE division/sqrt expansions
 SHADING_FLAGS = ["-ffast-math", "-fno-slp-vectorize"]
+# (shading_relight_rayset.hip regenerates the visibility trace's ray set and must get its directions bit for bit: no fast-math,
+# and the file itself switches contraction off around ray_set.hpp)
 # LBVH units: Morton codes decide the tree topology, slab comparisons decide integer hit counts -> as the CPU oracle computes them
 BVH_FLAGS = ["-ffp-contract=off"]
 EXTRA = {

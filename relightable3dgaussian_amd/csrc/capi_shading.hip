@@ -69,6 +69,24 @@ int r3dg_shade_build_transport(void* stream_, int P, int K, int M, const float* 
     });
 }
 
+int r3dg_shade_build_transport_rayset(void* stream_, int P, int K, int M, const float* normals, const float* incidents,
+                                      const float* visibility, const float* zsamples, float uniform_area, const float* env,
+                                      int He, int We, const float* env_transform, float* transport, float* consts)
+{
+    if (P < 0 || K <= 0) return invalid("shade_build_transport_rayset: bad P/K");
+    if (M != 1 && M != 4 && M != 9 && M != 16)
+        return invalid("shade_build_transport_rayset: incidents must hold 1, 4, 9 or 16 SH coefficients");
+    if (He <= 0 || We <= 0 || He > 32767 || We > 32767) return invalid("shade_build_transport_rayset: bad env size");
+    if (P == 0) return R3DG_OK;
+    if (!normals || !incidents || !visibility || !zsamples || !env || !transport || !consts)
+        return invalid("shade_build_transport_rayset: null buffer");
+    return guarded([&]() -> int {
+        launch_shade_build_transport_rayset((hipStream_t)stream_, P, K, M, normals, incidents, visibility, zsamples, uniform_area,
+                                            env, He, We, env_transform, transport, consts);
+        return R3DG_OK;
+    });
+}
+
 int r3dg_shade_build_split(void* stream_, int P, int K, const int32_t* perm, const float* normals, const float* incidents,
                            const float* visibility, const float* incident_dirs, const float* zsamples, float uniform_area,
                            float* lt, float* vis_t, float* consts)

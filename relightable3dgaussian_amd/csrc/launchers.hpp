@@ -102,6 +102,9 @@ void launch_shade_env_footprints(hipStream_t s, int He, int We, const float* env
 void launch_shade_build_transport(hipStream_t s, int P, int K, int M, const float* normals, const float* incidents,
                                   const float* visibility, const float* dirs, const float* areas, float uniform_area,
                                   float* radiance_to_transport, float* consts);
+void launch_shade_build_transport_rayset(hipStream_t s, int P, int K, int M, const float* normals, const float* incidents,
+                                         const float* visibility, const float* zsamples, float uniform_area, const float* env,
+                                         int He, int We, const float* tr, float* transport, float* consts);
 void launch_shade_forward_transport(hipStream_t s, int P, int K, const float* base_color, const float* roughness,
                                     const float* normals, const float* viewdirs, const float* transport, const float* consts,
                                     const float* zsamples, const float* dirs, float* out);

@@ -1,9 +1,10 @@
 // The fixed ray set of a visibility update: sample k of the Gaussian with normal n is d_k = normalize(R(n) z_k), z_k the
 // K-entry Fibonacci table around +z (sampling.fibonacci_z_samples) and R = rotation_between_z (utils/sh_utils.py:36-68).
 // ONE definition for everybody who regenerates the directions instead of reading a [P,K,3] tensor: the fixed-ray-set shading
-// kernels (shading_frs.hip, shading_split.hpp, shading_transport.hpp) and the bundle source of the visibility trace
-// (bvh_trace.hip), so that trace and shading see one ray set.  The units are compiled with different floating-point flags
-// (-ffast-math for the shading units, -ffp-contract=off for the trace): the operations are the same, their last bits are not.
+// kernels (shading_frs.hip, shading_split.hpp, shading_transport.hpp, shading_transport_rayset.hpp) and the bundle source of the
+// visibility trace (bvh_trace.hip), so that trace and shading see one ray set.  The units are compiled with different
+// floating-point flags (-ffast-math for the shading units, -ffp-contract=off for the trace): the operations are the same, their
+// last bits are not -- except in shading_relight_rayset.hip, which includes this header under the trace's regime.
 #pragma once
 
 namespace r3dg {

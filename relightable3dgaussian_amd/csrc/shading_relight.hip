@@ -1,5 +1,6 @@
-// Launchers of the relight frame's two opt-in caches: the transport cache under a fixed light (shading_transport.hpp) and
-// the split transport cache under a light that turns with every frame (shading_split.hpp).
+// Launchers of the relight frame's two opt-in caches: the transport cache under a fixed light (shading_transport.hpp; its
+// builder from the ray set alone has a unit of its own, shading_relight_rayset.hip) and the split transport cache under a light
+// that turns with every frame (shading_split.hpp).
 #include "shading_host.hpp"
 #include "shading_transport.hpp"
 #include "shading_split.hpp"

@@ -1,8 +1,9 @@
 // The relight frame's opt-in transport cache: builder + per-frame kernel (see the banner below).  Included by
 // shading_relight.hip, which holds the launchers, and, unchanged, by the CPU emulation in tests/emu -- so it depends on
-// shading_math.hpp alone.
+// shading_math.hpp and the layout header alone.
 #pragma once
 #include "shading_math.hpp"
+#include "shading_transport_layout.hpp"
 
 namespace r3dg {
 
@@ -20,16 +21,6 @@ namespace r3dg {
 // graphics_utils.py:9-37), or read from the cache when the caller passes it -- and evaluates ~80 instead of ~290
 // instructions per sample.  One wave per Gaussian, lane = sample; plain (non-persistent) launches.
 // =====================================================================================================================
-constexpr int TR_WAVES = 4;
-constexpr int TR_CONSTS = 16;     // floats per Gaussian: diffuse_light 3 | incident light 3 | local 3 | global 3 | visibility 1 | pad
-
-// (common.hpp's wave_sum, restated: the CPU emulation compiles this header and cannot include the HIP-only common.hpp)
-__device__ __forceinline__ float wave_sum64(float x)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
 
 __global__ void __launch_bounds__(64 * TR_WAVES)
 shade_build_transport_kernel(int P, int K, int M, const float* __restrict__ normals, const float* __restrict__ incidents,

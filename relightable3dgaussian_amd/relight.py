@@ -7,6 +7,12 @@ r3dg_shade_forward, r3dg_relight_pack_features, the rasterizer forward, r3dg_rel
 around the two hot kernels where the reference (and `frame_reference` below, the parity target) spends a few dozen
 PyTorch elementwise launches.  The capture maps of neilf.py:146-182 (CAPTURE_MAPS) come from one more pass over the feature
 image, r3dg_relight_capture, when a caller asks for them.  Replicas only under multi-GPU: frames are independent, no collective.
+
+Construction traces the visibility of the snapshot it takes.  By default through train_step.update_visibility (PyTorch glue
+around the trace; visibility, directions, areas and the cache records stay resident: 32 bytes per sample).  With
+`RelightRenderer(device_visibility=True)` through train_step.update_visibility_device and, for the transport cache,
+r3dg_shade_build_transport_rayset: no [P,K,3] direction tensor, no area tensor, 16 bytes per sample -- the path for composites
+(compose_scenes), whose concatenated objects must be re-traced at relighting sample counts.
 """
 import math
 
@@ -14,7 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, rasterizer_ops, sampling, shading_ops
-from .train_step import rgb_to_srgb, update_visibility   # noqa: F401  (rgb_to_srgb: part of this module's surface)
+from .train_step import rgb_to_srgb, update_visibility, update_visibility_device   # noqa: F401  (rgb_to_srgb: part of this module's surface)
 
 
 # the maps render_view(is_training=False) derives from the feature image (neilf.py:146-182) and their channel counts
@@ -61,7 +67,7 @@ class RelightRenderer:
     bench_core.GaussianParams and fused_step.FusedStage2Step both do.  `envmap` [He,We,3] HDR (EnvLight.envmap)."""
 
     def __init__(self, model, envmap, sample_num, process_group=None, cache="transport", regenerate_dirs=True,
-                 base_color_scale=None):
+                 base_color_scale=None, device_visibility=False):
         """`base_color_scale` [3] (None: nothing changes): multiplies the ACTIVATED base colour before shading and packing, as
         GaussianModel.get_base_color does with the per-scene albedo scale that eval_relighting_syn4.py:96-103 sets.
         `cache` -- what is kept between frames while the light does not change:
@@ -73,7 +79,21 @@ class RelightRenderer:
             path by itself (see _taps_for), so nothing can go stale.  `regenerate_dirs`: the kernel rebuilds each
             direction from the normal and the Fibonacci table instead of reading the direction cache.
         "radiance": only the sampled environment radiance of every cached direction (12 bytes per sample) is kept and the
-            full integral (r3dg_shade_forward_cached) runs per frame."""
+            full integral (r3dg_shade_forward_cached) runs per frame.
+        `device_visibility` (default False: nothing changes): the visibility is traced by train_step.update_visibility_device
+            (the rays are generated in the trace kernel; sharded over `process_group` like update_visibility) and the transport
+            cache is built by ONE r3dg_shade_build_transport_rayset launch from the normals and the Fibonacci table.
+            `incident_areas` is None (every area is 2 pi by construction, nothing is read back) and `incident_dirs` is None
+            unless `cache` is "radiance": resident per sample are the visibility (4 bytes) and the transport (12) instead of 32
+            bytes.  Needs `regenerate_dirs`.  The caches are then keyed on the visibility tensor and the normal snapshot (the
+            directions are a function of the normals; a swapped-in `incident_dirs` is not noticed).  What still reads a stored
+            direction tensor -- the radiance cache; the general kernel r3dg_shade_forward_cached that a turning light falls
+            back to when shading_ops.split_supported is false or the light transform is no rotation; frame_reference --
+            materialises `incident_dirs` on first use (_directions: sampling.fibonacci_sphere_sampling in chunks, 12 bytes per
+            sample resident from then on plus a transient of about three chunks of [P / ((K-1)//24 + 1), K, 3])."""
+        self.device_visibility = bool(device_visibility)
+        if self.device_visibility and not regenerate_dirs:
+            raise RuntimeError("RelightRenderer: device_visibility=True keeps no direction tensor; it needs regenerate_dirs=True")
         if cache not in ("radiance", "transport"):
             raise RuntimeError("RelightRenderer: cache must be 'radiance' or 'transport'")
         self.cache, self.regenerate_dirs = cache, bool(regenerate_dirs)
@@ -116,8 +136,31 @@ class RelightRenderer:
             self._order_stream = shared_stream(dev, "order")
         with torch.no_grad():
             self._activate(torch.zeros(3, device=dev))
-            self.visibility, self.incident_dirs, self.incident_areas, self.tracer = update_visibility(
-                self.xyz, self.a_scales, self.a_rot, self.a_opacity, self.a_normal, sample_num, group=process_group)
+            if self.device_visibility:
+                self.visibility, self.incident_dirs, self.tracer = update_visibility_device(
+                    self.xyz, self.a_scales, self.a_rot, self.a_opacity, self.a_normal, sample_num, group=process_group,
+                    want_dirs=(cache == "radiance"))
+                self.incident_areas, self._uniform_area = None, 2.0 * math.pi       # (fibonacci_sphere_sampling: 2 pi to all)
+            else:
+                self.visibility, self.incident_dirs, self.incident_areas, self.tracer = update_visibility(
+                    self.xyz, self.a_scales, self.a_rot, self.a_opacity, self.a_normal, sample_num, group=process_group)
+
+    def _sample_tensors(self):
+        """The tensors the per-sample caches are keyed on (address + version) and reference while they are the key: the
+        direction cache; with device_visibility, where there may be none, the visibility and the normal snapshot."""
+        return (self.visibility, self.normal) if self.device_visibility else (self.incident_dirs,)
+
+    def _directions(self):
+        """`incident_dirs`; a device_visibility renderer that holds none fills it here, on first use, in the chunks of
+        update_visibility (the directions update_visibility_device evaluates under a process group)."""
+        if self.incident_dirs is None:
+            P, K = self.P, self.K
+            dirs = torch.empty(P, K, 3, dtype=torch.float32, device=self.dev)
+            chunk = max(1, P // ((K - 1) // 24 + 1))
+            for off in range(0, P, chunk):
+                dirs[off:off + chunk] = sampling.fibonacci_sphere_sampling(self.a_normal[off:off + chunk], K)[0]
+            self.incident_dirs = dirs
+        return self.incident_dirs
 
     def _taps_for(self, tr, He, We, given=None):
         """shading_ops.build_taps of the direction cache for this light rotation (None = identity); one entry is kept, so
@@ -135,24 +178,37 @@ class RelightRenderer:
         # (the map and the direction cache are held by this object, so their addresses are theirs alone for as long as the
         # key is; a caller that swaps either in gets a new key through the version / address pair of the new tensor while the
         # old one is still referenced below)
-        key = (ident, He, We, self.incident_dirs.data_ptr(), self.incident_dirs._version, self.envmap.data_ptr(),
-               self.envmap._version)
+        samples = self._sample_tensors()
+        key = (ident, He, We) + tuple(v for t in samples for v in (t.data_ptr(), t._version)) + (
+            self.envmap.data_ptr(), self.envmap._version)
         # A light that turns with EVERY frame (configs/nerf_syn_light, configs/tnt): writing the cache costs what the lookup
         # inside the shading kernel costs and the kernel would then still have to read it back -- from the second
         # consecutive change on, no cache: None = r3dg_shade_forward_cached evaluates the lookup itself (measured: 3.6 ms
         # per frame with a rebuild, 2.5 without).  A light that stops turning gets its cache back on
         # the next frame.
         changed = self._light_key != key
-        self._light_key, self._light_ref = key, (tr, self.incident_dirs, self.envmap)
+        self._light_key, self._light_ref = key, (tr, samples, self.envmap)
         self._light_changes = (self._light_changes + 1) if changed else 0
         if self._light_changes >= 2 and self._area_key is not None:          # (the first frame always builds)
             return None
-        if self._taps_key != key:
+        if self._taps_key != key and self.device_visibility and self.cache == "transport":
+            # the whole cache -- direction, lookup, radiance, transport, constants -- in one launch from the normals and the
+            # Fibonacci table; the record buffer of the previous light is reused
+            if self._zsamples is None:
+                self._zsamples = sampling.fibonacci_z_samples(self.K, self.dev)[0].t().contiguous()      # [K,3]
+            self._taps, self._consts = shading_ops.build_transport_rayset(
+                self.a_normal, self.incidents, self.visibility, self._zsamples, self._uniform_area, self.envmap, tr,
+                self._taps, self._consts)
+            self._taps_key, self._taps_ref = key, (tr, samples, self.envmap)
+            self._area_key = 0                                 # (no area tensor: nothing to read back, ever)
+        elif self._taps_key != key:
             # the HDR map is fixed while relighting, so the SAMPLED RADIANCE of every cached direction is cached (not just
             # the lookup coordinates): the shading kernel then reads 12 bytes per sample and no texture
-            self._taps = shading_ops.build_taps(self.incident_dirs, He, We, tr, radiance_of=self.envmap)
-            self._taps_key, self._taps_ref = key, (tr, self.incident_dirs, self.envmap)
-            if self._area_key != self.incident_areas.data_ptr():
+            self._taps = shading_ops.build_taps(self._directions(), He, We, tr, radiance_of=self.envmap)
+            self._taps_key, self._taps_ref = key, (tr, samples, self.envmap)
+            if self.incident_areas is None:
+                self._area_key = 0                             # (device_visibility: 2 pi by construction)
+            elif self._area_key != self.incident_areas.data_ptr():
                 # fibonacci_sphere_sampling gives every sample the area 2 pi: then the area cache need not be read at all
                 lo, hi = float(self.incident_areas.min()), float(self.incident_areas.max())
                 self._uniform_area = lo if lo == hi else None
@@ -187,15 +243,15 @@ class RelightRenderer:
             t = given.detach().to(torch.float64).reshape(3, 3)
             if float((t @ t.t() - torch.eye(3, dtype=torch.float64)).abs().max()) > 1e-4:
                 return None                       # scaled / sheared light transform: the general kernel handles it
-        sample_key = (self.incident_dirs.data_ptr(), self.incident_dirs._version, self.visibility.data_ptr(),
-                      self.visibility._version, self.regenerate_dirs)
+        samples = self._sample_tensors() if self.device_visibility else (self.incident_dirs, self.visibility)
+        sample_key = tuple(v for t in samples for v in (t.data_ptr(), t._version)) + (self.regenerate_dirs,)
         env_key = (self.envmap.data_ptr(), self.envmap._version, He, We)
         sp = self._split if isinstance(self._split, dict) else None
         if sp is None or sp["sample_key"] != sample_key:
             zs = sampling.fibonacci_z_samples(self.K, self.dev)[0].t().contiguous()
             new = shading_ops.build_split(normal_order(self.a_normal), self.a_normal, self.incidents, self.visibility,
                                           None if self.regenerate_dirs else self.incident_dirs, zs, float(self._uniform_area))
-            new.update(sample_key=sample_key, sample_ref=(self.incident_dirs, self.visibility),
+            new.update(sample_key=sample_key, sample_ref=samples,
                        env4=None if sp is None else sp["env4"], env_key=None if sp is None else sp["env_key"],
                        env_ref=None if sp is None else sp["env_ref"])
             sp = self._split = new
@@ -220,7 +276,7 @@ class RelightRenderer:
         _lib.check(L.r3dg_shade_forward_cached(
             stream(), P, self.K, self.M, self.a_base.data_ptr(), self.a_rough.data_ptr(), self.a_normal.data_ptr(),
             self.a_viewdirs.data_ptr(), self.incidents.data_ptr(), self.envmap.data_ptr(), He, We, _lib.ptr(tr),
-            self.visibility.data_ptr(), self.incident_dirs.data_ptr(),
+            self.visibility.data_ptr(), self._directions().data_ptr(),
             None if self._uniform_area is not None else self.incident_areas.data_ptr(), self._uniform_area or 0.0,
             # no cache (a light that changes every frame): lookup in the kernel
             taps.data_ptr() if taps is not None else None, shading_ops.TAPS_ARE_RADIANCE if taps is not None else 0,
@@ -342,8 +398,13 @@ def frame_reference(renderer, cam, bg, env_transform=None, exact_activations=Fal
         if getattr(r, "base_color_scale", None) is not None:
             base_color = base_color * r.base_color_scale
     tr = None if env_transform is None else env_transform.to(r.dev, torch.float32).contiguous()
+    # (a device_visibility renderer holds no direction or area tensor: the directions are materialised on it, on first use, and
+    # stay; the areas, 2 pi each, live for this call)
+    dirs, areas = r._directions(), r.incident_areas
+    if areas is None:
+        areas = torch.full((r.P, r.K, 1), r._uniform_area, dtype=torch.float32, device=r.dev)
     pbr, diffuse, rest = shading_ops.shade(base_color, roughness, normal, viewdirs, r.incidents, r.envmap, r.visibility,
-                                           r.incident_dirs, r.incident_areas, tr)
+                                           dirs, areas, tr)
     xyz_h = torch.cat([r.xyz, torch.ones_like(r.xyz[:, :1])], -1)
     depths = (xyz_h @ cam.world_view_transform)[:, 2:3]
     feats = torch.cat([depths, depths.square(), pbr, normal, base_color, roughness, diffuse, rest], -1)      # S = 28
@@ -403,7 +464,10 @@ def transform_object(params, transform):
 def compose_scenes(objects, transforms):
     """scene_composition (relighting.py:28-52): every object's parameters under its own 4x4 transform, concatenated row
     wise in the order given; the incident-light coefficients of the composite are zeroed (:49-50).  `objects`: dicts of
-    raw parameter tensors with identical keys.  Returns one dict (feed it to RelightRenderer through a namespace)."""
+    raw parameter tensors with identical keys.  Returns one dict (feed it to RelightRenderer through a namespace).
+    The composite's visibility is traced anew by the renderer it is fed to (relighting.py:119): at a composite's size and
+    relighting sample counts pass `device_visibility=True` there, which traces and builds the transport cache without a
+    direction tensor."""
     if not objects or len(objects) != len(transforms):
         raise RuntimeError("compose_scenes needs one transform per object")
     moved = [transform_object(o, t) for o, t in zip(objects, transforms)]

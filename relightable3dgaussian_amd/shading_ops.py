@@ -138,6 +138,34 @@ def build_transport(normals, incidents, visibility, incident_dirs, incident_area
     return consts
 
 
+def build_transport_rayset(normals, incidents, visibility, zsamples, uniform_area, env, env_transform=None, transport=None,
+                           consts=None):
+    """r3dg_shade_build_transport_rayset: the transport cache of build_taps(..., radiance_of=env) + build_transport in ONE launch
+    for the fixed ray set of `normals` and `zsamples` [K,3] (no direction tensor is read or written) -> (transport [P,K,3],
+    consts [P,16]); `transport` / `consts`: buffers to reuse (fully overwritten)."""
+    P, K, M = normals.shape[0], zsamples.shape[0], incidents.shape[1]
+    He, We = env.shape[0], env.shape[1]
+    f = dict(dtype=torch.float32, device=normals.device)
+    if transport is None:
+        transport = torch.empty(P, K, 3, **f)
+    elif transport.dtype != torch.float32 or transport.numel() != 3 * P * K or not transport.is_contiguous():
+        raise RuntimeError("transport must be a contiguous float32 [P,K,3] tensor")
+    if consts is None:
+        consts = torch.empty(P, 16, **f)
+    elif consts.dtype != torch.float32 or consts.numel() != 16 * P or not consts.is_contiguous():
+        raise RuntimeError("consts must be a contiguous float32 [P,16] tensor")
+    if visibility.numel() != P * K:
+        raise RuntimeError("visibility must hold P x K values")
+    t = [_c(x) for x in (normals, incidents, visibility, zsamples, env)]
+    tr = _c(env_transform) if env_transform is not None else None
+    with torch.cuda.device(normals.device):
+        _lib.check(_lib.lib().r3dg_shade_build_transport_rayset(
+            _lib.current_stream(), P, K, M, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
+            float(uniform_area), t[4].data_ptr(), int(He), int(We), _lib.ptr(tr), transport.data_ptr(), consts.data_ptr()),
+            "shade_build_transport_rayset")
+    return transport, consts
+
+
 def shade_forward_transport(base_color, roughness, normals, viewdirs, transport, consts, zsamples, incident_dirs=None, out=None):
     """r3dg_shade_forward_transport: the GGX lobe of every sample against the cached transport -> out[P,19].
     `incident_dirs` None: the directions are regenerated from the normals and `zsamples` [K,3]."""
