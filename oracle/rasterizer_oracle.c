@@ -558,6 +558,259 @@ void r3dgo_render_backward(int W, int H, int S, const uint32_t* ranges, const ui
         }
 }
 
+/* ---- r3dgo_render_backward_bounds: the tile pass again, with every sum's ROUNDING SCALE next to it --------------------------
+ * Twin of r3dgo_render_backward (same terms, same order of operations per term).  All five arrays are rows of one
+ * [P, NC] table, NC = 11 + S:  0..2 dL_dmean2D | 3..6 dL_dconic2D | 7 dL_dopacity | 8..10 dL_dcolors | 11.. dL_dfeature.
+ *   sums   the signed sum of the fp32 terms (sum_mode 0: in double, bit-identical to r3dgo_render_backward;
+ *          1: fp32 in pixel order; 2: fp32 in reverse pixel order; 3: fp32 per 8x8 pixel block, then fp32 across blocks)
+ *   E      sum over the terms of  w_t |t|_abs, in units of one fp32 rounding u = 2^-24 (the caller multiplies)
+ *   Epix   [P,2] the same for dL_dmean2D.xy with the reference's per-pixel form |A dx + B dy| where E holds the form the
+ *          tile kernel computes, |A| sum|m dx| + |B| sum|m dy| (>= the per-pixel form)
+ *   count  [P] number of terms (every blended (pixel, Gaussian) pair adds one term to each element of the row)
+ * |t|_abs is the term with every signed sub-sum (c - accum_rec, the channel sum of dL_dalpha, its background piece,
+ * A dx + B dy) replaced by the sum of the absolute values of its pieces.
+ * w_t counts the roundings by which two correct fp32 evaluations of the term may differ (each rounding <= u relative):
+ *   e_G   = 2 + 6 pabs    exp(): power is 7 rounded operations on pieces of total magnitude pabs = |q_xx| + |q_yy| + |q_xy|
+ *                         (<= 4 u pabs absolute, i.e. relative in G), v_exp_f32's argument scaling and result 2 u |power| + 2 u
+ *   e_a   = e_G + 1       alpha = opacity G (0 where min(0.99, .) saturates)
+ *   b_i   = 2 + e_a alpha/(1 - alpha)      one step of T: (1 - alpha) and the division / product, plus alpha's own error
+ *   w_T   = sum of b_i over ALL blended entries of the pixel (T_final is that product) + those walked back so far
+ *   w_A   = sum over the steps walked of 3 + e_a (1 + alpha/(1 - alpha))     accum_rec: two products, one sum, alpha's error
+ *   dL_dalpha:  T sum (|c| + |accum_rec|) |dL_dchannel|      w1 = w_A + w_T + NCH + 4   (subtract, multiply, NCH-term sum, x T)
+ *               T_final/(1 - alpha) sum |bg dL_dpixel|        w2 = w_T(all) + e_a alpha/(1 - alpha) + 7  (3-term dot, divide, add)
+ *   then  dL_dopacity  G dL_dalpha                 + e_G + 1
+ *         dL_dconic    0.5 G dx dx opacity dL_dalpha   + e_G + 6   (dx, dy, G dx, x dx, opacity x, x dL_dG)
+ *         dL_dmean2D   W/2 (A m dx + B m dy)           + e_G + 7   (the same and the conic product / sum)
+ *         colours, features, depth channel:  alpha T dL_dchannel   w = w_T + e_a + 2
+ * perturb > 0: a correct-but-different evaluation -- every exp result is multiplied by 1 + perturb e_G u r, every T step by
+ * 1 + 2 perturb u r, every accum_rec step by 1 + 3 perturb u r, T_final by 1 + perturb w_T(all) u r, r uniform in [-1, 1]
+ * from a hash of (seed, pixel, entry, slot); the discrete decisions are taken on the unperturbed values. */
+static double r3dgo_unit(uint32_t seed, uint32_t a, uint32_t b, uint32_t c)
+{
+    uint32_t h = seed * 0x9E3779B1u ^ (a + 0x7F4A7C15u) * 0x85EBCA6Bu;
+    h ^= h >> 15; h *= 0xC2B2AE35u; h ^= (b + 0x165667B1u) * 0x27D4EB2Fu;
+    h ^= h >> 13; h *= 0x85EBCA6Bu; h ^= (c + 0x9E3779B9u) * 0xC2B2AE35u;
+    h ^= h >> 16; h *= 0x27D4EB2Fu; h ^= h >> 15;
+    return (double)h / 2147483648.0 - 1.0;
+}
+
+void r3dgo_render_backward_bounds(int P, int W, int H, int S, const uint32_t* ranges, const uint32_t* point_list,
+                                  const float* bg_color, const float* means2D, const float* depths,
+                                  const float* conic_opacity, const float* colors, const float* features,
+                                  const float* final_Ts, const uint32_t* n_contrib, const float* dL_dpixels,
+                                  const float* dL_dpixels_o, const float* dL_dpixels_d, const float* dL_dpixels_f,
+                                  int backward_geometry, int sum_mode, float perturb, uint32_t seed, double* sums,
+                                  double* E, double* Epix, int32_t* count)
+{
+    const int gx = (W + BLOCK_X - 1) / BLOCK_X;
+    const size_t HW = (size_t)H * W;
+    const int NC = 11 + S;
+    const double U = 1.0 / 16777216.0;
+    const float ddelx_dx = (float)(0.5 * W), ddely_dy = (float)(0.5 * H);
+    const int NCH = 3 + (backward_geometry ? S : 0) + 2;
+    float* facc = sum_mode ? (float*)calloc((size_t)P * NC, sizeof(float)) : NULL;
+    float* fblk = sum_mode == 3 ? (float*)calloc((size_t)P * NC, sizeof(float)) : NULL;
+    uint8_t* touched = sum_mode == 3 ? (uint8_t*)calloc((size_t)P, 1) : NULL;
+    uint32_t* tlist = sum_mode == 3 ? (uint32_t*)malloc(sizeof(uint32_t) * (size_t)(P > 0 ? P : 1)) : NULL;
+    size_t ntouched = 0;
+    /* pixel order */
+    size_t* order = (size_t*)malloc(sizeof(size_t) * (HW > 0 ? HW : 1));
+    size_t* blk_of = sum_mode == 3 ? (size_t*)malloc(sizeof(size_t) * (HW > 0 ? HW : 1)) : NULL;
+    if (sum_mode == 3) {
+        size_t n = 0;
+        const int bxn = (W + 7) / 8, byn = (H + 7) / 8;
+        for (int by = 0; by < byn; by++)
+            for (int bx = 0; bx < bxn; bx++)
+                for (int y = 8 * by; y < 8 * by + 8 && y < H; y++)
+                    for (int x = 8 * bx; x < 8 * bx + 8 && x < W; x++) {
+                        blk_of[n] = (size_t)by * bxn + bx;
+                        order[n++] = (size_t)W * y + x;
+                    }
+    } else {
+        for (size_t i = 0; i < HW; i++) order[i] = sum_mode == 2 ? HW - 1 - i : i;
+    }
+#define R3DGO_ADD(g_, comp_, val_)                                                   \
+    do {                                                                             \
+        const size_t at_ = (size_t)(g_) * NC + (comp_);                              \
+        if (sum_mode == 0) sums[at_] += (double)(val_);                              \
+        else if (sum_mode == 3) fblk[at_] += (val_);                                 \
+        else facc[at_] += (val_);                                                    \
+    } while (0)
+    for (size_t oi = 0; oi < HW; oi++) {
+        if (sum_mode == 3 && oi > 0 && blk_of[oi] != blk_of[oi - 1]) {
+            for (size_t q = 0; q < ntouched; q++) {
+                const size_t g = tlist[q];
+                for (int c = 0; c < NC; c++) {
+                    facc[g * NC + c] += fblk[g * NC + c];
+                    fblk[g * NC + c] = 0.f;
+                }
+                touched[g] = 0;
+            }
+            ntouched = 0;
+        }
+        const size_t pix_id = order[oi];
+        const int py = (int)(pix_id / W), px = (int)(pix_id % W);
+        const int tile = (py / BLOCK_Y) * gx + (px / BLOCK_X);
+        const uint32_t r0 = ranges[2 * tile], r1 = ranges[2 * tile + 1];
+        const float pixf[2] = {(float)px, (float)py};
+        const uint32_t last_contributor = n_contrib[pix_id];
+        /* first walk: the rounding budget of T_final (the product over every blended entry) */
+        double w_all = 0;
+        {
+            uint32_t contributor = r1 - r0;
+            for (uint32_t kk = r1; kk > r0; kk--) {
+                const uint32_t g = point_list[kk - 1];
+                contributor--;
+                if (contributor >= last_contributor) continue;
+                float dx = means2D[2 * g] - pixf[0], dy = means2D[2 * g + 1] - pixf[1];
+                const float* con_o = conic_opacity + 4 * g;
+                const float power = -0.5f * (con_o[0] * dx * dx + con_o[2] * dy * dy) - con_o[1] * dx * dy;
+                if (power > 0.0f) continue;
+                const float G = expf(power);
+                const float alpha = fminf(0.99f, con_o[3] * G);
+                if (alpha < 1.0f / 255.0f) continue;
+                const double pabs = 0.5 * (fabs((double)con_o[0] * dx * dx) + fabs((double)con_o[2] * dy * dy)) +
+                                    fabs((double)con_o[1] * dx * dy);
+                const double eA = (con_o[3] * G >= 0.99f) ? 0.0 : 3.0 + 6.0 * pabs;
+                w_all += 2.0 + eA * (double)alpha / (1.0 - (double)alpha);
+            }
+        }
+        float T_final = final_Ts[pix_id];
+        if (perturb > 0) T_final = (float)((double)T_final * (1.0 + perturb * w_all * U * r3dgo_unit(seed, (uint32_t)pix_id, 0xFFFFFFFFu, 0)));
+        float T = T_final;
+        uint32_t contributor = r1 - r0;
+        float accum_rec[3] = {0, 0, 0}, accum_rec_d = 0, accum_rec_o = 0, accum_rec_f[64];
+        double abs_rec[3] = {0, 0, 0}, abs_rec_d = 0, abs_rec_o = 0, abs_rec_f[64];
+        float dL_dpixel[3], dL_dpixel_f[64];
+        for (int i = 0; i < 3; i++) dL_dpixel[i] = dL_dpixels[i * HW + pix_id];
+        float dL_dpixel_d = dL_dpixels_d[pix_id], dL_dpixel_o = dL_dpixels_o[pix_id];
+        for (int i = 0; i < S; i++) {
+            dL_dpixel_f[i] = dL_dpixels_f[i * HW + pix_id];
+            accum_rec_f[i] = 0;
+            abs_rec_f[i] = 0;
+        }
+        float last_alpha = 0, last_depth = 0, last_color[3] = {0, 0, 0}, last_feature[64];
+        for (int i = 0; i < S; i++) last_feature[i] = 0;
+        double w_T = w_all, w_A = 0, last_eA = 0;
+        double bg_abs = 0;
+        for (int i = 0; i < 3; i++) bg_abs += fabs((double)bg_color[i] * dL_dpixel[i]);
+        for (uint32_t kk = r1; kk > r0; kk--) {
+            const uint32_t g = point_list[kk - 1];
+            contributor--;
+            if (contributor >= last_contributor) continue;
+            float dx = means2D[2 * g] - pixf[0], dy = means2D[2 * g + 1] - pixf[1];
+            const float* con_o = conic_opacity + 4 * g;
+            const float power = -0.5f * (con_o[0] * dx * dx + con_o[2] * dy * dy) - con_o[1] * dx * dy;
+            if (power > 0.0f) continue;
+            const float G0 = expf(power);
+            if (fminf(0.99f, con_o[3] * G0) < 1.0f / 255.0f) continue;
+            const double pabs = 0.5 * (fabs((double)con_o[0] * dx * dx) + fabs((double)con_o[2] * dy * dy)) +
+                                fabs((double)con_o[1] * dx * dy);
+            const double eG = 2.0 + 6.0 * pabs;
+            float G = G0;
+            if (perturb > 0) G = (float)((double)G0 * (1.0 + perturb * eG * U * r3dgo_unit(seed, (uint32_t)pix_id, kk, 1)));
+            const float alpha = fminf(0.99f, con_o[3] * G);
+            const double eA = (con_o[3] * G0 >= 0.99f) ? 0.0 : eG + 1.0;
+            const double amp = (double)alpha / (1.0 - (double)alpha);
+            T = T / (1.f - alpha);
+            if (perturb > 0) T = (float)((double)T * (1.0 + 2.0 * perturb * U * r3dgo_unit(seed, (uint32_t)pix_id, kk, 2)));
+            w_T += 2.0 + eA * amp;
+            w_A += 3.0 + last_eA;
+            const float dchannel_dcolor = alpha * T;
+            const double w_ch = w_T + eA + 2.0;
+            float dL_dalpha = 0.0f;
+            double pa = 0;
+            if (touched && !touched[g]) {
+                touched[g] = 1;
+                tlist[ntouched++] = g;
+            }
+#define R3DGO_STEP(acc_, abs_, lastv_, slot_)                                                                          \
+    do {                                                                                                               \
+        acc_ = last_alpha * (lastv_) + (1.f - last_alpha) * acc_;                                                      \
+        if (perturb > 0) acc_ = (float)((double)acc_ * (1.0 + 3.0 * perturb * U * r3dgo_unit(seed, (uint32_t)pix_id, kk, 8 + (slot_)))); \
+        abs_ = (double)last_alpha * fabs((double)(lastv_)) + (1.0 - (double)last_alpha) * abs_;                        \
+    } while (0)
+            for (int ch = 0; ch < 3; ch++) {
+                const float c = colors[g * 3 + ch];
+                R3DGO_STEP(accum_rec[ch], abs_rec[ch], last_color[ch], ch);
+                last_color[ch] = c;
+                const float dL_dchannel = dL_dpixel[ch];
+                dL_dalpha += (c - accum_rec[ch]) * dL_dchannel;
+                pa += (fabs((double)c) + abs_rec[ch]) * fabs((double)dL_dchannel);
+                const float t = dchannel_dcolor * dL_dchannel;
+                R3DGO_ADD(g, 8 + ch, t);
+                E[(size_t)g * NC + 8 + ch] += w_ch * fabs((double)t);
+            }
+            for (int ch = 0; ch < S; ch++) {
+                const float f = features[(size_t)g * S + ch];
+                R3DGO_STEP(accum_rec_f[ch], abs_rec_f[ch], last_feature[ch], 3 + ch);
+                last_feature[ch] = f;
+                const float dL_dchannel_f = dL_dpixel_f[ch];
+                if (backward_geometry) {
+                    dL_dalpha += (f - accum_rec_f[ch]) * dL_dchannel_f;
+                    pa += (fabs((double)f) + abs_rec_f[ch]) * fabs((double)dL_dchannel_f);
+                }
+                const float t = dchannel_dcolor * dL_dchannel_f;
+                R3DGO_ADD(g, 11 + ch, t);
+                E[(size_t)g * NC + 11 + ch] += w_ch * fabs((double)t);
+            }
+            const float depth = depths[g];
+            R3DGO_STEP(accum_rec_d, abs_rec_d, last_depth, 70);
+            last_depth = depth;
+            dL_dalpha += (depth - accum_rec_d) * dL_dpixel_d;
+            pa += (fabs((double)depth) + abs_rec_d) * fabs((double)dL_dpixel_d);
+            accum_rec_o = last_alpha + (1.f - last_alpha) * accum_rec_o;
+            if (perturb > 0) accum_rec_o = (float)((double)accum_rec_o * (1.0 + 3.0 * perturb * U * r3dgo_unit(seed, (uint32_t)pix_id, kk, 79)));
+            abs_rec_o = (double)last_alpha + (1.0 - (double)last_alpha) * abs_rec_o;
+            dL_dalpha += (1.0f - accum_rec_o) * dL_dpixel_o;
+            pa += (1.0 + abs_rec_o) * fabs((double)dL_dpixel_o);
+            dL_dalpha *= T;
+            last_alpha = alpha;
+            last_eA = eA * (1.0 + amp);
+            float bg_dot_dpixel = 0;
+            for (int i = 0; i < 3; i++) bg_dot_dpixel += bg_color[i] * dL_dpixel[i];
+            dL_dalpha += (-T_final / (1.f - alpha)) * bg_dot_dpixel;
+            const double A1 = (double)T * pa, A2 = (double)T_final / (1.0 - (double)alpha) * bg_abs;
+            const double w1 = w_A + w_T + NCH + 4.0, w2 = w_all + eA * amp + 7.0;
+            const double dabs = A1 + A2, dw = w1 * A1 + w2 * A2;
+            const float dL_dG = con_o[3] * dL_dalpha;
+            const float gdx = G * dx, gdy = G * dy;
+            const float dG_ddelx = -gdx * con_o[0] - gdy * con_o[1];
+            const float dG_ddely = -gdy * con_o[2] - gdx * con_o[1];
+            const double mabs = (double)G * fabs((double)con_o[3]);      /* |m|_abs = mabs * dabs */
+            const double wm = dw + (eG + 7.0) * dabs, wc = dw + (eG + 6.0) * dabs;
+            const double adx = fabs((double)dx), ady = fabs((double)dy);
+            const double cA = fabs((double)con_o[0]), cB = fabs((double)con_o[1]), cC = fabs((double)con_o[2]);
+            R3DGO_ADD(g, 0, dL_dG * dG_ddelx * ddelx_dx);
+            R3DGO_ADD(g, 1, dL_dG * dG_ddely * ddely_dy);
+            const float tz = dL_dpixel_d * dchannel_dcolor;
+            R3DGO_ADD(g, 2, tz);
+            E[(size_t)g * NC + 0] += (double)ddelx_dx * mabs * (cA * adx + cB * ady) * wm;
+            E[(size_t)g * NC + 1] += (double)ddely_dy * mabs * (cC * ady + cB * adx) * wm;
+            E[(size_t)g * NC + 2] += w_ch * fabs((double)tz);
+            Epix[(size_t)g * 2 + 0] += (double)ddelx_dx * mabs * fabs((double)con_o[0] * dx + (double)con_o[1] * dy) * wm;
+            Epix[(size_t)g * 2 + 1] += (double)ddely_dy * mabs * fabs((double)con_o[2] * dy + (double)con_o[1] * dx) * wm;
+            R3DGO_ADD(g, 3, -0.5f * gdx * dx * dL_dG);
+            R3DGO_ADD(g, 4, -0.5f * gdx * dy * dL_dG);
+            R3DGO_ADD(g, 6, -0.5f * gdy * dy * dL_dG);
+            E[(size_t)g * NC + 3] += 0.5 * mabs * adx * adx * wc;
+            E[(size_t)g * NC + 4] += 0.5 * mabs * adx * ady * wc;
+            E[(size_t)g * NC + 6] += 0.5 * mabs * ady * ady * wc;
+            R3DGO_ADD(g, 7, G * dL_dalpha);
+            E[(size_t)g * NC + 7] += (double)G * (dw + (eG + 1.0) * dabs);
+            count[g] += 1;
+        }
+#undef R3DGO_STEP
+    }
+#undef R3DGO_ADD
+    if (sum_mode == 3)
+        for (size_t q = 0; q < ntouched; q++)
+            for (int c = 0; c < NC; c++) facc[(size_t)tlist[q] * NC + c] += fblk[(size_t)tlist[q] * NC + c];
+    if (sum_mode)
+        for (size_t i = 0; i < (size_t)P * NC; i++) sums[i] = (double)facc[i];
+    free(facc); free(fblk); free(touched); free(tlist); free(order); free(blk_of);
+}
+
 /* reference backward.cu:144-276 (computeCov2DCUDA). Inputs/outputs are float like the reference's. */
 void r3dgo_cov2d_backward(int P, const float* means, const int32_t* radii, const float* cov3Ds, float h_x,
                           float h_y, float tan_fovx, float tan_fovy, const float* view_matrix,

@@ -66,6 +66,28 @@ def rasterize_forward(bg, means3D, features, colors, opacity, scales, rotations,
     return out
 
 
+def decode_geometry(fwd, P):
+    """The reference forward's per-Gaussian state (GeometryState, rasterizer_impl.cu:153-171: consecutive arrays, each start
+    rounded up to 128 bytes) as CPU numpy arrays: depths [P], means2D [P,2], conic_opacity [P,4], rgb [P,3] -- what its tile
+    passes read."""
+    import numpy as np
+    buf = fwd["buffers"][0]
+    base = buf.data_ptr()
+    addr = base
+    offs = {}
+    for name, nbytes in (("depths", 4 * P), ("clamped", 3 * P), ("radii", 4 * P), ("means2D", 8 * P), ("cov3D", 24 * P),
+                         ("cov3DInverse", 24 * P), ("conic_opacity", 16 * P), ("rgb", 12 * P)):
+        addr = (addr + 127) & ~127
+        offs[name] = addr - base
+        addr += nbytes
+    host = buf.cpu().numpy()
+
+    def view(name, n, shape):
+        return np.ascontiguousarray(host[offs[name]:offs[name] + 4 * n].view(np.float32).reshape(shape))
+    return dict(depths=view("depths", P, (P,)), means2D=view("means2D", 2 * P, (P, 2)),
+                conic_opacity=view("conic_opacity", 4 * P, (P, 4)), rgb=view("rgb", 3 * P, (P, 3)))
+
+
 def rasterize_backward(fwd, bg, means3D, features, colors, scales, rotations, scale_modifier, cov3D, viewmatrix,
                        projmatrix, tan_fovx, tan_fovy, gC, gO, gD, gF, sh, degree, campos, backward_geometry=True):
     dev = means3D.device

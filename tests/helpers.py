@@ -30,16 +30,66 @@ def report(name, got, ref, rtol, atol):
     return not bad.any(), msg
 
 
+U32 = 2.0 ** -24          # one fp32 rounding (half an ulp, relative)
+
+# The constants in front of the two element bounds (tests/test_gradient_bounds_cpu.py measures both and asserts that they
+# are 4 x its measured maxima, rounded up):
+#   tile pass:            |err| <= TILE_BOUND_C * 2^-24 * E      (E: oracle.rasterizer ... want_bounds)
+#   per-Gaussian stage:   |err| <= STAGE_BOUND_C * sigma          (sigma: oracle.rasterizer.per_gaussian_sigma)
+TILE_BOUND_C = 4.0
+STAGE_BOUND_C = 8300.0
+
+
+def report_elementwise(name, got, ref, bound):
+    """Returns (ok, message): every element within ITS OWN bound, |got - ref| <= bound (an array of ref's shape), and finite.
+    The message names the largest err / bound, where it occurs, and the median ratio (over elements with a non-zero bound;
+    an element whose bound is zero has to be exact)."""
+    got = to_np(got).astype(np.float64)
+    ref = to_np(ref).astype(np.float64)
+    bound = np.broadcast_to(np.asarray(bound, np.float64), ref.shape)
+    assert got.shape == ref.shape, "%s: shape %s vs %s" % (name, got.shape, ref.shape)
+    if ref.size == 0:
+        return True, "%s: empty" % name
+    finite = np.isfinite(got).all()
+    err = np.abs(np.where(np.isfinite(got), got, 0.0) - ref)
+    bad = err > bound
+    nz = bound > 0
+    ratio = np.zeros_like(err)
+    ratio[nz] = err[nz] / bound[nz]
+    ratio[~nz & (err > 0)] = np.inf
+    at = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+    msg = "%-14s max err/bound %.3e at %s (err %.3e, ref %.3e)  median %.2e  bad %d/%d  zero-bound elements %d" % (
+        name, ratio[at], tuple(int(i) for i in at), err[at], ref[at], float(np.median(ratio[nz])) if nz.any() else 0.0,
+        bad.sum(), ref.size, (~nz).sum())
+    if not finite:
+        return False, msg + "  NON-FINITE values in result"
+    return not bad.any(), msg
+
+
 def make_case(P=3000, W=128, H=128, S=5, seed=1, scale_log_mean=-3.0, eye=(3.2, 1.0, 1.5), use_colors=False,
-              use_cov=False, bg=(1.0, 0.5, 0.2), sh_degree=3):
-    """A seeded scene + camera + feature block; everything as CPU fp32 torch tensors (dict)."""
+              use_cov=False, bg=(1.0, 0.5, 0.2), sh_degree=3, scale_modifier=1.0, sh_shift=0.0, fovy_scale=1.0,
+              principal_point=None):
+    """A seeded scene + camera + feature block; everything as CPU fp32 torch tensors (dict).
+    `sh_shift` is added to every DC coefficient (negative: more colour channels clamp); `fovy_scale` multiplies tan(fovy/2)
+    (focal_x != focal_y); `principal_point` = (cx / W, cy / H) moves the principal point off the centre."""
     sc = syn.make_scene(P=P, seed=seed, scale_log_mean=scale_log_mean)
     cam = syn.look_at_camera(eye, width=W, height=H)
+    if fovy_scale != 1.0:
+        import math
+        fovy = 2 * math.atan(cam.tanfovy * fovy_scale)
+        proj = syn._projection(0.01, 100.0, cam.FoVx, fovy).transpose(0, 1)
+        full = (cam.world_view_transform.unsqueeze(0).bmm(proj.unsqueeze(0))).squeeze(0).contiguous()
+        cam = cam._replace(FoVy=fovy, tanfovy=math.tan(fovy * 0.5), full_proj_transform=full)
+    if principal_point is not None:
+        cam = cam._replace(cx=principal_point[0] * W, cy=principal_point[1] * H)
+    if sh_shift != 0.0:
+        sc["shs"] = sc["shs"].clone()
+        sc["shs"][:, 0] += sh_shift
     g = torch.Generator().manual_seed(seed + 100)
     feat = torch.rand(P, S, generator=g) if S > 0 else torch.zeros(P, 0)
     case = dict(P=P, W=W, H=H, S=S, bg=torch.tensor(bg, dtype=torch.float32), means3D=sc["xyz"], features=feat,
                 opacity=sc["opacity"], scales=sc["scales"], rotations=sc["rotations"], shs=sc["shs"],
-                degree=sh_degree, cam=cam, colors=None, cov3D=None)
+                degree=sh_degree, cam=cam, colors=None, cov3D=None, scale_modifier=scale_modifier)
     if use_colors:
         case["colors"] = torch.rand(P, 3, generator=g)
         case["shs"] = None
@@ -72,6 +122,66 @@ def fwd_args(case, device=None, debug=False):
             return empty
         return t.to(device) if device is not None else t
     return (dv(case["bg"]), dv(case["means3D"]), dv(case["features"]), dv(case["colors"]), dv(case["opacity"]),
-            dv(case["scales"]), dv(case["rotations"]), 1.0, dv(case["cov3D"]), dv(cam.world_view_transform),
+            dv(case["scales"]), dv(case["rotations"]), case.get("scale_modifier", 1.0), dv(case["cov3D"]),
+            dv(cam.world_view_transform),
             dv(cam.full_proj_transform), cam.tanfovx, cam.tanfovy, cam.cx, cam.cy, case["H"], case["W"],
             dv(case["shs"]), case["degree"], dv(cam.camera_center), False, True, debug)
+
+
+# ---- the element-wise gradient bounds (tests/test_gradient_bounds_cpu.py, tests/test_rasterizer_gpu.py) ----------------------
+# Cases added for the element-wise checks: what the parity cases above leave out of the argument space.
+ELEMENTWISE_CASES = {
+    "scale_mod_0.6": dict(S=5, seed=41, scale_modifier=0.6),
+    "scale_mod_1.7": dict(S=5, seed=42, scale_modifier=1.7),
+    "scale_mod_1.7_cov": dict(S=4, seed=43, use_cov=True, scale_modifier=1.7),
+    "sh_degree_0": dict(S=3, seed=44, sh_degree=0),
+    "sh_degree_1": dict(S=3, seed=45, sh_degree=1),
+    "sh_degree_2": dict(S=3, seed=46, sh_degree=2),
+    "camera_inside": dict(S=5, seed=47, eye=(0.2, 0.1, 0.0)),
+    "black_bg": dict(S=5, seed=48, bg=(0.0, 0.0, 0.0)),
+    "sh_negative": dict(S=5, seed=49, sh_shift=-1.2),
+    "aniso_fov_ragged": dict(S=5, seed=50, W=200, H=120, fovy_scale=1.3),
+    "deep_list": dict(S=5, seed=51, P=4000, scale_log_mean=-2.5, W=48, H=40),
+}
+# The backward parity cases of tests/test_rasterizer_gpu.py (test_backward_parity, test_backward_no_geometry_flag)
+BWD_CASES = {
+    "S5": dict(S=5),
+    "S0": dict(S=0, seed=21),
+    "S16": dict(S=16, seed=22),
+    "S24": dict(S=24, seed=23, P=1500),
+    "S33": dict(S=33, seed=24, P=1000),
+    "colors_precomp": dict(S=3, use_colors=True, seed=25),
+    "cov_precomp": dict(S=4, use_cov=True, seed=26),
+    "ragged_image": dict(S=5, W=200, H=120, seed=27),
+    "big_splats": dict(S=5, scale_log_mean=-1.5, P=800, seed=28),
+}
+NO_GEOMETRY_CASE = dict(S=5, seed=31)
+TILE_ARRAYS = ("mean2D", "conic", "opacity", "colors", "feature")
+STAGE_ARRAYS = ("means3D", "cov3D", "sh", "scales", "rot")
+
+
+def upstream(case, seed=123):
+    """Seeded upstream gradients (colour, opacity, depth, feature) of a case, CPU fp32."""
+    H, W, S = case["H"], case["W"], case["S"]
+    g = torch.Generator().manual_seed(seed)
+    gC, gO, gD = torch.randn(3, H, W, generator=g), torch.randn(1, H, W, generator=g), torch.randn(1, H, W, generator=g)
+    return gC, gO, gD, torch.randn(S, H, W, generator=g)
+
+
+def oracle_backward(case, fwd_ref, ups, backward_geometry=True, **kw):
+    """oracle.rasterizer.rasterize_gaussians_backward of a case on the oracle forward `fwd_ref` (keyword arguments passed on)."""
+    from oracle import rasterizer as orc
+    c = fwd_args(case)
+    return orc.rasterize_gaussians_backward(c[0], c[1], c[2], fwd_ref[9], c[3], c[5], c[6], c[7], c[8], c[9], c[10], c[11],
+                                            c[12], ups[0], ups[1], ups[2], ups[3], c[17], c[18], c[19], fwd_ref[-1],
+                                            backward_geometry, **kw)
+
+
+def stage_args(case, fwd_ref, d_mean2D, d_conic, d_colors):
+    """Arguments of oracle.rasterizer.per_gaussian_backward_f64 / per_gaussian_sigma for a case and given tile-pass sums (the
+    sums as the per-Gaussian kernel sees them: fp32)."""
+    c = fwd_args(case)
+    st = fwd_ref[-1]
+    f32 = lambda a: to_np(a).astype(np.float32)
+    return (c[1], c[5], c[6], c[7], c[8], c[17], c[18], c[9], c[10], c[11], c[12], c[19], case["W"], case["H"], fwd_ref[9],
+            st["clamped"], f32(d_mean2D).reshape(-1, 3), f32(d_conic).reshape(-1, 4), f32(d_colors).reshape(-1, 3))

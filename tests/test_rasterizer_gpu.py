@@ -6,12 +6,18 @@ Tolerances (stated per buffer):
     last ulps of exp(); the oracle reports the margin per pixel)
   * forward float buffers: |err| <= 1e-5 + 2e-5*max|ref|;  weights (float atomics): 1e-4 relative
   * gradients (float atomics vs double-accumulated oracle): |err| <= 1e-6 + 2e-3*max|ref|
+  * AND every gradient element within its own rounding scale (tests/test_gradient_bounds_cpu.py):
+    the five tile-pass arrays |err| <= TILE_BOUND_C 2^-24 E against the oracle (E: the oracle's weighted absolute sum of the
+    element's terms), the five per-Gaussian arrays |err| <= STAGE_BOUND_C sigma against the float64 chain evaluated on the
+    kernel's OWN tile-pass sums (sigma: that chain's input conditioning).  No element of a visible Gaussian is exempt; a zero
+    bound (invisible Gaussians, coefficients above the SH degree, inactive feature columns) means exactly zero.
 """
 import numpy as np
 import pytest
 import torch
 
-from tests.helpers import fwd_args, make_case, report, to_np
+from tests.helpers import (BWD_CASES, ELEMENTWISE_CASES, NO_GEOMETRY_CASE, STAGE_BOUND_C, TILE_BOUND_C, U32, fwd_args,
+                           make_case, report, report_elementwise, stage_args, to_np)
 
 pytestmark = pytest.mark.gpu
 
@@ -182,6 +188,49 @@ def test_forward_bad_shape_raises():
         _C.rasterize_gaussians(*fwd_args(case, DEV))
 
 
+def _accumulators(case):
+    """The slab rasterize_gaussians_backward accumulates into (`zeroed_accumulators`): handing it in keeps dL_dconic -- since
+    round 5 the raw second moments of the tile pass -- readable after the call."""
+    return torch.empty((11 + case["S"]) * case["P"], dtype=torch.float32, device=DEV)
+
+
+def _conic_of(acc, case):
+    """The op's dL_dconic [P,4] from the slab: -1/2 x the raw moments (S_xx, S_xy, -, S_yy) the tile pass left there."""
+    P, S = case["P"], case["S"]
+    return -0.5 * acc[S * P:S * P + 4 * P].view(P, 4)
+
+
+def _elementwise(label, case, ref, grads, conic, oref, tile_only=None):
+    """Every element of the nine gradient arrays (and dL_dconic) within its own bound; returns (ok, messages).
+    `oref`: the oracle's backward with want_bounds=True on the same upstream gradients; `grads`: the op's 9-tuple (entries may
+    be None: not produced by the entry point under test); `conic`: the op's dL_dconic or None."""
+    from oracle import rasterizer as orc
+    bounds = oref[-1]
+    msgs, ok_all = [], True
+    tile = (("mean2D", grads[0], oref[0]), ("colors", grads[1], oref[1]), ("opacity", grads[2], oref[2]),
+            ("feature", grads[4], oref[4]), ("conic", conic, oref[9]))
+    for key, got, want in tile:
+        if got is None or (tile_only is not None and key not in tile_only):
+            continue
+        ok, m = report_elementwise("tile/" + key, got, np.asarray(want).reshape(tuple(got.shape)),
+                                   TILE_BOUND_C * U32 * bounds["E"][key].reshape(tuple(got.shape)))
+        msgs.append(m)
+        ok_all &= ok
+    e, ep = bounds["E"]["mean2D"][:, :2], bounds["E_pixel_form"]
+    msgs.append("dL_dmean2D absolute sum, moment form / pixel form: max %.1f, median %.2f" % (
+        float((e[ep > 0] / ep[ep > 0]).max()) if (ep > 0).any() else 0.0,
+        float(np.median(e[ep > 0] / ep[ep > 0])) if (ep > 0).any() else 0.0))
+    if tile_only is None and grads[3] is not None:
+        # the per-Gaussian stage on its own: float64 chain on the kernel's own sums
+        base, sigma = orc.per_gaussian_sigma(*stage_args(case, ref, grads[0], conic, grads[1]))
+        for key, got in (("means3D", grads[3]), ("cov3D", grads[5]), ("sh", grads[6]), ("scales", grads[7]), ("rot", grads[8])):
+            ok, m = report_elementwise("stage/" + key, got, base[key].reshape(tuple(got.shape)),
+                                       STAGE_BOUND_C * sigma[key].reshape(tuple(got.shape)))
+            msgs.append(m)
+            ok_all &= ok
+    return ok_all, ["[%s] element-wise" % label] + msgs
+
+
 def _check_backward(case, label, backward_geometry=True):
     from oracle import rasterizer as orc
     from r3dg_rasterization import _C
@@ -191,9 +240,11 @@ def _check_backward(case, label, backward_geometry=True):
     gC, gO, gD = torch.randn(3, H, W, generator=g), torch.randn(1, H, W, generator=g), torch.randn(1, H, W, generator=g)
     gF = torch.randn(S, H, W, generator=g)
     a = fwd_args(case, DEV)
-    grads = _C.rasterize_gaussians_backward(a[0], a[1], a[2], out[9], a[3], a[5], a[6], 1.0, a[8], a[9], a[10], a[11],
+    acc = _accumulators(case)
+    grads = _C.rasterize_gaussians_backward(a[0], a[1], a[2], out[9], a[3], a[5], a[6], a[7], a[8], a[9], a[10], a[11],
                                             a[12], gC.to(DEV), gO.to(DEV), gD.to(DEV), gF.to(DEV), a[17], a[18], a[19],
-                                            out[10], out[0], out[11], out[12], backward_geometry, False)
+                                            out[10], out[0], out[11], out[12], backward_geometry, False,
+                                            zeroed_accumulators=acc)
     torch.cuda.synchronize()
     c = fwd_args(case)
     # the oracle backward walks the ORACLE's forward state; borderline pixels (threshold margin < 1e-4) are zeroed in both
@@ -202,13 +253,14 @@ def _check_backward(case, label, backward_geometry=True):
     if not bool(nc_same.all()):
         mask = nc_same[None].float()
         gC, gO, gD, gF = gC * mask, gO * mask, gD * mask, gF * mask
-        grads = _C.rasterize_gaussians_backward(a[0], a[1], a[2], out[9], a[3], a[5], a[6], 1.0, a[8], a[9], a[10],
+        grads = _C.rasterize_gaussians_backward(a[0], a[1], a[2], out[9], a[3], a[5], a[6], a[7], a[8], a[9], a[10],
                                                 a[11], a[12], gC.to(DEV), gO.to(DEV), gD.to(DEV), gF.to(DEV), a[17],
                                                 a[18], a[19], out[10], out[0], out[11], out[12], backward_geometry,
-                                                False)
+                                                False, zeroed_accumulators=acc)
         torch.cuda.synchronize()
-    oref = orc.rasterize_gaussians_backward(c[0], c[1], c[2], ref[9], c[3], c[5], c[6], 1.0, c[8], c[9], c[10], c[11],
-                                            c[12], gC, gO, gD, gF, c[17], c[18], c[19], ref[-1], backward_geometry)
+    oref = orc.rasterize_gaussians_backward(c[0], c[1], c[2], ref[9], c[3], c[5], c[6], c[7], c[8], c[9], c[10], c[11],
+                                            c[12], gC, gO, gD, gF, c[17], c[18], c[19], ref[-1], backward_geometry,
+                                            want_bounds=True)
     names = ["dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dfeatures", "dL_dcov3D", "dL_dsh",
              "dL_dscales", "dL_drotations"]
     msgs, ok_all = [], True
@@ -216,22 +268,13 @@ def _check_backward(case, label, backward_geometry=True):
         ok, m = report(name, got, np.asarray(want).reshape(tuple(got.shape)), 2e-3, 1e-6)
         msgs.append(m)
         ok_all &= ok
-    text = "\n".join(["[%s] backward" % label] + msgs)
+    # ... and every element within its own bound
+    ok_el, m_el = _elementwise(label, case, ref, grads, _conic_of(acc, case), oref)
+    text = "\n".join(["[%s] backward" % label] + msgs + m_el)
     print(text)
     assert ok_all, text
-
-
-BWD_CASES = {
-    "S5": dict(S=5),
-    "S0": dict(S=0, seed=21),
-    "S16": dict(S=16, seed=22),
-    "S24": dict(S=24, seed=23, P=1500),
-    "S33": dict(S=33, seed=24, P=1000),
-    "colors_precomp": dict(S=3, use_colors=True, seed=25),
-    "cov_precomp": dict(S=4, use_cov=True, seed=26),
-    "ragged_image": dict(S=5, W=200, H=120, seed=27),
-    "big_splats": dict(S=5, scale_log_mean=-1.5, P=800, seed=28),
-}
+    assert ok_el, text
+    return grads, oref, ref
 
 
 @pytest.mark.parametrize("name", list(BWD_CASES))
@@ -240,7 +283,118 @@ def test_backward_parity(name):
 
 
 def test_backward_no_geometry_flag():
-    _check_backward(make_case(S=5, seed=31), "bg_geom_off", backward_geometry=False)
+    _check_backward(make_case(**NO_GEOMETRY_CASE), "bg_geom_off", backward_geometry=False)
+
+
+@pytest.mark.parametrize("name", list(ELEMENTWISE_CASES))
+def test_backward_parity_rest_of_the_argument_space(name):
+    """scale_modifier != 1 (with scales + rotations, and with a precomputed cov3D, which it must not touch), SH degrees 0-2
+    (coefficient gradients above the degree exactly zero), the camera inside the scene (the +-1.3 tan_fov clamp with
+    x/y_grad_mul = 0), a black background, an SH set whose colours mostly clamp, focal_x != focal_y on a ragged image, and
+    tile lists of up to 2 000 entries on 12 tiles -- forward parity first, then the backward as in test_backward_parity."""
+    case = make_case(**ELEMENTWISE_CASES[name])
+    grads, _, _ = _check_backward(case, name)
+    if case["cov3D"] is not None and case["scale_modifier"] != 1.0:
+        a, b = _run_forward(case), _run_forward(dict(case, scale_modifier=1.0))
+        torch.cuda.synchronize()
+        for i in (1, 2, 3, 4, 5, 9):
+            assert torch.equal(a[i], b[i]), "scale_modifier changed output %d of a precomputed covariance" % i
+    M_live = (case["degree"] + 1) ** 2
+    if M_live < 16:
+        assert float(grads[6][:, M_live:].abs().max()) == 0.0
+        assert float(grads[6][:, :M_live].abs().max()) > 0.0
+
+
+def test_forward_off_centre_principal_point():
+    """cx = 0.37 W, cy = 0.61 H: only surface_xyz and the pseudo normal read the principal point."""
+    kw = dict(S=5, seed=52)
+    out, _ = _check_forward(make_case(principal_point=(0.37, 0.61), **kw), "principal_point")
+    centred = _run_forward(make_case(**kw))
+    torch.cuda.synchronize()
+    for i in (1, 2, 3, 4, 5):
+        assert torch.equal(out[i], centred[i]), i
+    assert not torch.equal(out[7], centred[7]) and not torch.equal(out[6], centred[6])
+
+
+VARIANT_CASES = {"S5_128": dict(S=5, seed=53), "deep_list": ELEMENTWISE_CASES["deep_list"]}
+_variant_cache = {}
+
+
+def _variant_setup(name):
+    """Forward of both sides, the agreeing-pixel mask and masked upstream gradients of a variant case (computed once)."""
+    if name not in _variant_cache:
+        case = make_case(**VARIANT_CASES[name])
+        out, ref = _run_forward(case), _oracle_forward(case)
+        torch.cuda.synchronize()
+        H, W, S = case["H"], case["W"], case["S"]
+        g = torch.Generator().manual_seed(321)
+        mask = torch.from_numpy((to_np(out[1]) == ref[1]) & ~(ref[-1]["margin"] < 1e-4))[None].float()
+        ups = [torch.randn(n, H, W, generator=g) * mask for n in (3, 1, 1, S)]
+        _variant_cache[name] = (case, out, ref, ups)
+    return _variant_cache[name]
+
+
+def _oracle_variant(case, ref, ups):
+    from oracle import rasterizer as orc
+    c = fwd_args(case)
+    return orc.rasterize_gaussians_backward(c[0], c[1], c[2], ref[9], c[3], c[5], c[6], c[7], c[8], c[9], c[10], c[11], c[12],
+                                            ups[0], ups[1], ups[2], ups[3], c[17], c[18], c[19], ref[-1], True,
+                                            want_bounds=True)
+
+
+@pytest.mark.parametrize("name", list(VARIANT_CASES))
+@pytest.mark.parametrize("variant", ["split_active_subset", "lean", "lean_off", "features_only", "bounded_forward"])
+def test_variant_entry_points_against_the_oracle_elementwise(name, variant):
+    """Every other way into the tile backward -- r3dg_rasterize_backward_split with an active feature subset, the lean
+    instances (no depth gradient) with BWD_LEAN on and off, r3dg_rasterize_backward_features, and the backward behind
+    r3dg_rasterize_forward_begin_bounded -- against the ORACLE (not against each other) under the element-wise bounds."""
+    from relightable3dgaussian_amd import _lib, rasterizer_ops as ro
+    case, out, ref, ups = _variant_setup(name)
+    H, W, S, P = case["H"], case["W"], case["S"], case["P"]
+    a = fwd_args(case, DEV)
+    gC, gO, gD, gF = [u.clone() for u in ups]
+    active = None
+    if variant in ("split_active_subset", "lean", "lean_off"):
+        active = (0, 2, 3)
+        keep = torch.zeros(S, 1, 1)
+        keep[list(active)] = 1.0
+        gF = gF * keep
+    no_depth = variant in ("lean", "lean_off")
+    if no_depth:
+        gD = torch.zeros_like(gD)
+    oref = _oracle_variant(case, ref, (gC, gO, gD, gF))
+    dev = [t.to(DEV) for t in (gC, gO, gD, gF)]
+    label = "%s/%s" % (name, variant)
+    if variant == "features_only":
+        only = ro.rasterize_gaussians_backward_features(P, S, H, W, dev[3], out[10], out[0], out[11], out[12])
+        torch.cuda.synchronize()
+        ok, msgs = _elementwise(label, case, ref, (None, None, None, None, only, None, None, None, None), None, oref,
+                                tile_only=("feature",))
+    else:
+        state, R = out, out[0]
+        if variant == "bounded_forward":
+            R = out[0] + 1000
+            state = ro.rasterize_gaussians_begin(*fwd_args(case, DEV, False), capacity=R).finish()
+        acc = _accumulators(case)
+        try:
+            if variant == "lean_off":
+                _lib.set_option("BWD_LEAN", 0)
+            grads = ro.rasterize_gaussians_backward(
+                a[0], a[1], a[2], state[9], a[3], a[5], a[6], a[7], a[8], a[9], a[10], a[11], a[12], dev[0], dev[1],
+                torch.Tensor([]) if no_depth else dev[2], dev[3], a[17], a[18], a[19], state[10], R, state[11], state[12],
+                True, False, active_features=active, zeroed_accumulators=acc)
+            torch.cuda.synchronize()
+        finally:
+            _lib.set_option("BWD_LEAN", 1)
+        ok, msgs = _elementwise(label, case, ref, grads, _conic_of(acc, case), oref)
+        if no_depth:
+            assert float(grads[0][:, 2].abs().max()) == 0.0
+        if active is not None:
+            inactive = [ch for ch in range(S) if ch not in active]
+            assert float(grads[4][:, inactive].abs().max()) == 0.0
+    text = "\n".join(msgs)
+    print(text)
+    assert ok, text
 
 
 @pytest.mark.parametrize("order", [0, 1])

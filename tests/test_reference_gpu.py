@@ -35,7 +35,7 @@ def _ok(name, got, ref, rtol, atol, msgs):
                                      ("colors_cov_S3", dict(S=3, P=8000, W=200, H=120, seed=73, use_colors=True, use_cov=True)),
                                      ("S0", dict(S=0, P=5000, W=128, H=128, seed=74))])
 def test_rasterizer_matches_real_reference(name, kw):
-    _compare_rasterizer(name, make_case(**kw), backward=True)
+    _compare_rasterizer(name, make_case(**kw), backward=True, element_bounds=True)
 
 
 # The BASELINE configurations themselves (BASELINE.json configs / SURVEY 8d), against forward.cu:263-395 and
@@ -85,7 +85,43 @@ def test_rasterizer_matches_real_reference_at_baseline_sizes(name, kw, backward)
     _compare_rasterizer(name, case, backward=backward)
 
 
-def _compare_rasterizer(name, case, backward=True, margin_floor=1e-4):
+def _reference_through_the_tile_bound(case, ref, gr, go, o_ref, ups, rows, msgs):
+    """The reference's OWN compiled tile backward through the element-wise tile-pass bound (tests/test_gradient_bounds_cpu.py)
+    on the five arrays it exposes: the oracle walks the reference's own forward state (its means2D / conic / colours / final_T /
+    n_contrib / lists), so only the tile pass is compared.  Evidence that the bound accepts the reference itself; returns
+    whether every element is inside (largest err / bound <= 1).  Our kernels' ratio on the same upstream gradients (oracle on
+    the oracle's state, as in tests/test_rasterizer_gpu.py) is printed next to it."""
+    from oracle import rasterizer as orc
+    from tests.helpers import TILE_BOUND_C, U32, report_elementwise
+    rg = _need_ref()
+    P, S = case["P"], case["S"]
+    c = fwd_args(case)
+    st = dict(o_ref[-1])
+    st.update(rg.decode_geometry(ref, P))
+    R = int(ref["num_rendered"])
+    st.update(final_T=ref["final_T"].cpu().numpy(), n_contrib=ref["n_contrib"].cpu().numpy().astype(np.uint32),
+              ranges=ref["ranges"].cpu().numpy().astype(np.uint32),
+              point_list=ref["point_list"][:max(R, 1)].cpu().numpy().astype(np.uint32))
+    colors = c[3] if c[3].numel() else None
+    ok = True
+    for tag, state, res in (("reference", st, (gr["mean2D"], gr["color"], gr["opacity"], gr["feature"], gr["conic"])),
+                            ("ours", o_ref[-1], (go[0], go[1], go[2], go[4], None))):
+        ob = orc.rasterize_gaussians_backward(c[0], c[1], c[2], o_ref[9], colors, c[5], c[6], c[7], c[8], c[9], c[10], c[11],
+                                              c[12], ups[0], ups[1], ups[2], ups[3], c[17], c[18], c[19], state, True,
+                                              want_bounds=True)
+        for key, got, want in zip(("mean2D", "colors", "opacity", "feature", "conic"), res, (ob[0], ob[1], ob[2], ob[4], ob[9])):
+            if got is None or want.size == 0:
+                continue
+            g_ = got.cpu().numpy().astype(np.float64).reshape(P, -1)[rows]
+            good, m = report_elementwise("%s tile/%s" % (tag, key), g_, want.reshape(P, -1)[rows],
+                                         TILE_BOUND_C * U32 * ob[-1]["E"][key].reshape(P, -1)[rows])
+            msgs.append(m)
+            if tag == "reference":
+                ok &= good
+    return ok
+
+
+def _compare_rasterizer(name, case, backward=True, margin_floor=1e-4, element_bounds=False):
     rg = _need_ref()
     from r3dg_rasterization import _C
     from relightable3dgaussian_amd.rasterizer_ops import decode_state
@@ -245,6 +281,8 @@ def _compare_rasterizer(name, case, backward=True, margin_floor=1e-4):
                     % (nm, np.abs(o_ - r_).max(), scale, bad.sum(), r_.size, rows.sum(), float(np.median(rel)), p999))
         ok &= not bad.any()
         ok &= p999 <= 1e-3
+    if element_bounds:
+        ok &= _reference_through_the_tile_bound(case, ref, gr, go, o_ref, [t.cpu() for t in (gC, gO, gD, gF)], r_o == r_r, msgs)
     text = "\n".join(["[real reference / %s] P=%d %dx%d S=%d" % (name, P, W, H, S)] + msgs)
     print(text)
     assert ok, text
