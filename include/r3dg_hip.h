@@ -861,6 +861,33 @@ int r3dg_bvh_prepare_leaves(void* stream, int P, const float* d_means3D, const f
 int r3dg_bvh_trace_bundles(void* stream, int num_gaussians, int K, void* d_records, const int32_t* d_nodes,
                            const float* d_zsamples, int leaf_lo, int leaf_hi, float origin_offset, float* d_visibility,
                            int32_t* d_num_contributes, float* d_dirs_out, int32_t* d_stack_overflow);
+
+/* Baking traced visibility into the per-Gaussian SH coefficients (visibility_bake.VisibilityBaker;
+ * GaussianModel.finetune_visibility, scene/gaussian_model.py:275-310, is what it restates -- with the prediction taken from the live
+ * coefficients, which the reference's loop reads from a copy made before it starts, :289).  T iterations are two launches:
+ * r3dg_bvh_trace_hemisphere: the trace of r3dg_bvh_trace_opacity_packed over the T random hemisphere rays of every Gaussian: for
+ *   every Morton leaf slot i in [leaf_lo, leaf_hi) (object id g) and every t < T the ray with direction d = z / max(|z|, 1e-12),
+ *   z = d_raw_dirs[t,g,:] (F.normalize of the caller's draw), negated when d . normal_g < 0 (strict; mean and normal of g are read
+ *   from d_records), and origin mean_g + d * origin_offset.  The transmittance goes to d_visibility[t*P + g], d to
+ *   d_dirs_out[(t*P + g)*3 ..], the hit count to d_num_contributes[t*P + g] (NULL: not wanted): iteration-major, what the fit reads
+ *   coalesced; rows of leaves outside [leaf_lo, leaf_hi) are untouched.  Each result is bit-identical to
+ *   r3dg_bvh_trace_opacity_packed given that origin and direction.  P * T must fit an int; one trace at a time per d_records;
+ *   P == 0, T == 0 or an empty range: nothing is launched.
+ * r3dg_visibility_sh_fit: T Adam steps of every Gaussian's 16 coefficients in one launch, one thread per Gaussian with the 48 state
+ *   values in registers.  Iteration t: Y = the degree-3 SH basis (utils/sh_utils.py:71-128) at d_dirs[t,g,:], x = sum c Y + 0.5,
+ *   vhat = clamp(x, 0, 1), gradient sign(vhat - v) [0 <= x <= 1] Y / P of mean |v - vhat| (sign(0) = 0, the clamp's mask inclusive
+ *   at both ends), then torch.optim.Adam's default single-tensor step number steps_done + t + 1 (bias corrections in double).
+ *   d_coeffs / d_exp_avg / d_exp_avg_sq [P,16] (16-byte aligned) are updated in place.  The same inputs give the same bits, and T
+ *   iterations split into several calls (steps_done advanced by the caller) give the bits of one call.  d_loss_partials (NULL: not
+ *   wanted), [r3dg_visibility_sh_fit_loss_rows(P), T]: per-workgroup sums of |v - vhat| per iteration; the loss of iteration t is
+ *   the sum of column t, added by the caller in a fixed order, divided by P (no float atomics). */
+int r3dg_bvh_trace_hemisphere(void* stream, int num_gaussians, int T, void* d_records, const int32_t* d_nodes,
+                              const float* d_raw_dirs, int leaf_lo, int leaf_hi, float origin_offset, float* d_visibility,
+                              float* d_dirs_out, int32_t* d_num_contributes, int32_t* d_stack_overflow);
+int r3dg_visibility_sh_fit(void* stream, int P, int T, int64_t steps_done, const float* d_dirs, const float* d_visibility,
+                           float lr, float beta1, float beta2, float eps, float* d_coeffs, float* d_exp_avg,
+                           float* d_exp_avg_sq, float* d_loss_partials);
+int r3dg_visibility_sh_fit_loss_rows(int P);
 /* Measurement ("report rays/s and node-visits/s"): with R3DG_OPT_TRACE_COUNT_VISITS = 1 the phased trace counts
  * its node steps (one slab test of both children of a node, trace.cu:228-246) and leaf steps (one Gaussian evaluated,
  * :247-276); r3dg_bvh_trace_visits synchronises `stream` and returns the two sums of the LAST trace over `d_records` in

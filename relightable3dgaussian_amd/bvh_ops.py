@@ -79,6 +79,38 @@ def trace_bundles(records, nodes, zsamples, visibility, leaf_lo=0, leaf_hi=None,
     return overflow
 
 
+def trace_hemisphere(records, nodes, raw_dirs, visibility, dirs_out, leaf_lo=0, leaf_hi=None, origin_offset=0.05, contributes=None):
+    """The visibility trace over T random hemisphere rays per Gaussian (r3dg_bvh_trace_hemisphere; one iteration of
+    GaussianModel.finetune_visibility per t): for the Morton leaf slots [leaf_lo, leaf_hi) of the tree `nodes` (`records` =
+    trace_records(...) of it) and every t < T = raw_dirs.shape[0] the ray of the slot's Gaussian g with direction
+    F.normalize(raw_dirs[t, g]), negated into the hemisphere of g's normal, and origin mean + direction * origin_offset -- written
+    IN PLACE to `visibility` [T,P], `dirs_out` [T,P,3] (float32) and `contributes` [T,P] (int32, optional), iteration-major.
+    Rows of other leaves are untouched.  -> the stack-overflow counter (int32[1], on the device)."""
+    L = _lib.lib()
+    P = (nodes.shape[0] + 1) // 2
+    dev = visibility.device
+    if raw_dirs.dim() != 3 or raw_dirs.shape[1:] != (P, 3):
+        raise RuntimeError("trace_hemisphere: raw_dirs must be [T,P,3] over the P Gaussians of the tree")
+    T = raw_dirs.shape[0]
+    leaf_hi = P if leaf_hi is None else leaf_hi
+    for name, t, dtype, n in (("raw_dirs", raw_dirs, torch.float32, 3 * P * T), ("visibility", visibility, torch.float32, P * T),
+                              ("dirs_out", dirs_out, torch.float32, 3 * P * T), ("contributes", contributes, torch.int32, P * T)):
+        if t is not None and (t.dtype != dtype or t.numel() != n or not t.is_contiguous() or not t.is_cuda):
+            raise RuntimeError("trace_hemisphere: %s must be a contiguous %s CUDA(HIP) tensor of %d elements" % (name, dtype, n))
+    if nodes.dtype != torch.int32 or not nodes.is_contiguous() or nodes.shape[1] != 5:
+        raise RuntimeError("trace_hemisphere: nodes must be the contiguous int32 [2P-1,5] table")
+    if records.numel() < int(L.r3dg_bvh_trace_records_bytes(P)):
+        raise RuntimeError("trace_hemisphere: records are not the packed records of this tree")
+    overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.r3dg_bvh_trace_hemisphere(_lib.current_stream(), P, T, records.data_ptr(), nodes.data_ptr(),
+                                               _lib.ptr(raw_dirs), int(leaf_lo), int(leaf_hi), float(origin_offset),
+                                               _lib.ptr(visibility), _lib.ptr(dirs_out), _lib.ptr(contributes),
+                                               overflow.data_ptr()), "trace_hemisphere")
+    trace_hemisphere.last_overflow = overflow
+    return overflow
+
+
 def trace_records(nodes, aabbs, means3D, covs3D, opacities, normals):
     """The tree and the per-Gaussian arrays packed into 64-byte traversal records (r3dg_bvh_pack_traversal), for
     trace_bvh_opacity(..., records=...): pack once, trace many ray chunks.  Valid while the six tensors are unchanged."""

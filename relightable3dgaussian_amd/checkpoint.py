@@ -72,8 +72,9 @@ def step_learning_rates(step):
 
 def capture(step, iteration, spatial_lr_scale=1.0, active_sh_degree=3, learning_rates=None):
     """-> the object train.py saves: `(GaussianModel.capture() list, iteration)`.  `step`: FusedStage1Step or
-    FusedStage2Step (stage 2 adds the six PBR entries; the baked-visibility SH groups this repo does not train are
-    written as zeros of the reference's shapes).  `learning_rates`: {group name: lr} for the param_groups -- torch's
+    FusedStage2Step (stage 2 adds the six PBR entries; the baked-visibility SH groups are the step's `visibility_dc` /
+    `visibility_rest` -- what visibility_bake.bake_visibility wrote, carried by the step, never trained by it -- and zeros of the
+    reference's shapes for a holder without them).  `learning_rates`: {group name: lr} for the param_groups -- torch's
     Optimizer.load_state_dict ADOPTS the saved groups' hyper-parameters, so a reference GaussianModel.restore(is_training=
     True) on this file trains with exactly these rates; the default is what the step itself trains with
     (step_learning_rates: the scheduled xyz rate, the stage-2 rates of the run script), and the reference's own training_setup
@@ -89,8 +90,10 @@ def capture(step, iteration, spatial_lr_scale=1.0, active_sh_degree=3, learning_
     pbr = "base_color" in named
     if pbr:
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
-        named["visibility_dc"] = (z(P, 1, 1), z(P, 1, 1), z(P, 1, 1))
-        named["visibility_rest"] = (z(P, 15, 1), z(P, 15, 1), z(P, 15, 1))
+        # (baked by visibility_bake with an optimizer of its own, as finetune_visibility does: the training moments stay zero)
+        vdc, vrest = getattr(step, "visibility_dc", None), getattr(step, "visibility_rest", None)
+        named["visibility_dc"] = (z(P, 1, 1) if vdc is None else vdc, z(P, 1, 1), z(P, 1, 1))
+        named["visibility_rest"] = (z(P, 15, 1) if vrest is None else vrest, z(P, 15, 1), z(P, 15, 1))
     names = STAGE1_GROUPS + (PBR_GROUPS if pbr else ())
     params = {n: nn.Parameter(named[n][0].detach().clone().contiguous().requires_grad_(True)) for n in names}
     lrs = reference_learning_rates(spatial_lr_scale)

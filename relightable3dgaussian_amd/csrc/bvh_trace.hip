@@ -262,6 +262,37 @@ struct BundleRays {
     }
 };
 
+// HemisphereRays: T random rays of every Gaussian of the Morton leaf slots [leaf_lo, leaf_hi) in the hemisphere of its normal, the
+// rays GaussianModel.finetune_visibility draws one iteration at a time (scene/gaussian_model.py:293-296).  Ray idx of the launch
+// is iteration t = idx % T of slot i = leaf_lo + idx / T: the origin coherence of BundleRays.  With g the slot's object id the
+// direction is d = z / max(|z|, 1e-12) of the caller's draw z = raw_dirs[t, g, :] (F.normalize), negated when d . n_g < 0 (strict,
+// n_g from the packed leaf record), the origin mean_g + d * offset as a separate multiply and add.  The result belongs to row
+// t * P + g of the outputs and d to dirs_out[t, g, :]: iteration-major, what the fit kernel (visibility_bake.hip) reads coalesced.
+struct HemisphereRays {
+    const int32_t* __restrict__ leaf_nodes;        // rows P-1.. of the node table: column 3 = object id of the slot
+    const float* __restrict__ raw_dirs;            // [T,P,3]
+    float* __restrict__ dirs_out;                  // [T,P,3]
+    int T, P, leaf_lo;
+    float offset;
+    static constexpr bool optional_counts = true;
+    __device__ __forceinline__ int load(int idx, const TLeaf* __restrict__ tl, float& ox, float& oy, float& oz, float& dx,
+                                        float& dy, float& dz) const
+    {
+        const int q = idx / T, t = idx - q * T, i = leaf_lo + q;
+        const TLeaf* __restrict__ leaf = tl + i;
+        const int g = leaf_nodes[5 * (size_t)i + 3];
+        const int row = t * P + g;                 // (< P * T, which the caller checked to fit an int)
+        const float zx = raw_dirs[3 * (size_t)row], zy = raw_dirs[3 * (size_t)row + 1], zz = raw_dirs[3 * (size_t)row + 2];
+        const float len = fmaxf(sqrtf(zx * zx + zy * zy + zz * zz), 1e-12f);
+        dx = zx / len; dy = zy / len; dz = zz / len;
+        if (dx * leaf->n[0] + dy * leaf->n[1] + dz * leaf->n[2] < 0.f) { dx = -dx; dy = -dy; dz = -dz; }
+        const float sx = dx * offset, sy = dy * offset, sz = dz * offset;
+        ox = leaf->mean[0] + sx; oy = leaf->mean[1] + sy; oz = leaf->mean[2] + sz;
+        dirs_out[3 * (size_t)row] = dx; dirs_out[3 * (size_t)row + 1] = dy; dirs_out[3 * (size_t)row + 2] = dz;
+        return row;
+    }
+};
+
 // ---- packed records, phase-separated persistent waves (R3DG_OPT_TRACE_FORMULATION = 1, default) -------------------------------
 // Persistent waves: 83 % of the visibility rays are occluded after a handful of leaves while the rest walk thousands of
 // nodes, so a fixed ray per thread leaves ~3/4 of the lanes idle.  Here a lane whose ray has finished pulls the next ray
@@ -279,7 +310,7 @@ struct BundleRays {
 // COUNT (R3DG_OPT_TRACE_COUNT_VISITS, measurement builds of the same kernel): every lane counts the node steps (one slab test of
 // both children) and leaf steps (one Gaussian evaluated) of its rays; one 64-bit atomic pair per wave at the end, into words
 // 8..11 of the wave's own queue line (zeroed with the queue heads before the launch; read by r3dg_bvh_trace_visits).
-// Rays: ArrayRays or BundleRays (above).  `ray` holds the OUTPUT row of the lane's current ray (< 0: idle).
+// Rays: ArrayRays, BundleRays or HemisphereRays (above).  `ray` holds the OUTPUT row of the lane's current ray (< 0: idle).
 template <bool COUNT, class Rays>
 __global__ void __launch_bounds__(256)
 trace_opacity_phased_kernel(int num_rays, int P, const TNode* __restrict__ tn, const TLeaf* __restrict__ tl, const Rays rays,
@@ -650,6 +681,32 @@ void bvh_trace_bundles(hipStream_t s, int P, int K, void* records, const int32_t
         trace_opacity_phased_kernel<false, BundleRays><<<grid, 256, 0, s>>>(num_rays, P, tn, tl, rays, contributes, out, overflow,
                                                                            queues, opt(R3DG_OPT_TRACE_REFILL),
                                                                            opt(R3DG_OPT_TRACE_NODE_WEIGHT), opt(R3DG_OPT_TRACE_LEAF_WEIGHT));
+}
+
+// the same trace over the T hemisphere rays of every Gaussian of the leaf slots [leaf_lo, leaf_hi) (HemisphereRays): results at rows
+// t * P + g of out / contributes (NULL: not wanted) / dirs_out, rows of other leaves untouched
+void bvh_trace_hemisphere(hipStream_t s, int P, int T, void* records, const int32_t* nodes, const float* raw_dirs, int leaf_lo,
+                          int leaf_hi, float origin_offset, float* out, float* dirs_out, int32_t* contributes, int* overflow)
+{
+    if (P <= 0 || T <= 0 || leaf_hi <= leaf_lo) return;
+    char* rec = reinterpret_cast<char*>(records);
+    TNode* tn = reinterpret_cast<TNode*>(rec);
+    TLeaf* tl = reinterpret_cast<TLeaf*>(rec + (size_t)P * 64);
+    int* queues = reinterpret_cast<int*>(rec + (size_t)P * 128);
+    const int num_rays = (leaf_hi - leaf_lo) * T;                               // (<= P * T, which the caller checked)
+    const int nblk = (num_rays + 255) / 256, chunk = (nblk + 7) / 8;
+    const int cap = persistent_cus() * 8;
+    const int grid = chunk * 8 < cap ? chunk * 8 : cap;
+    R3DG_HIP(hipMemsetAsync(queues, 0, 8 * 64, s));
+    const HemisphereRays rays = {nodes + 5 * (size_t)(P - 1), raw_dirs, dirs_out, T, P, leaf_lo, origin_offset};
+    if (opt(R3DG_OPT_TRACE_COUNT_VISITS))
+        trace_opacity_phased_kernel<true, HemisphereRays><<<grid, 256, 0, s>>>(num_rays, P, tn, tl, rays, contributes, out, overflow,
+                                                                              queues, opt(R3DG_OPT_TRACE_REFILL),
+                                                                              opt(R3DG_OPT_TRACE_NODE_WEIGHT), opt(R3DG_OPT_TRACE_LEAF_WEIGHT));
+    else
+        trace_opacity_phased_kernel<false, HemisphereRays><<<grid, 256, 0, s>>>(num_rays, P, tn, tl, rays, contributes, out, overflow,
+                                                                               queues, opt(R3DG_OPT_TRACE_REFILL),
+                                                                               opt(R3DG_OPT_TRACE_NODE_WEIGHT), opt(R3DG_OPT_TRACE_LEAF_WEIGHT));
 }
 
 // node / leaf steps of the LAST counting trace over these records (sums over the eight queue lines; synchronises the stream)

@@ -1,4 +1,5 @@
-// C ABI of the BVH build / visibility trace and of the nearest-neighbour distances (include/r3dg_hip.h).
+// C ABI of the BVH build / visibility trace, of the visibility SH fit over its rays and of the nearest-neighbour distances
+// (include/r3dg_hip.h).
 #include "capi_internal.hpp"
 
 using namespace r3dg;
@@ -125,6 +126,50 @@ int r3dg_bvh_trace_bundles(void* stream_, int num_gaussians, int K, void* record
         bvh_trace_bundles(stream, num_gaussians, K, records, nodes, zsamples, leaf_lo, leaf_hi, origin_offset, visibility,
                           num_contributes, dirs_out, stack_overflow);
         check_launch(stream, false, "bvh_trace_bundles");
+        t.stop();
+        return R3DG_OK;
+    });
+}
+
+int r3dg_bvh_trace_hemisphere(void* stream_, int num_gaussians, int T, void* records, const int32_t* nodes, const float* raw_dirs,
+                              int leaf_lo, int leaf_hi, float origin_offset, float* visibility, float* dirs_out,
+                              int32_t* num_contributes, int32_t* stack_overflow)
+{
+    if (num_gaussians < 0) return invalid("bvh_trace_hemisphere: bad Gaussian count");
+    if (T < 0) return invalid("bvh_trace_hemisphere: bad iteration count");
+    if ((int64_t)num_gaussians * T > 0x7fffffffll) return invalid("bvh_trace_hemisphere: num_gaussians * T does not fit the ray index");
+    if (leaf_lo < 0 || leaf_hi < leaf_lo || leaf_hi > num_gaussians) return invalid("bvh_trace_hemisphere: bad leaf range");
+    if (num_gaussians == 0 || T == 0 || leaf_lo == leaf_hi) return R3DG_OK;
+    if (!records || !nodes || !raw_dirs || !visibility || !dirs_out || !stack_overflow)
+        return invalid("bvh_trace_hemisphere: null buffer");
+    return guarded([&]() -> int {
+        hipStream_t stream = (hipStream_t)stream_;
+        StageTimer t(stream, ST_BVH_TRACE);
+        bvh_trace_hemisphere(stream, num_gaussians, T, records, nodes, raw_dirs, leaf_lo, leaf_hi, origin_offset, visibility,
+                             dirs_out, num_contributes, stack_overflow);
+        check_launch(stream, false, "bvh_trace_hemisphere");
+        t.stop();
+        return R3DG_OK;
+    });
+}
+
+int r3dg_visibility_sh_fit_loss_rows(int P) { return visibility_sh_fit_loss_rows(P); }
+
+int r3dg_visibility_sh_fit(void* stream_, int P, int T, int64_t steps_done, const float* dirs, const float* visibility, float lr,
+                           float beta1, float beta2, float eps, float* coeffs, float* exp_avg, float* exp_avg_sq,
+                           float* loss_partials)
+{
+    if (P < 0 || T < 0 || steps_done < 0) return invalid("visibility_sh_fit: bad P, T or step count");
+    if ((int64_t)P * T > 0x7fffffffll) return invalid("visibility_sh_fit: P * T does not fit the row index");
+    if (!(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f)) return invalid("visibility_sh_fit: betas must be in [0, 1)");
+    if (P == 0 || T == 0) return R3DG_OK;
+    if (!dirs || !visibility || !coeffs || !exp_avg || !exp_avg_sq) return invalid("visibility_sh_fit: null buffer");
+    return guarded([&]() -> int {
+        hipStream_t stream = (hipStream_t)stream_;
+        StageTimer t(stream, ST_ADAM);
+        visibility_sh_fit(stream, P, T, (long long)steps_done, dirs, visibility, lr, beta1, beta2, eps, coeffs, exp_avg, exp_avg_sq,
+                          loss_partials);
+        check_launch(stream, false, "visibility_sh_fit");
         t.stop();
         return R3DG_OK;
     });

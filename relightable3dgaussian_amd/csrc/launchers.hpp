@@ -246,6 +246,13 @@ void bvh_trace_opacity_packed(hipStream_t s, int num_rays, int P, void* records,
                               int32_t* contributes, float* out, int* overflow);
 void bvh_trace_bundles(hipStream_t s, int P, int K, void* records, const int32_t* nodes, const float* zsamples, int leaf_lo,
                        int leaf_hi, float origin_offset, float* out, int32_t* contributes, float* dirs_out, int* overflow);
+void bvh_trace_hemisphere(hipStream_t s, int P, int T, void* records, const int32_t* nodes, const float* raw_dirs, int leaf_lo,
+                          int leaf_hi, float origin_offset, float* out, float* dirs_out, int32_t* contributes, int* overflow);
+// visibility_bake.hip
+int visibility_sh_fit_loss_rows(int P);
+void visibility_sh_fit(hipStream_t s, int P, int T, long long steps_done, const float* dirs, const float* visibility, float lr,
+                       float beta1, float beta2, float eps, float* coeffs, float* exp_avg, float* exp_avg_sq,
+                       float* loss_partials);
 void launch_transpose_selftest(hipStream_t s, int N, int dpp, const float* in, float* out, int* chan, int* owner);
 
 }  // namespace r3dg

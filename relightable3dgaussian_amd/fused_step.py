@@ -92,6 +92,10 @@ class FusedStage2Step(FusedStepBase):
         self._incidents = torch.cat([params.incidents_dc.detach(), params.incidents_rest.detach()], 1).contiguous()
         if self._incidents.shape[1] != self.M:      # the reference gives both the same degree (gaussian_model.py:421, :450)
             raise RuntimeError("FusedStage2Step: colour and incident-light SH must hold the same number of coefficients")
+        # the baked-visibility SH groups (visibility_bake.bake_visibility): carried for checkpoint.capture, read by no kernel here
+        for k in ("visibility_dc", "visibility_rest"):
+            t = getattr(params, k, None)
+            setattr(self, k, None if t is None else t.detach().clone().contiguous())
         # script/run_nerf.sh:20-39 (stage 2): lambda_pbr 1, lambda_light 0.01, lambda_env_smooth 0.01; the command does not
         # pass --lambda_normal_render_depth, so that term is off (arguments/__init__.py:115) -- opt in with
         # loss_weights={"normal": 0.01}; the edge-aware smoothness terms are 0 there and 1 / 0.5 / 1 in run_syn4.sh / run_dtu.sh
