@@ -268,6 +268,19 @@ int r3dg_shade_build_transport_rayset(void* stream, int P, int K, int M, const f
                                       const float* d_visibility, const float* d_zsamples, float uniform_area,
                                       const float* d_env, int He, int We, const float* d_env_transform,
                                       float* d_transport, float* d_consts);
+/* The same cache from BAKED visibility: d_visibility_sh [P*16] holds the visibility SH of every Gaussian (visibility_dc |
+ * visibility_rest, what r3dg_visibility_sh_fit produces) and the visibility of sample k is clamp(0.5 + sum_i v_i Y_i(d_k), 0, 1)
+ * (gaussian_renderer/neilf_composite.py:229-231 with bake=True), evaluated at the WORLD-frame direction d_k whatever
+ * d_env_transform is.  No trace and no [P,K] visibility: 0 B in and 12 B out per sample.  The basis of the visibility is always
+ * the full 16; M, the count of incident-light coefficients, is as above.
+ * r3dg_visibility_sh_expand writes that visibility itself, d_visibility_out [P*K], for the consumers that take a [P,K] tensor
+ * (r3dg_shade_build_split, r3dg_shade_forward_cached, r3dg_shade_build_transport). */
+int r3dg_shade_build_transport_baked(void* stream, int P, int K, int M, const float* d_normals, const float* d_incidents,
+                                     const float* d_visibility_sh, const float* d_zsamples, float uniform_area,
+                                     const float* d_env, int He, int We, const float* d_env_transform,
+                                     float* d_transport, float* d_consts);
+int r3dg_visibility_sh_expand(void* stream, int P, int K, const float* d_normals, const float* d_zsamples,
+                              const float* d_visibility_sh, float* d_visibility_out);
 /* Relighting under a light that TURNS WITH EVERY FRAME (relighting.py:160-161 with configs/nerf_syn_light or configs/tnt
  * light_transform.json) and static Gaussians: the "split transport" cache holds what does NOT depend on the light --
  *   d_lt [K,P,4]: per sample (max(SH_incident(d), 0) * a, a) with a = area * max(n . d, 0);  d_vis_t [K/4,P,4]: the visibility

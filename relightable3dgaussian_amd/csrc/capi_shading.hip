@@ -87,6 +87,36 @@ int r3dg_shade_build_transport_rayset(void* stream_, int P, int K, int M, const 
     });
 }
 
+int r3dg_shade_build_transport_baked(void* stream_, int P, int K, int M, const float* normals, const float* incidents,
+                                     const float* visibility_sh, const float* zsamples, float uniform_area, const float* env,
+                                     int He, int We, const float* env_transform, float* transport, float* consts)
+{
+    if (P < 0 || K <= 0) return invalid("shade_build_transport_baked: bad P/K");
+    if (M != 1 && M != 4 && M != 9 && M != 16)
+        return invalid("shade_build_transport_baked: incidents must hold 1, 4, 9 or 16 SH coefficients");
+    if (He <= 0 || We <= 0 || He > 32767 || We > 32767) return invalid("shade_build_transport_baked: bad env size");
+    if (P == 0) return R3DG_OK;
+    if (!normals || !incidents || !visibility_sh || !zsamples || !env || !transport || !consts)
+        return invalid("shade_build_transport_baked: null buffer");
+    return guarded([&]() -> int {
+        launch_shade_build_transport_baked((hipStream_t)stream_, P, K, M, normals, incidents, visibility_sh, zsamples, uniform_area,
+                                           env, He, We, env_transform, transport, consts);
+        return R3DG_OK;
+    });
+}
+
+int r3dg_visibility_sh_expand(void* stream_, int P, int K, const float* normals, const float* zsamples,
+                              const float* visibility_sh, float* visibility_out)
+{
+    if (P < 0 || K <= 0) return invalid("visibility_sh_expand: bad P/K");
+    if (P == 0) return R3DG_OK;
+    if (!normals || !zsamples || !visibility_sh || !visibility_out) return invalid("visibility_sh_expand: null buffer");
+    return guarded([&]() -> int {
+        launch_visibility_sh_expand((hipStream_t)stream_, P, K, normals, zsamples, visibility_sh, visibility_out);
+        return R3DG_OK;
+    });
+}
+
 int r3dg_shade_build_split(void* stream_, int P, int K, const int32_t* perm, const float* normals, const float* incidents,
                            const float* visibility, const float* incident_dirs, const float* zsamples, float uniform_area,
                            float* lt, float* vis_t, float* consts)

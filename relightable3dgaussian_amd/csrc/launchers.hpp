@@ -105,6 +105,11 @@ void launch_shade_build_transport(hipStream_t s, int P, int K, int M, const floa
 void launch_shade_build_transport_rayset(hipStream_t s, int P, int K, int M, const float* normals, const float* incidents,
                                          const float* visibility, const float* zsamples, float uniform_area, const float* env,
                                          int He, int We, const float* tr, float* transport, float* consts);
+void launch_shade_build_transport_baked(hipStream_t s, int P, int K, int M, const float* normals, const float* incidents,
+                                        const float* visibility_sh, const float* zsamples, float uniform_area, const float* env,
+                                        int He, int We, const float* tr, float* transport, float* consts);
+void launch_visibility_sh_expand(hipStream_t s, int P, int K, const float* normals, const float* zsamples,
+                                 const float* visibility_sh, float* out);
 void launch_shade_forward_transport(hipStream_t s, int P, int K, const float* base_color, const float* roughness,
                                     const float* normals, const float* viewdirs, const float* transport, const float* consts,
                                     const float* zsamples, const float* dirs, float* out);

@@ -1,4 +1,5 @@
-// Launcher of the transport-cache builder that regenerates the ray set (shading_transport_rayset.hpp).  A unit of its own, beside
+// Launchers of the transport-cache builders that regenerate the ray set -- from traced [P,K] visibility or from the baked
+// visibility SH -- and of the expansion of that SH into [P,K] (shading_transport_rayset.hpp).  A unit of its own, beside
 // shading_relight.hip, for its floating-point regime.  The lat-long lookup is singular at its poles: what a direction is off by
 // reaches the lookup multiplied by 1 / sin(polar angle), and among a few hundred thousand samples some sit within a tenth of
 // a degree of a pole (a factor of 760 at 0.075 degrees).  So the cache agrees with the two-kernel path on the directions the
@@ -25,9 +26,27 @@ void launch_shade_build_transport_rayset(hipStream_t s, int P, int K, int M, con
                                          int He, int We, const float* tr, float* transport, float* consts)
 {
     if (P == 0) return;
-    shade_build_transport_rayset_kernel<<<(P + TR_WAVES - 1) / TR_WAVES, 64 * TR_WAVES, 0, s>>>(
+    shade_build_transport_rayset_kernel<false><<<(P + TR_WAVES - 1) / TR_WAVES, 64 * TR_WAVES, 0, s>>>(
         P, K, M, normals, incidents, visibility, zsamples, uniform_area, env, He, We, tr, transport, consts);
     check_launch(s, false, "shade_build_transport_rayset_kernel");
+}
+
+void launch_shade_build_transport_baked(hipStream_t s, int P, int K, int M, const float* normals, const float* incidents,
+                                        const float* visibility_sh, const float* zsamples, float uniform_area, const float* env,
+                                        int He, int We, const float* tr, float* transport, float* consts)
+{
+    if (P == 0) return;
+    shade_build_transport_rayset_kernel<true><<<(P + TR_WAVES - 1) / TR_WAVES, 64 * TR_WAVES, 0, s>>>(
+        P, K, M, normals, incidents, visibility_sh, zsamples, uniform_area, env, He, We, tr, transport, consts);
+    check_launch(s, false, "shade_build_transport_rayset_kernel<baked>");
+}
+
+void launch_visibility_sh_expand(hipStream_t s, int P, int K, const float* normals, const float* zsamples,
+                                 const float* visibility_sh, float* out)
+{
+    if (P == 0) return;
+    visibility_sh_expand_kernel<<<(P + TR_WAVES - 1) / TR_WAVES, 64 * TR_WAVES, 0, s>>>(P, K, normals, zsamples, visibility_sh, out);
+    check_launch(s, false, "visibility_sh_expand_kernel");
 }
 
 }  // namespace r3dg

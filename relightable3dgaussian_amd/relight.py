@@ -12,7 +12,10 @@ Construction traces the visibility of the snapshot it takes.  By default through
 around the trace; visibility, directions, areas and the cache records stay resident: 32 bytes per sample).  With
 `RelightRenderer(device_visibility=True)` through train_step.update_visibility_device and, for the transport cache,
 r3dg_shade_build_transport_rayset: no [P,K,3] direction tensor, no area tensor, 16 bytes per sample -- the path for composites
-(compose_scenes), whose concatenated objects must be re-traced at relighting sample counts.
+(compose_scenes), whose concatenated objects must be re-traced at relighting sample counts.  With
+`RelightRenderer(baked_visibility=True)` nothing is traced at all: the visibility of every sample is the clamped SH sum of the
+model's baked coefficients (visibility_bake; relighting.py --bake), evaluated inside r3dg_shade_build_transport_baked -- no BVH,
+no [P,K] visibility tensor, 12 bytes per sample.
 """
 import math
 
@@ -61,13 +64,29 @@ def _incidents_of(model):
     return torch.cat([model.incidents_dc.detach(), model.incidents_rest.detach()], 1).contiguous()
 
 
+def _visibility_sh_of(model):
+    """The baked visibility SH of a model as [P,16]: `visibility_sh` [P,16] (or [P,16,1]), or `visibility_dc` [P,1,1] +
+    `visibility_rest` [P,15,1] -- what visibility_bake.bake_visibility writes, FusedStage2Step carries and checkpoint.restore
+    returns.  None when the model holds neither."""
+    one = getattr(model, "visibility_sh", None)
+    if one is None:
+        dc, rest = getattr(model, "visibility_dc", None), getattr(model, "visibility_rest", None)
+        if dc is None or rest is None:
+            return None
+        one = torch.cat([dc.detach(), rest.detach()], 1)
+    P = one.shape[0]
+    if tuple(one.shape) not in ((P, 16), (P, 16, 1)):
+        raise RuntimeError("the visibility SH of a model must hold 16 coefficients per Gaussian, got %s" % (tuple(one.shape),))
+    return one.detach().reshape(P, 16).contiguous()
+
+
 class RelightRenderer:
     """`model`: anything holding the RAW parameters xyz, normal, scaling, rotation, opacity, base_color, roughness,
     SH colour (`shs` or `features_dc`/`features_rest`) and incident light (`incidents` or `incidents_dc`/`_rest`) --
     bench_core.GaussianParams and fused_step.FusedStage2Step both do.  `envmap` [He,We,3] HDR (EnvLight.envmap)."""
 
     def __init__(self, model, envmap, sample_num, process_group=None, cache="transport", regenerate_dirs=True,
-                 base_color_scale=None, device_visibility=False):
+                 base_color_scale=None, device_visibility=False, baked_visibility=False):
         """`base_color_scale` [3] (None: nothing changes): multiplies the ACTIVATED base colour before shading and packing, as
         GaussianModel.get_base_color does with the per-scene albedo scale that eval_relighting_syn4.py:96-103 sets.
         `cache` -- what is kept between frames while the light does not change:
@@ -90,10 +109,33 @@ class RelightRenderer:
             direction tensor -- the radiance cache; the general kernel r3dg_shade_forward_cached that a turning light falls
             back to when shading_ops.split_supported is false or the light transform is no rotation; frame_reference --
             materialises `incident_dirs` on first use (_directions: sampling.fibonacci_sphere_sampling in chunks, 12 bytes per
-            sample resident from then on plus a transient of about three chunks of [P / ((K-1)//24 + 1), K, 3])."""
-        self.device_visibility = bool(device_visibility)
+            sample resident from then on plus a transient of about three chunks of [P / ((K-1)//24 + 1), K, 3]).
+        `baked_visibility` (default False: nothing changes): NOTHING is traced.  The visibility of sample k is
+            clamp(0.5 + sum_i v_i Y_i(d_k), 0, 1) of the model's baked visibility SH (`visibility_dc` / `visibility_rest` or one
+            `visibility_sh` [P,16]: visibility_bake.bake_visibility; neilf_composite.py:229-231 with bake=True), of which a
+            snapshot `visibility_sh` [P,16] is taken.  No BVH is built: `tracer`, `incident_dirs` and `incident_areas` are None,
+            and so is `visibility` -- the transport cache is built by ONE r3dg_shade_build_transport_baked launch that evaluates
+            the sum per sample (12 bytes per sample resident, 64 bytes per Gaussian of coefficients), keyed on the coefficient
+            and the normal snapshot.  `sample_num` is free of the count the bake used.  A turning light expands the
+            coefficients into a [P,K] tensor for the one r3dg_shade_build_split launch and drops it; what reads a [P,K]
+            visibility per frame -- the radiance cache, the general kernel (see above), frame_reference -- materialises it on
+            first use (_visibility: r3dg_visibility_sh_expand) and keeps it, like the directions.  Needs `regenerate_dirs`;
+            not together with `device_visibility`.  The coefficients of a composite know nothing of the other objects:
+            bake_visibility(composite) first (compose_scenes)."""
+        self.device_visibility, self.baked_visibility = bool(device_visibility), bool(baked_visibility)
         if self.device_visibility and not regenerate_dirs:
             raise RuntimeError("RelightRenderer: device_visibility=True keeps no direction tensor; it needs regenerate_dirs=True")
+        self.visibility_sh = None
+        if self.baked_visibility:
+            if self.device_visibility:
+                raise RuntimeError("RelightRenderer: baked_visibility=True traces nothing; it cannot be combined with device_visibility=True")
+            if not regenerate_dirs:
+                raise RuntimeError("RelightRenderer: baked_visibility=True keeps no direction tensor; it needs regenerate_dirs=True")
+            self.visibility_sh = _visibility_sh_of(model)
+            if self.visibility_sh is None:
+                raise RuntimeError("RelightRenderer: baked_visibility=True needs a model with baked visibility SH (visibility_dc / "
+                                   "visibility_rest or visibility_sh: visibility_bake.bake_visibility)")
+            self.visibility_sh = self.visibility_sh.clone()            # a snapshot, like every parameter below
         if cache not in ("radiance", "transport"):
             raise RuntimeError("RelightRenderer: cache must be 'radiance' or 'transport'")
         self.cache, self.regenerate_dirs = cache, bool(regenerate_dirs)
@@ -116,6 +158,9 @@ class RelightRenderer:
             self.base_color_scale = torch.as_tensor(base_color_scale, dtype=torch.float32).to(self.xyz.device).reshape(3).clone()
         if self.envmap.dim() != 3 or self.envmap.shape[2] != 3:
             raise RuntimeError("envmap must be [He,We,3]")
+        if self.baked_visibility and (self.visibility_sh.shape[0] != self.xyz.shape[0] or self.visibility_sh.dtype != torch.float32
+                                      or self.visibility_sh.device != self.xyz.device):
+            raise RuntimeError("RelightRenderer: the visibility SH must be float32 [P,16] on the device of the parameters")
         for t in (self.xyz, self.envmap):
             if not t.is_cuda:
                 raise RuntimeError("RelightRenderer needs device tensors (there is no CPU path)")
@@ -136,7 +181,10 @@ class RelightRenderer:
             self._order_stream = shared_stream(dev, "order")
         with torch.no_grad():
             self._activate(torch.zeros(3, device=dev))
-            if self.device_visibility:
+            if self.baked_visibility:
+                self.visibility = self.incident_dirs = self.incident_areas = self.tracer = None
+                self._uniform_area = 2.0 * math.pi                                  # (the Fibonacci ray set's, as below)
+            elif self.device_visibility:
                 self.visibility, self.incident_dirs, self.tracer = update_visibility_device(
                     self.xyz, self.a_scales, self.a_rot, self.a_opacity, self.a_normal, sample_num, group=process_group,
                     want_dirs=(cache == "radiance"))
@@ -147,8 +195,23 @@ class RelightRenderer:
 
     def _sample_tensors(self):
         """The tensors the per-sample caches are keyed on (address + version) and reference while they are the key: the
-        direction cache; with device_visibility, where there may be none, the visibility and the normal snapshot."""
+        direction cache; with device_visibility, where there may be none, the visibility and the normal snapshot; with
+        baked_visibility the coefficient and the normal snapshot."""
+        if self.baked_visibility:
+            return (self.visibility_sh, self.normal)
         return (self.visibility, self.normal) if self.device_visibility else (self.incident_dirs,)
+
+    def _ray_table(self):
+        if self._zsamples is None:
+            self._zsamples = sampling.fibonacci_z_samples(self.K, self.dev)[0].t().contiguous()      # [K,3]
+        return self._zsamples
+
+    def _visibility(self):
+        """`visibility`; a baked_visibility renderer, which holds none, expands its coefficients here on first use and keeps the
+        tensor (valid for the coefficient and normal snapshots, which is what such a renderer is built on)."""
+        if self.visibility is None and self.baked_visibility:
+            self.visibility = shading_ops.expand_visibility(self.a_normal, self.visibility_sh, self._ray_table())
+        return self.visibility
 
     def _directions(self):
         """`incident_dirs`; a device_visibility renderer that holds none fills it here, on first use, in the chunks of
@@ -191,13 +254,18 @@ class RelightRenderer:
         self._light_changes = (self._light_changes + 1) if changed else 0
         if self._light_changes >= 2 and self._area_key is not None:          # (the first frame always builds)
             return None
-        if self._taps_key != key and self.device_visibility and self.cache == "transport":
+        if self._taps_key != key and self.baked_visibility and self.cache == "transport":
+            # as below, with the visibility of every sample evaluated in the launch from the 16 baked coefficients
+            self._taps, self._consts = shading_ops.build_transport_baked(
+                self.a_normal, self.incidents, self.visibility_sh, self._ray_table(), self._uniform_area, self.envmap, tr,
+                self._taps, self._consts)
+            self._taps_key, self._taps_ref = key, (tr, samples, self.envmap)
+            self._area_key = 0
+        elif self._taps_key != key and self.device_visibility and self.cache == "transport":
             # the whole cache -- direction, lookup, radiance, transport, constants -- in one launch from the normals and the
             # Fibonacci table; the record buffer of the previous light is reused
-            if self._zsamples is None:
-                self._zsamples = sampling.fibonacci_z_samples(self.K, self.dev)[0].t().contiguous()      # [K,3]
             self._taps, self._consts = shading_ops.build_transport_rayset(
-                self.a_normal, self.incidents, self.visibility, self._zsamples, self._uniform_area, self.envmap, tr,
+                self.a_normal, self.incidents, self.visibility, self._ray_table(), self._uniform_area, self.envmap, tr,
                 self._taps, self._consts)
             self._taps_key, self._taps_ref = key, (tr, samples, self.envmap)
             self._area_key = 0                                 # (no area tensor: nothing to read back, ever)
@@ -216,8 +284,7 @@ class RelightRenderer:
             if self.cache == "transport":
                 # radiance -> transport in place, + the per-Gaussian constants (the buffer must not be handed to
                 # r3dg_shade_forward_cached any more: frame() takes the transport kernel whenever this cache is live)
-                if self._zsamples is None:
-                    self._zsamples = sampling.fibonacci_z_samples(self.K, self.dev)[0].t().contiguous()      # [K,3]
+                self._ray_table()                              # (the per-frame kernel regenerates the directions from it)
                 self._consts = shading_ops.build_transport(
                     self.a_normal, self.incidents, self.visibility, self.incident_dirs, self.incident_areas, self._uniform_area,
                     self._taps, self._consts)
@@ -243,13 +310,17 @@ class RelightRenderer:
             t = given.detach().to(torch.float64).reshape(3, 3)
             if float((t @ t.t() - torch.eye(3, dtype=torch.float64)).abs().max()) > 1e-4:
                 return None                       # scaled / sheared light transform: the general kernel handles it
-        samples = self._sample_tensors() if self.device_visibility else (self.incident_dirs, self.visibility)
+        samples = self._sample_tensors() if self.device_visibility or self.baked_visibility else (self.incident_dirs, self.visibility)
         sample_key = tuple(v for t in samples for v in (t.data_ptr(), t._version)) + (self.regenerate_dirs,)
         env_key = (self.envmap.data_ptr(), self.envmap._version, He, We)
         sp = self._split if isinstance(self._split, dict) else None
         if sp is None or sp["sample_key"] != sample_key:
             zs = sampling.fibonacci_z_samples(self.K, self.dev)[0].t().contiguous()
-            new = shading_ops.build_split(normal_order(self.a_normal), self.a_normal, self.incidents, self.visibility,
+            # (baked_visibility: the [P,K] tensor this one launch reads lives for it alone, unless a consumer already keeps one)
+            vis = self.visibility
+            if vis is None and self.baked_visibility:
+                vis = shading_ops.expand_visibility(self.a_normal, self.visibility_sh, zs)
+            new = shading_ops.build_split(normal_order(self.a_normal), self.a_normal, self.incidents, vis,
                                           None if self.regenerate_dirs else self.incident_dirs, zs, float(self._uniform_area))
             new.update(sample_key=sample_key, sample_ref=samples,
                        env4=None if sp is None else sp["env4"], env_key=None if sp is None else sp["env_key"],
@@ -276,7 +347,7 @@ class RelightRenderer:
         _lib.check(L.r3dg_shade_forward_cached(
             stream(), P, self.K, self.M, self.a_base.data_ptr(), self.a_rough.data_ptr(), self.a_normal.data_ptr(),
             self.a_viewdirs.data_ptr(), self.incidents.data_ptr(), self.envmap.data_ptr(), He, We, _lib.ptr(tr),
-            self.visibility.data_ptr(), self._directions().data_ptr(),
+            self._visibility().data_ptr(), self._directions().data_ptr(),
             None if self._uniform_area is not None else self.incident_areas.data_ptr(), self._uniform_area or 0.0,
             # no cache (a light that changes every frame): lookup in the kernel
             taps.data_ptr() if taps is not None else None, shading_ops.TAPS_ARE_RADIANCE if taps is not None else 0,
@@ -398,12 +469,12 @@ def frame_reference(renderer, cam, bg, env_transform=None, exact_activations=Fal
         if getattr(r, "base_color_scale", None) is not None:
             base_color = base_color * r.base_color_scale
     tr = None if env_transform is None else env_transform.to(r.dev, torch.float32).contiguous()
-    # (a device_visibility renderer holds no direction or area tensor: the directions are materialised on it, on first use, and
-    # stay; the areas, 2 pi each, live for this call)
+    # (a device_visibility or baked_visibility renderer holds no direction or area tensor: the directions -- and the [P,K]
+    # visibility of a baked one -- are materialised on it, on first use, and stay; the areas, 2 pi each, live for this call)
     dirs, areas = r._directions(), r.incident_areas
     if areas is None:
         areas = torch.full((r.P, r.K, 1), r._uniform_area, dtype=torch.float32, device=r.dev)
-    pbr, diffuse, rest = shading_ops.shade(base_color, roughness, normal, viewdirs, r.incidents, r.envmap, r.visibility,
+    pbr, diffuse, rest = shading_ops.shade(base_color, roughness, normal, viewdirs, r.incidents, r.envmap, r._visibility(),
                                            dirs, areas, tr)
     xyz_h = torch.cat([r.xyz, torch.ones_like(r.xyz[:, :1])], -1)
     depths = (xyz_h @ cam.world_view_transform)[:, 2:3]
@@ -467,7 +538,9 @@ def compose_scenes(objects, transforms):
     raw parameter tensors with identical keys.  Returns one dict (feed it to RelightRenderer through a namespace).
     The composite's visibility is traced anew by the renderer it is fed to (relighting.py:119): at a composite's size and
     relighting sample counts pass `device_visibility=True` there, which traces and builds the transport cache without a
-    direction tensor."""
+    direction tensor.  The per-object baked visibility SH (`visibility_dc` / `visibility_rest`), concatenated like every other
+    key, knows nothing of the OTHER objects: the baked path for a composite is visibility_bake.bake_visibility(composite), which
+    traces the composite, followed by RelightRenderer(baked_visibility=True) -- what `--bake` means in relighting.py:97."""
     if not objects or len(objects) != len(transforms):
         raise RuntimeError("compose_scenes needs one transform per object")
     moved = [transform_object(o, t) for o, t in zip(objects, transforms)]

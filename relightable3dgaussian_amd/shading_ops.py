@@ -166,6 +166,63 @@ def build_transport_rayset(normals, incidents, visibility, zsamples, uniform_are
     return transport, consts
 
 
+def _visibility_sh(visibility_sh, P):
+    """The baked visibility coefficients as a contiguous [P,16]; [P,16,1] (visibility_dc | visibility_rest concatenated) is taken too."""
+    v = _c(visibility_sh)
+    if tuple(v.shape) not in ((P, 16), (P, 16, 1)):
+        raise RuntimeError("visibility_sh must hold the 16 visibility SH coefficients of every Gaussian: [P,16] or [P,16,1]")
+    return v.reshape(P, 16)
+
+
+def expand_visibility(normals, visibility_sh, zsamples, out=None):
+    """r3dg_visibility_sh_expand: the baked visibility clamp(0.5 + sum_i v_i Y_i(d_k), 0, 1) of `visibility_sh` [P,16] on the
+    fixed ray set of `normals` and `zsamples` [K,3] -> [P,K,1], for the consumers that take a visibility tensor (build_split,
+    shade_forward, build_transport); `out`: a buffer to reuse (fully overwritten)."""
+    if normals.dim() != 2 or normals.shape[1] != 3 or zsamples.dim() != 2 or zsamples.shape[1] != 3:
+        raise RuntimeError("expand_visibility: normals must be [P,3] and zsamples [K,3]")
+    P, K = normals.shape[0], zsamples.shape[0]
+    t = [_c(x) for x in (normals, zsamples)]
+    v = _visibility_sh(visibility_sh, P)
+    if out is None:
+        out = torch.empty(P, K, 1, dtype=torch.float32, device=normals.device)
+    elif out.dtype != torch.float32 or not out.is_cuda or out.numel() != P * K or not out.is_contiguous():
+        raise RuntimeError("out must be a contiguous float32 [P,K,1] device tensor")
+    with torch.cuda.device(normals.device):
+        _lib.check(_lib.lib().r3dg_visibility_sh_expand(
+            _lib.current_stream(), P, K, t[0].data_ptr(), t[1].data_ptr(), v.data_ptr(), out.data_ptr()), "visibility_sh_expand")
+    return out
+
+
+def build_transport_baked(normals, incidents, visibility_sh, zsamples, uniform_area, env, env_transform=None, transport=None,
+                          consts=None):
+    """r3dg_shade_build_transport_baked: build_transport_rayset with the visibility of every sample taken from the baked
+    coefficients `visibility_sh` [P,16] (visibility_bake; evaluated at the world-frame direction, whatever `env_transform`): no
+    trace and no [P,K] visibility tensor -> (transport [P,K,3], consts [P,16]); `transport` / `consts`: buffers to reuse (fully
+    overwritten)."""
+    if normals.dim() != 2 or normals.shape[1] != 3 or zsamples.dim() != 2 or zsamples.shape[1] != 3 or incidents.dim() != 3:
+        raise RuntimeError("build_transport_baked: normals must be [P,3], zsamples [K,3] and incidents [P,M,3]")
+    P, K, M = normals.shape[0], zsamples.shape[0], incidents.shape[1]
+    t = [_c(x) for x in (normals, incidents, zsamples, env)]
+    v = _visibility_sh(visibility_sh, P)
+    tr = _c(env_transform) if env_transform is not None else None
+    He, We = env.shape[0], env.shape[1]
+    f = dict(dtype=torch.float32, device=normals.device)
+    if transport is None:
+        transport = torch.empty(P, K, 3, **f)
+    elif transport.dtype != torch.float32 or tuple(transport.shape) != (P, K, 3) or not transport.is_contiguous():
+        raise RuntimeError("transport must be a contiguous float32 [P,K,3] tensor")
+    if consts is None:
+        consts = torch.empty(P, 16, **f)
+    elif consts.dtype != torch.float32 or consts.numel() != 16 * P or not consts.is_contiguous():
+        raise RuntimeError("consts must be a contiguous float32 [P,16] tensor")
+    with torch.cuda.device(normals.device):
+        _lib.check(_lib.lib().r3dg_shade_build_transport_baked(
+            _lib.current_stream(), P, K, M, t[0].data_ptr(), t[1].data_ptr(), v.data_ptr(), t[2].data_ptr(),
+            float(uniform_area), t[3].data_ptr(), int(He), int(We), _lib.ptr(tr), transport.data_ptr(), consts.data_ptr()),
+            "shade_build_transport_baked")
+    return transport, consts
+
+
 def shade_forward_transport(base_color, roughness, normals, viewdirs, transport, consts, zsamples, incident_dirs=None, out=None):
     """r3dg_shade_forward_transport: the GGX lobe of every sample against the cached transport -> out[P,19].
     `incident_dirs` None: the directions are regenerated from the normals and `zsamples` [K,3]."""
