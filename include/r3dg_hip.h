@@ -752,6 +752,51 @@ int r3dg_eval_image_metrics(void* stream, int width, int height, int channels, c
 int r3dg_eval_median_ratio(void* stream, int width, int height, const float* d_pred, const float* d_gt,
                            const float* d_mask, uint32_t* d_state, double* d_row);
 
+/* ---- scene assembly: PLY records <-> parameter groups, objects into a composite (relighting.py:28-52 scene_composition;
+ *      scene/gaussian_model.py:507-665 save_ply / load_ply; ply.py, compose.py) ------------------------------------------------
+ * A RECORD is one row of a reference PLY body: R3DG_SCENE_COLUMNS (130) floats in the order of construct_list_of_attributes
+ *   (x y z, nx ny nz, f_dc_0..2, f_rest_0..44, opacity, scale_0..2, rot_0..3 -- the R3DG_SCENE_STAGE1_COLUMNS (62) a stage-1
+ *   file ends with -- then base_color_0..2, roughness, incidents_dc_0..2, incidents_rest_0..44, visibility_dc_0,
+ *   visibility_rest_0..14); *_rest columns are channel-major (f_rest_{c*15+i} is coefficient i+1 of channel c).
+ * The GROUPS are the R3DG_SCENE_GROUPS (13) parameter tensors of a model, coefficient-major, in the order
+ *   xyz [P,3], normal [P,3], features_dc [P,1,3], features_rest [P,15,3], opacity [P,1], scaling [P,3], rotation [P,4],
+ *   base_color [P,3], roughness [P,1], incidents_dc [P,1,3], incidents_rest [P,15,3], visibility_dc [P,1,1],
+ *   visibility_rest [P,15,1].  A group table is a HOST array of 13 device pointers in that order (`dst_groups`, `src_groups`).
+ * r3dg_scene_place_records: rows [0,P) of d_records [P,A] (A floats per row, 62 <= A <= R3DG_SCENE_MAX_COLUMNS; 4-byte aligned
+ *   is enough) are read through d_column_map (int32 [130]: the file column of every canonical slot, -1 = absent, read as 0) and
+ *   written to rows [row_offset, row_offset + P) of the 13 destination tensors (all required), one launch: 64-row tiles staged
+ *   through LDS, every access to device memory with consecutive lanes on consecutive floats.
+ *   d_placement (may be NULL: a pure copy) is R3DG_SCENE_PLACEMENT_FLOATS floats describing the object's similarity transform
+ *   T as relight.transform_object defines it: [0..11] the upper three rows of T, row-major 3x4; [12..14] the per-axis scale
+ *   (row norms of T[:3,:3]); [15..23] R = T[:3,:3] / scale, row-major; [24..27] R's quaternion (w,x,y,z); [28..36], [37..61],
+ *   [62..110] the band 1, 2, 3 SH rotation matrices, row-major (read only with R3DG_SCENE_ROTATE_SH).  Per row:
+ *   xyz = T (x,1); scaling = log(exp(s) * scale); normal = R n; rotation = quaternion * rotation.
+ *   flags: R3DG_SCENE_ZERO_INCIDENTS writes zeros to the placed rows of incidents_dc / incidents_rest (relighting.py:49-50);
+ *   R3DG_SCENE_ROTATE_SH (needs d_placement) multiplies bands 1..3 of the colour, incident-light (unless zeroed) and visibility
+ *   SH by the three matrices, c'_l = M_l c_l; without it coefficients are copied unchanged, as the reference does.
+ * r3dg_scene_place_groups: the same with the 13 tensors of an in-memory model (P rows each) as the source; the six PBR
+ *   entries of src_groups may ALL be NULL (a stage-1 model: read as 0).
+ * r3dg_scene_pack_records: the inverse of the unpack -- src_groups (P rows) -> d_records [P,columns], columns 62 (the first
+ *   seven groups are read) or 130.
+ * Rows outside the placed range are not touched; nothing synchronises; no atomics. */
+#define R3DG_SCENE_COLUMNS 130
+#define R3DG_SCENE_STAGE1_COLUMNS 62
+#define R3DG_SCENE_GROUPS 13
+#define R3DG_SCENE_MAX_COLUMNS 250
+#define R3DG_SCENE_PLACEMENT_FLOATS 111
+#define R3DG_SCENE_ZERO_INCIDENTS 1
+#define R3DG_SCENE_ROTATE_SH 2
+int r3dg_scene_place_records(void* stream, int P, int A, const float* d_records, const int32_t* d_column_map,
+                             const float* d_placement, int flags, long long row_offset, void** dst_groups);
+int r3dg_scene_place_groups(void* stream, int P, void** src_groups, const float* d_placement, int flags,
+                            long long row_offset, void** dst_groups);
+int r3dg_scene_pack_records(void* stream, int P, int columns, void** src_groups, float* d_records);
+
+/* r3dg_relight_quantize: a frame for an 8-bit image file, d_image [C,H,W] float -> d_bytes [H,W,C] uint8 (1 <= C <= 4) as
+ *   torchvision's save_image quantises: clamp(x * 255 + 0.5, 0, 255) truncated, the product and the sum rounded separately.
+ *   NaN quantises to 0.  The driver copies d_bytes asynchronously into its ring of pinned host buffers. */
+int r3dg_relight_quantize(void* stream, int width, int height, int channels, const float* d_image, uint8_t* d_bytes);
+
 /* ---- densification bookkeeping -------------------------------------------------------------------
  * r3dg_densify_accumulate: GaussianModel.add_densification_stats (scene/gaussian_model.py:931-937) + the max-radii
  *   update of train.py:164-165, one pass.  The visibility filter is radii > 0 (render.py / neilf.py `visibility_filter`).

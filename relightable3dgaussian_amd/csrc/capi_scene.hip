@@ -1,0 +1,93 @@
+// C ABI of the scene assembly (include/r3dg_hip.h): PLY records <-> parameter groups, objects into a composite, and the 8-bit
+// quantisation of a frame.  Set-up and output paths, outside the per-stage timing of a training iteration or a relight frame.
+#include "capi_internal.hpp"
+
+using namespace r3dg;
+
+namespace {
+
+// a host table of R3DG_SCENE_GROUPS device pointers -> SceneGroups; `required`: how many leading entries must be non-NULL, and
+// the remaining ones must then be all set or all NULL
+bool read_groups(void** table, int required, bool rest_optional, SceneGroups& out)
+{
+    if (!table) return false;
+    int rest = 0;
+    for (int g = 0; g < R3DG_SCENE_GROUPS; g++) {
+        out.p[g] = (float*)table[g];
+        if (g < required && !table[g]) return false;
+        if (g >= required && table[g]) rest++;
+    }
+    if (rest_optional) return rest == 0 || rest == R3DG_SCENE_GROUPS - required;
+    return rest == R3DG_SCENE_GROUPS - required;
+}
+
+int check_placement(const char* who, int P, long long row_offset, const float* placement, int flags)
+{
+    if (P < 0 || row_offset < 0) return invalid(std::string(who) + ": bad row count or offset");
+    if (flags & ~(R3DG_SCENE_ZERO_INCIDENTS | R3DG_SCENE_ROTATE_SH)) return invalid(std::string(who) + ": unknown flag");
+    if ((flags & R3DG_SCENE_ROTATE_SH) && !placement) return invalid(std::string(who) + ": rotate_sh needs a placement");
+    return R3DG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int r3dg_scene_place_records(void* stream_, int P, int A, const float* records, const int32_t* column_map,
+                             const float* placement, int flags, long long row_offset, void** dst_groups)
+{
+    if (int e = check_placement("scene_place_records", P, row_offset, placement, flags)) return e;
+    if (A < R3DG_SCENE_STAGE1_COLUMNS || A > R3DG_SCENE_MAX_COLUMNS) return invalid("scene_place_records: bad column count");
+    if (P == 0) return R3DG_OK;
+    SceneGroups dst;
+    if (!records || !column_map || !read_groups(dst_groups, R3DG_SCENE_GROUPS, false, dst))
+        return invalid("scene_place_records: null buffer");
+    if ((size_t)records & 3) return invalid("scene_place_records: records must be 4-byte aligned");
+    return guarded([&]() -> int {
+        launch_scene_place_records((hipStream_t)stream_, P, A, records, column_map, placement, flags, row_offset, dst);
+        return R3DG_OK;
+    });
+}
+
+int r3dg_scene_place_groups(void* stream_, int P, void** src_groups, const float* placement, int flags, long long row_offset,
+                            void** dst_groups)
+{
+    if (int e = check_placement("scene_place_groups", P, row_offset, placement, flags)) return e;
+    if (P == 0) return R3DG_OK;
+    SceneGroups src, dst;
+    if (!read_groups(src_groups, 7, true, src) || !read_groups(dst_groups, R3DG_SCENE_GROUPS, false, dst))
+        return invalid("scene_place_groups: null buffer (the six PBR source groups are all present or all absent)");
+    return guarded([&]() -> int {
+        launch_scene_place_groups((hipStream_t)stream_, P, src, placement, flags, row_offset, dst);
+        return R3DG_OK;
+    });
+}
+
+int r3dg_scene_pack_records(void* stream_, int P, int columns, void** src_groups, float* records)
+{
+    if (P < 0) return invalid("scene_pack_records: bad P");
+    if (columns != R3DG_SCENE_STAGE1_COLUMNS && columns != R3DG_SCENE_COLUMNS)
+        return invalid("scene_pack_records: a record holds 62 or 130 columns");
+    if (P == 0) return R3DG_OK;
+    SceneGroups src;
+    if (!records || !read_groups(src_groups, columns == R3DG_SCENE_COLUMNS ? R3DG_SCENE_GROUPS : 7, true, src))
+        return invalid("scene_pack_records: null buffer");
+    return guarded([&]() -> int {
+        launch_scene_pack_records((hipStream_t)stream_, P, columns, src, records);
+        return R3DG_OK;
+    });
+}
+
+int r3dg_relight_quantize(void* stream_, int width, int height, int channels, const float* image, uint8_t* bytes)
+{
+    if (width < 0 || height < 0 || channels < 1 || channels > 4) return invalid("relight_quantize: bad shape");
+    if ((long long)width * height == 0) return R3DG_OK;
+    if ((long long)width * height >= (1ll << 31)) return invalid("relight_quantize: image too large");
+    if (!image || !bytes) return invalid("relight_quantize: null buffer");
+    return guarded([&]() -> int {
+        launch_relight_quantize((hipStream_t)stream_, width, height, channels, image, bytes);
+        return R3DG_OK;
+    });
+}
+
+}  // extern "C"

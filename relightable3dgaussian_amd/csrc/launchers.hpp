@@ -220,6 +220,16 @@ struct CaptureMaps {
 };
 void launch_relight_capture(hipStream_t s, int W, int H, const float* feature, const float* opacity, const int* n_contrib,
                             const float* background, const float* mask, const CaptureMaps& maps);
+// scene_assembly.hip: PLY records <-> the 13 parameter groups (r3dg_hip.h "scene assembly"); a NULL entry = absent group
+struct SceneGroups {
+    float* p[R3DG_SCENE_GROUPS];
+};
+void launch_scene_place_records(hipStream_t s, int P, int A, const float* records, const int* column_map, const float* placement,
+                                int flags, long long row_offset, const SceneGroups& dst);
+void launch_scene_place_groups(hipStream_t s, int P, const SceneGroups& src, const float* placement, int flags,
+                               long long row_offset, const SceneGroups& dst);
+void launch_scene_pack_records(hipStream_t s, int P, int columns, const SceneGroups& src, float* records);
+void launch_relight_quantize(hipStream_t s, int W, int H, int C, const float* image, uint8_t* bytes);
 // ssim.hip: the value-only SSIM tiling; tile_sums [C * ceil(W/32) * ceil(H/32)][2]
 void launch_eval_metric_tiles(hipStream_t s, int W, int H, int C, const float* pred, const float* gt, const float* mask,
                               const float* fill, int fill_is_image, double* tile_sums);
