@@ -15,7 +15,8 @@ r3dg_shade_build_transport_rayset: no [P,K,3] direction tensor, no area tensor, 
 (compose_scenes), whose concatenated objects must be re-traced at relighting sample counts.  With
 `RelightRenderer(baked_visibility=True)` nothing is traced at all: the visibility of every sample is the clamped SH sum of the
 model's baked coefficients (visibility_bake; relighting.py --bake), evaluated inside r3dg_shade_build_transport_baked -- no BVH,
-no [P,K] visibility tensor, 12 bytes per sample.
+no [P,K] visibility tensor, 12 bytes per sample.  Which of the three a renderer is built on is known to its sample-set owner
+alone (_StoredSamples, _RaySetSamples); the renderer keeps the cache state and asks the owner for everything per sample.
 """
 import math
 
@@ -80,6 +81,140 @@ def _visibility_sh_of(model):
     return one.detach().reshape(P, 16).contiguous()
 
 
+def _tensor_key(*tensors):
+    """Identity of tensors WITHOUT reading device memory back: storage address + version counter of each.  It is one only for
+    as long as the tensors live, so whoever stores such a key stores the tensors beside it: the allocator then cannot hand the
+    address of a dropped tensor to its successor (relighting.py:162-163 builds a new light matrix per frame: without the
+    reference a recycled address would read as "the light did not move").  A tensor that is swapped in or edited in place gets
+    a new key through the address / version pair."""
+    return tuple(v for t in tensors for v in (t.data_ptr(), t._version))
+
+
+class _Samples:
+    """Where the visibility, direction and area of the P x K samples come from: one owner per kind (below).  The renderer asks
+    its owner (RelightRenderer._samples) and never which kind it is; `r` is the renderer that asks (not kept: bench_core clones
+    renderers that then share one owner).  An owner holds `visibility`, `incident_dirs`, `incident_areas`, `tracer`,
+    `visibility_sh` (None where its kind has none) and answers:
+      light_key(r) / split_key(r)    the tensors the fixed-light cache / the split cache are keyed on (_tensor_key) and reference
+      visibility_of(r, keep)         the [P,K,1] visibility; one made for the call is only kept if `keep`
+      directions(r)                  the [P,K,3] direction tensor; one made for the call is kept
+      areas(r), uniform_area         the [P,K,1] areas; the area of all samples where there is one (the kernels then take no pointer)
+      build_cache(r, tr, He, We)     the transport / radiance records of this light into r._taps (+ r._consts), r._area_key set"""
+
+    def visibility_of(self, r, keep=True):
+        if self.visibility is not None:
+            return self.visibility
+        vis = shading_ops.expand_visibility(r.a_normal, self.visibility_sh, r._ray_table())
+        self.visibility = vis if keep else None     # (kept: valid for the coefficient and normal snapshots it was made of)
+        return vis
+
+    def directions(self, r):
+        if self.incident_dirs is None:      # in the chunks of update_visibility: a transient of about three chunks
+            dirs = torch.empty(r.P, r.K, 3, dtype=torch.float32, device=r.dev)
+            chunk = max(1, r.P // ((r.K - 1) // 24 + 1))
+            for off in range(0, r.P, chunk):
+                dirs[off:off + chunk] = sampling.fibonacci_sphere_sampling(r.a_normal[off:off + chunk], r.K)[0]
+            self.incident_dirs = dirs
+        return self.incident_dirs
+
+
+class _StoredSamples(_Samples):
+    """Traced by train_step.update_visibility (PyTorch glue around the trace, sharded over the process group): visibility,
+    directions and areas are resident tensors, 20 bytes per sample beside the 12 of the cache records.  The caches are keyed on
+    the direction tensor (the split cache on the visibility as well).  The area of all samples is found on the first build for
+    an area tensor (fibonacci_sphere_sampling gives 2 pi to all: then the area tensor need not be read at all)."""
+
+    def __init__(self, r, sample_num, group):
+        self.visibility, self.incident_dirs, self.incident_areas, self.tracer = update_visibility(
+            r.xyz, r.a_scales, r.a_rot, r.a_opacity, r.a_normal, sample_num, group=group)
+        self.visibility_sh = self.uniform_area = None
+
+    def light_key(self, r):
+        return (self.incident_dirs,)
+
+    def split_key(self, r):
+        return (self.incident_dirs, self.visibility)
+
+    def areas(self, r):
+        return self.incident_areas
+
+    def build_cache(self, r, tr, He, We):
+        # the HDR map is fixed while relighting, so the SAMPLED RADIANCE of every cached direction is cached (not just the
+        # lookup coordinates): the shading kernel then reads 12 bytes per sample and no texture
+        r._taps = shading_ops.build_taps(self.incident_dirs, He, We, tr, radiance_of=r.envmap)
+        if r._area_key != self.incident_areas.data_ptr():
+            lo, hi = float(self.incident_areas.min()), float(self.incident_areas.max())
+            self.uniform_area = lo if lo == hi else None
+            r._area_key = self.incident_areas.data_ptr()
+        if r.cache == "transport":
+            # radiance -> transport in place, + the per-Gaussian constants (the buffer must not be handed to
+            # r3dg_shade_forward_cached any more: the renderer takes the transport kernel whenever this cache is live)
+            r._ray_table()                                 # (the per-frame kernel regenerates the directions from it)
+            r._consts = shading_ops.build_transport(r.a_normal, r.incidents, self.visibility, self.incident_dirs,
+                                                    self.incident_areas, self.uniform_area, r._taps, r._consts)
+
+
+class _RaySetSamples(_Samples):
+    """The Fibonacci ray set of the normals, of which nothing per sample is stored but the visibility: no direction tensor, no
+    area tensor (2 pi to all by construction, nothing is read back), the transport cache from ONE launch that generates the
+    rays itself, into the record buffer of the previous light.  The caches are keyed on the visibility tensor and the normal
+    snapshot (the directions are a function of the normals; a swapped-in `incident_dirs` is not noticed).  What still reads a
+    stored direction tensor -- the radiance cache, the general kernel r3dg_shade_forward_cached, frame_reference --
+    materialises `incident_dirs` on first use and keeps it (12 bytes per sample from then on).  Two kinds:
+    traced(): the visibility [P,K,1] comes from train_step.update_visibility_device (rays generated in the trace kernel,
+        sharded over the process group); builder r3dg_shade_build_transport_rayset; 4 + 12 bytes per sample resident.
+    baked(): NOTHING is traced and no BVH is built.  The visibility of sample k is clamp(0.5 + sum_i v_i Y_i(d_k), 0, 1) of a
+        snapshot `visibility_sh` [P,16] of the model's baked coefficients (visibility_bake.bake_visibility;
+        neilf_composite.py:229-231 with bake=True), which stands in the keys where the visibility tensor stands above;
+        builder r3dg_shade_build_transport_baked, which evaluates the sum per sample: 12 bytes per sample resident, 64 per
+        Gaussian.  The split cache's one launch reads a [P,K] expansion (r3dg_visibility_sh_expand) that is dropped after it;
+        what reads one per frame (see above) keeps it, like the directions."""
+    incident_areas, uniform_area = None, 2.0 * math.pi
+
+    def __init__(self, visibility=None, incident_dirs=None, tracer=None, visibility_sh=None):
+        self.visibility, self.incident_dirs, self.tracer, self.visibility_sh = visibility, incident_dirs, tracer, visibility_sh
+
+    @classmethod
+    def traced(cls, r, sample_num, group):
+        return cls(*update_visibility_device(r.xyz, r.a_scales, r.a_rot, r.a_opacity, r.a_normal, sample_num, group=group,
+                                             want_dirs=(r.cache == "radiance")))
+
+    @classmethod
+    def baked(cls, model):
+        sh = _visibility_sh_of(model)
+        if sh is None:
+            raise RuntimeError("RelightRenderer: baked_visibility=True needs a model with baked visibility SH (visibility_dc / "
+                               "visibility_rest or visibility_sh: visibility_bake.bake_visibility)")
+        return cls(visibility_sh=sh.clone())                # a snapshot, like every parameter of the renderer
+
+    def _source(self):
+        return self.visibility if self.visibility_sh is None else self.visibility_sh
+
+    def light_key(self, r):
+        return (self._source(), r.normal)
+
+    split_key = light_key
+
+    def areas(self, r):
+        return torch.full((r.P, r.K, 1), self.uniform_area, dtype=torch.float32, device=r.dev)
+
+    def build_cache(self, r, tr, He, We):
+        if r.cache == "transport":
+            # the whole cache -- direction, lookup, radiance, transport, constants -- in one launch from the normals and the
+            # Fibonacci table; the record buffer of the previous light is reused
+            build = shading_ops.build_transport_rayset if self.visibility_sh is None else shading_ops.build_transport_baked
+            r._taps, r._consts = build(r.a_normal, r.incidents, self._source(), r._ray_table(), self.uniform_area, r.envmap, tr,
+                                       r._taps, r._consts)
+        else:
+            r._taps = shading_ops.build_taps(self.directions(r), He, We, tr, radiance_of=r.envmap)
+        r._area_key = 0                                     # (no area tensor: nothing to read back, ever)
+
+
+def _of_samples(name):
+    """A renderer attribute that lives in the sample-set owner."""
+    return property(lambda self: getattr(self._samples, name), lambda self, value: setattr(self._samples, name, value))
+
+
 class RelightRenderer:
     """`model`: anything holding the RAW parameters xyz, normal, scaling, rotation, opacity, base_color, roughness,
     SH colour (`shs` or `features_dc`/`features_rest`) and incident light (`incidents` or `incidents_dc`/`_rest`) --
@@ -99,43 +234,20 @@ class RelightRenderer:
             direction from the normal and the Fibonacci table instead of reading the direction cache.
         "radiance": only the sampled environment radiance of every cached direction (12 bytes per sample) is kept and the
             full integral (r3dg_shade_forward_cached) runs per frame.
-        `device_visibility` (default False: nothing changes): the visibility is traced by train_step.update_visibility_device
-            (the rays are generated in the trace kernel; sharded over `process_group` like update_visibility) and the transport
-            cache is built by ONE r3dg_shade_build_transport_rayset launch from the normals and the Fibonacci table.
-            `incident_areas` is None (every area is 2 pi by construction, nothing is read back) and `incident_dirs` is None
-            unless `cache` is "radiance": resident per sample are the visibility (4 bytes) and the transport (12) instead of 32
-            bytes.  Needs `regenerate_dirs`.  The caches are then keyed on the visibility tensor and the normal snapshot (the
-            directions are a function of the normals; a swapped-in `incident_dirs` is not noticed).  What still reads a stored
-            direction tensor -- the radiance cache; the general kernel r3dg_shade_forward_cached that a turning light falls
-            back to when shading_ops.split_supported is false or the light transform is no rotation; frame_reference --
-            materialises `incident_dirs` on first use (_directions: sampling.fibonacci_sphere_sampling in chunks, 12 bytes per
-            sample resident from then on plus a transient of about three chunks of [P / ((K-1)//24 + 1), K, 3]).
-        `baked_visibility` (default False: nothing changes): NOTHING is traced.  The visibility of sample k is
-            clamp(0.5 + sum_i v_i Y_i(d_k), 0, 1) of the model's baked visibility SH (`visibility_dc` / `visibility_rest` or one
-            `visibility_sh` [P,16]: visibility_bake.bake_visibility; neilf_composite.py:229-231 with bake=True), of which a
-            snapshot `visibility_sh` [P,16] is taken.  No BVH is built: `tracer`, `incident_dirs` and `incident_areas` are None,
-            and so is `visibility` -- the transport cache is built by ONE r3dg_shade_build_transport_baked launch that evaluates
-            the sum per sample (12 bytes per sample resident, 64 bytes per Gaussian of coefficients), keyed on the coefficient
-            and the normal snapshot.  `sample_num` is free of the count the bake used.  A turning light expands the
-            coefficients into a [P,K] tensor for the one r3dg_shade_build_split launch and drops it; what reads a [P,K]
-            visibility per frame -- the radiance cache, the general kernel (see above), frame_reference -- materialises it on
-            first use (_visibility: r3dg_visibility_sh_expand) and keeps it, like the directions.  Needs `regenerate_dirs`;
-            not together with `device_visibility`.  The coefficients of a composite know nothing of the other objects:
-            bake_visibility(composite) first (compose_scenes)."""
+        Where the samples come from (default: traced here, everything resident -- _StoredSamples):
+        `device_visibility`: traced on the device, no direction or area tensor (_RaySetSamples.traced) -- the path for
+            composites at relighting sample counts.
+        `baked_visibility`: nothing is traced; the model's baked visibility SH is evaluated instead (_RaySetSamples.baked).
+            `sample_num` is free of the count the bake used.  The coefficients of a composite know nothing of the other
+            objects: bake_visibility(composite) first (compose_scenes).
+        Either needs `regenerate_dirs`; not both."""
         self.device_visibility, self.baked_visibility = bool(device_visibility), bool(baked_visibility)
-        if self.device_visibility and not regenerate_dirs:
-            raise RuntimeError("RelightRenderer: device_visibility=True keeps no direction tensor; it needs regenerate_dirs=True")
-        self.visibility_sh = None
-        if self.baked_visibility:
-            if self.device_visibility:
-                raise RuntimeError("RelightRenderer: baked_visibility=True traces nothing; it cannot be combined with device_visibility=True")
-            if not regenerate_dirs:
-                raise RuntimeError("RelightRenderer: baked_visibility=True keeps no direction tensor; it needs regenerate_dirs=True")
-            self.visibility_sh = _visibility_sh_of(model)
-            if self.visibility_sh is None:
-                raise RuntimeError("RelightRenderer: baked_visibility=True needs a model with baked visibility SH (visibility_dc / "
-                                   "visibility_rest or visibility_sh: visibility_bake.bake_visibility)")
-            self.visibility_sh = self.visibility_sh.clone()            # a snapshot, like every parameter below
+        if (self.device_visibility or self.baked_visibility) and not regenerate_dirs:
+            raise RuntimeError("RelightRenderer: %s=True keeps no direction tensor; it needs regenerate_dirs=True"
+                               % ("device_visibility" if self.device_visibility else "baked_visibility"))
+        if self.device_visibility and self.baked_visibility:
+            raise RuntimeError("RelightRenderer: baked_visibility=True traces nothing; it cannot be combined with device_visibility=True")
+        self._samples = _RaySetSamples.baked(model) if self.baked_visibility else None      # (the others: traced below)
         if cache not in ("radiance", "transport"):
             raise RuntimeError("RelightRenderer: cache must be 'radiance' or 'transport'")
         self.cache, self.regenerate_dirs = cache, bool(regenerate_dirs)
@@ -143,7 +255,7 @@ class RelightRenderer:
         self._taps = self._taps_key = self._taps_ref = None
         self._light_key = self._light_ref = None
         self._light_changes = 0
-        self._area_key, self._uniform_area = None, None
+        self._area_key = None
         self._consts = self._zsamples = None
         self._split = None                          # split-transport cache of a light that turns with every frame (_split_cache)
         self._order_stream = None                   # the instance ordering of a frame runs there, beside the shading kernel
@@ -181,113 +293,44 @@ class RelightRenderer:
             self._order_stream = shared_stream(dev, "order")
         with torch.no_grad():
             self._activate(torch.zeros(3, device=dev))
-            if self.baked_visibility:
-                self.visibility = self.incident_dirs = self.incident_areas = self.tracer = None
-                self._uniform_area = 2.0 * math.pi                                  # (the Fibonacci ray set's, as below)
-            elif self.device_visibility:
-                self.visibility, self.incident_dirs, self.tracer = update_visibility_device(
-                    self.xyz, self.a_scales, self.a_rot, self.a_opacity, self.a_normal, sample_num, group=process_group,
-                    want_dirs=(cache == "radiance"))
-                self.incident_areas, self._uniform_area = None, 2.0 * math.pi       # (fibonacci_sphere_sampling: 2 pi to all)
-            else:
-                self.visibility, self.incident_dirs, self.incident_areas, self.tracer = update_visibility(
-                    self.xyz, self.a_scales, self.a_rot, self.a_opacity, self.a_normal, sample_num, group=process_group)
+            if not self.baked_visibility:
+                trace = _RaySetSamples.traced if self.device_visibility else _StoredSamples
+                self._samples = trace(self, sample_num, process_group)
 
-    def _sample_tensors(self):
-        """The tensors the per-sample caches are keyed on (address + version) and reference while they are the key: the
-        direction cache; with device_visibility, where there may be none, the visibility and the normal snapshot; with
-        baked_visibility the coefficient and the normal snapshot."""
-        if self.baked_visibility:
-            return (self.visibility_sh, self.normal)
-        return (self.visibility, self.normal) if self.device_visibility else (self.incident_dirs,)
+    # what tests, tools and the benchmark read and swap on the renderer (a swapped-in tensor is noticed by the keys)
+    visibility, incident_dirs, incident_areas = _of_samples("visibility"), _of_samples("incident_dirs"), _of_samples("incident_areas")
+    tracer, visibility_sh = _of_samples("tracer"), _of_samples("visibility_sh")
+    _uniform_area = property(lambda self: self._samples.uniform_area)
 
     def _ray_table(self):
         if self._zsamples is None:
             self._zsamples = sampling.fibonacci_z_samples(self.K, self.dev)[0].t().contiguous()      # [K,3]
         return self._zsamples
 
-    def _visibility(self):
-        """`visibility`; a baked_visibility renderer, which holds none, expands its coefficients here on first use and keeps the
-        tensor (valid for the coefficient and normal snapshots, which is what such a renderer is built on)."""
-        if self.visibility is None and self.baked_visibility:
-            self.visibility = shading_ops.expand_visibility(self.a_normal, self.visibility_sh, self._ray_table())
-        return self.visibility
-
-    def _directions(self):
-        """`incident_dirs`; a device_visibility renderer that holds none fills it here, on first use, in the chunks of
-        update_visibility (the directions update_visibility_device evaluates under a process group)."""
-        if self.incident_dirs is None:
-            P, K = self.P, self.K
-            dirs = torch.empty(P, K, 3, dtype=torch.float32, device=self.dev)
-            chunk = max(1, P // ((K - 1) // 24 + 1))
-            for off in range(0, P, chunk):
-                dirs[off:off + chunk] = sampling.fibonacci_sphere_sampling(self.a_normal[off:off + chunk], K)[0]
-            self.incident_dirs = dirs
-        return self.incident_dirs
-
     def _taps_for(self, tr, He, We, given=None):
         """shading_ops.build_taps of the direction cache for this light rotation (None = identity); one entry is kept, so
         a static light costs one build.  `tr`: the rotation on the device, `given`: the caller's tensor it came from."""
-        # Identity of the light WITHOUT reading device memory back: a host tensor is keyed by its nine values; a device
-        # tensor by its storage address + version counter -- and a reference to it is kept for as long as it is the key, so
-        # that the allocator cannot hand the same address to the NEXT frame's matrix (relighting.py:162-163 builds a new
-        # tensor per frame: without the reference a recycled address would read as "the light did not move").
+        # identity of the light: a host tensor by its nine values, a device tensor like every other keyed tensor
         if tr is None:
             ident = None
         elif given is not None and not given.is_cuda:
             ident = tuple(float(x) for x in given.detach().reshape(-1).tolist())
         else:
-            ident = (tr.data_ptr(), tr._version)
-        # (the map and the direction cache are held by this object, so their addresses are theirs alone for as long as the
-        # key is; a caller that swaps either in gets a new key through the version / address pair of the new tensor while the
-        # old one is still referenced below)
-        samples = self._sample_tensors()
-        key = (ident, He, We) + tuple(v for t in samples for v in (t.data_ptr(), t._version)) + (
-            self.envmap.data_ptr(), self.envmap._version)
+            ident = _tensor_key(tr)
+        samples = self._samples.light_key(self)
+        key = (ident, He, We) + _tensor_key(*samples, self.envmap)
         # A light that turns with EVERY frame (configs/nerf_syn_light, configs/tnt): writing the cache costs what the lookup
         # inside the shading kernel costs and the kernel would then still have to read it back -- from the second
         # consecutive change on, no cache: None = r3dg_shade_forward_cached evaluates the lookup itself (measured: 3.6 ms
         # per frame with a rebuild, 2.5 without; DESIGN.md section 6).  A light that stops turning gets its cache back on
         # the next frame.
-        changed = self._light_key != key
+        self._light_changes = (self._light_changes + 1) if self._light_key != key else 0
         self._light_key, self._light_ref = key, (tr, samples, self.envmap)
-        self._light_changes = (self._light_changes + 1) if changed else 0
         if self._light_changes >= 2 and self._area_key is not None:          # (the first frame always builds)
             return None
-        if self._taps_key != key and self.baked_visibility and self.cache == "transport":
-            # as below, with the visibility of every sample evaluated in the launch from the 16 baked coefficients
-            self._taps, self._consts = shading_ops.build_transport_baked(
-                self.a_normal, self.incidents, self.visibility_sh, self._ray_table(), self._uniform_area, self.envmap, tr,
-                self._taps, self._consts)
+        if self._taps_key != key:
+            self._samples.build_cache(self, tr, He, We)
             self._taps_key, self._taps_ref = key, (tr, samples, self.envmap)
-            self._area_key = 0
-        elif self._taps_key != key and self.device_visibility and self.cache == "transport":
-            # the whole cache -- direction, lookup, radiance, transport, constants -- in one launch from the normals and the
-            # Fibonacci table; the record buffer of the previous light is reused
-            self._taps, self._consts = shading_ops.build_transport_rayset(
-                self.a_normal, self.incidents, self.visibility, self._ray_table(), self._uniform_area, self.envmap, tr,
-                self._taps, self._consts)
-            self._taps_key, self._taps_ref = key, (tr, samples, self.envmap)
-            self._area_key = 0                                 # (no area tensor: nothing to read back, ever)
-        elif self._taps_key != key:
-            # the HDR map is fixed while relighting, so the SAMPLED RADIANCE of every cached direction is cached (not just
-            # the lookup coordinates): the shading kernel then reads 12 bytes per sample and no texture
-            self._taps = shading_ops.build_taps(self._directions(), He, We, tr, radiance_of=self.envmap)
-            self._taps_key, self._taps_ref = key, (tr, samples, self.envmap)
-            if self.incident_areas is None:
-                self._area_key = 0                             # (device_visibility: 2 pi by construction)
-            elif self._area_key != self.incident_areas.data_ptr():
-                # fibonacci_sphere_sampling gives every sample the area 2 pi: then the area cache need not be read at all
-                lo, hi = float(self.incident_areas.min()), float(self.incident_areas.max())
-                self._uniform_area = lo if lo == hi else None
-                self._area_key = self.incident_areas.data_ptr()
-            if self.cache == "transport":
-                # radiance -> transport in place, + the per-Gaussian constants (the buffer must not be handed to
-                # r3dg_shade_forward_cached any more: frame() takes the transport kernel whenever this cache is live)
-                self._ray_table()                              # (the per-frame kernel regenerates the directions from it)
-                self._consts = shading_ops.build_transport(
-                    self.a_normal, self.incidents, self.visibility, self.incident_dirs, self.incident_areas, self._uniform_area,
-                    self._taps, self._consts)
         return self._taps
 
     def _split_cache(self, tr=None, given=None):
@@ -310,21 +353,18 @@ class RelightRenderer:
             t = given.detach().to(torch.float64).reshape(3, 3)
             if float((t @ t.t() - torch.eye(3, dtype=torch.float64)).abs().max()) > 1e-4:
                 return None                       # scaled / sheared light transform: the general kernel handles it
-        samples = self._sample_tensors() if self.device_visibility or self.baked_visibility else (self.incident_dirs, self.visibility)
-        sample_key = tuple(v for t in samples for v in (t.data_ptr(), t._version)) + (self.regenerate_dirs,)
-        env_key = (self.envmap.data_ptr(), self.envmap._version, He, We)
+        samples = self._samples.split_key(self)
+        sample_key = _tensor_key(*samples) + (self.regenerate_dirs,)
+        env_key = _tensor_key(self.envmap) + (He, We)
         sp = self._split if isinstance(self._split, dict) else None
         if sp is None or sp["sample_key"] != sample_key:
-            zs = sampling.fibonacci_z_samples(self.K, self.dev)[0].t().contiguous()
-            # (baked_visibility: the [P,K] tensor this one launch reads lives for it alone, unless a consumer already keeps one)
-            vis = self.visibility
-            if vis is None and self.baked_visibility:
-                vis = shading_ops.expand_visibility(self.a_normal, self.visibility_sh, zs)
-            new = shading_ops.build_split(normal_order(self.a_normal), self.a_normal, self.incidents, vis,
-                                          None if self.regenerate_dirs else self.incident_dirs, zs, float(self._uniform_area))
-            new.update(sample_key=sample_key, sample_ref=samples,
-                       env4=None if sp is None else sp["env4"], env_key=None if sp is None else sp["env_key"],
-                       env_ref=None if sp is None else sp["env_ref"])
+            # (a visibility that has to be expanded lives for this one launch alone, unless a consumer already keeps one)
+            new = shading_ops.build_split(normal_order(self.a_normal), self.a_normal, self.incidents,
+                                          self._samples.visibility_of(self, keep=False),
+                                          None if self.regenerate_dirs else self.incident_dirs, self._ray_table(),
+                                          float(self._uniform_area))
+            new.update(sample_key=sample_key, sample_ref=samples,           # (the footprints of the map carry over)
+                       **{k: None if sp is None else sp[k] for k in ("env4", "env_key", "env_ref")})
             sp = self._split = new
         if sp["env_key"] != env_key:
             sp["env4"] = shading_ops.env_footprints(self.envmap)
@@ -343,15 +383,29 @@ class RelightRenderer:
         if self.base_color_scale is not None:
             self.a_base.mul_(self.base_color_scale)
 
-    def _shade_cached(self, L, stream, P, He, We, tr, taps):
-        _lib.check(L.r3dg_shade_forward_cached(
-            stream(), P, self.K, self.M, self.a_base.data_ptr(), self.a_rough.data_ptr(), self.a_normal.data_ptr(),
-            self.a_viewdirs.data_ptr(), self.incidents.data_ptr(), self.envmap.data_ptr(), He, We, _lib.ptr(tr),
-            self._visibility().data_ptr(), self._directions().data_ptr(),
-            None if self._uniform_area is not None else self.incident_areas.data_ptr(), self._uniform_area or 0.0,
-            # no cache (a light that changes every frame): lookup in the kernel
-            taps.data_ptr() if taps is not None else None, shading_ops.TAPS_ARE_RADIANCE if taps is not None else 0,
-            self.shade_out.data_ptr()), "shade_forward")
+    def _shade(self, tr, given, He, We):
+        """The shading of one frame into `shade_out`, by the entry point that the cache of this light (`tr`, from the caller's
+        `given`) allows: the GGX lobe against the transport cache; for a light that turns with every frame the split transport
+        with the lookup of the rotated direction in the kernel (lane = Gaussian, sorted by normal); else the general kernel,
+        with the radiance cache or, with none (taps NULL), the lookup in the kernel."""
+        # the lat-long lookups of the cached directions are constant for a fixed light rotation: cached per transform
+        taps = self._taps_for(tr, He, We, given)
+        if taps is not None and self.cache == "transport":
+            shading_ops.shade_forward_transport(
+                self.a_base, self.a_rough, self.a_normal, self.a_viewdirs, taps, self._consts, self._zsamples,
+                None if self.regenerate_dirs else self.incident_dirs, self.shade_out)
+        elif taps is None and (sp := self._split_cache(tr, given)) is not None:
+            shading_ops.shade_forward_split(sp, self.a_base, self.a_rough, self.a_normal, self.a_viewdirs, tr, sp["env4"],
+                                            He, We, self.shade_out)
+        else:
+            s = self._samples
+            _lib.check(_lib.lib().r3dg_shade_forward_cached(
+                _lib.current_stream(), self.P, self.K, self.M, self.a_base.data_ptr(), self.a_rough.data_ptr(),
+                self.a_normal.data_ptr(), self.a_viewdirs.data_ptr(), self.incidents.data_ptr(), self.envmap.data_ptr(), He, We,
+                _lib.ptr(tr), s.visibility_of(self).data_ptr(), s.directions(self).data_ptr(),
+                None if s.uniform_area is not None else s.incident_areas.data_ptr(), s.uniform_area or 0.0,
+                taps.data_ptr() if taps is not None else None, shading_ops.TAPS_ARE_RADIANCE if taps is not None else 0,
+                self.shade_out.data_ptr()), "shade_forward")
 
     @torch.no_grad()
     def frame(self, cam, bg, env_transform=None, outputs=("pbr_env",), mask=None, capture_background=None):
@@ -380,20 +434,7 @@ class RelightRenderer:
                 bg, self.xyz, self.features, empty, self.a_opacity, self.a_scales, self.a_rot, 1.0, empty, vm,
                 cam.full_proj_transform, cam.tanfovx, cam.tanfovy, cam.cx, cam.cy, H, W, self.shs, 3, campos, False,
                 True, False, want_weights=False)                   # (a frame has no use for the per-Gaussian blend weights)
-            # the lat-long lookups of the cached directions are constant for a fixed light rotation: cached per transform
-            taps = self._taps_for(tr, He, We, env_transform)
-            sp = None
-            if taps is not None and self.cache == "transport":
-                shading_ops.shade_forward_transport(
-                    self.a_base, self.a_rough, self.a_normal, self.a_viewdirs, taps, self._consts, self._zsamples,
-                    None if self.regenerate_dirs else self.incident_dirs, self.shade_out)
-            elif taps is None and (sp := self._split_cache(tr, env_transform)) is not None:
-                # a light that turns with every frame: the light-independent half of the transport is cached, the lookup of the
-                # rotated direction happens in the kernel (lane = Gaussian, sorted by normal)
-                shading_ops.shade_forward_split(sp, self.a_base, self.a_rough, self.a_normal, self.a_viewdirs, tr, sp["env4"],
-                                                He, We, self.shade_out)
-            else:
-                self._shade_cached(L, stream, P, He, We, tr, taps)
+            self._shade(tr, env_transform, He, We)
             _lib.check(L.r3dg_relight_pack_features(
                 stream(), P, self.xyz.data_ptr(), vm.data_ptr(), self.a_normal.data_ptr(), self.a_base.data_ptr(),
                 self.a_rough.data_ptr(), self.shade_out.data_ptr(), self.features.data_ptr()), "relight_pack_features")
@@ -469,13 +510,11 @@ def frame_reference(renderer, cam, bg, env_transform=None, exact_activations=Fal
         if getattr(r, "base_color_scale", None) is not None:
             base_color = base_color * r.base_color_scale
     tr = None if env_transform is None else env_transform.to(r.dev, torch.float32).contiguous()
-    # (a device_visibility or baked_visibility renderer holds no direction or area tensor: the directions -- and the [P,K]
-    # visibility of a baked one -- are materialised on it, on first use, and stay; the areas, 2 pi each, live for this call)
-    dirs, areas = r._directions(), r.incident_areas
-    if areas is None:
-        areas = torch.full((r.P, r.K, 1), r._uniform_area, dtype=torch.float32, device=r.dev)
-    pbr, diffuse, rest = shading_ops.shade(base_color, roughness, normal, viewdirs, r.incidents, r.envmap, r._visibility(),
-                                           dirs, areas, tr)
+    # (a sample set that holds no direction, visibility or area tensor materialises the first two on the renderer, on first
+    # use, where they stay; the areas live for this call)
+    s = r._samples
+    pbr, diffuse, rest = shading_ops.shade(base_color, roughness, normal, viewdirs, r.incidents, r.envmap, s.visibility_of(r),
+                                           s.directions(r), s.areas(r), tr)
     xyz_h = torch.cat([r.xyz, torch.ones_like(r.xyz[:, :1])], -1)
     depths = (xyz_h @ cam.world_view_transform)[:, 2:3]
     feats = torch.cat([depths, depths.square(), pbr, normal, base_color, roughness, diffuse, rest], -1)      # S = 28

@@ -138,32 +138,39 @@ def build_transport(normals, incidents, visibility, incident_dirs, incident_area
     return consts
 
 
+def _launch_ray_set_builder(entry, normals, incidents, visibility, zsamples, env, uniform_area, tr, transport, consts):
+    """What build_transport_rayset and build_transport_baked share: the record and constant buffers (a given `transport` was checked
+    by the caller, like every other argument) and the launch of r3dg_<entry>, whose `visibility` is the [P,K] tensor or the
+    [P,16] coefficients."""
+    P, K, M = normals.shape[0], zsamples.shape[0], incidents.shape[1]
+    f = dict(dtype=torch.float32, device=normals.device)
+    if transport is None:
+        transport = torch.empty(P, K, 3, **f)
+    if consts is None:
+        consts = torch.empty(P, 16, **f)
+    elif consts.dtype != torch.float32 or consts.numel() != 16 * P or not consts.is_contiguous():
+        raise RuntimeError("consts must be a contiguous float32 [P,16] tensor")
+    with torch.cuda.device(normals.device):
+        _lib.check(getattr(_lib.lib(), "r3dg_" + entry)(
+            _lib.current_stream(), P, K, M, normals.data_ptr(), incidents.data_ptr(), visibility.data_ptr(), zsamples.data_ptr(),
+            float(uniform_area), env.data_ptr(), int(env.shape[0]), int(env.shape[1]), _lib.ptr(tr), transport.data_ptr(),
+            consts.data_ptr()), entry)
+    return transport, consts
+
+
 def build_transport_rayset(normals, incidents, visibility, zsamples, uniform_area, env, env_transform=None, transport=None,
                            consts=None):
     """r3dg_shade_build_transport_rayset: the transport cache of build_taps(..., radiance_of=env) + build_transport in ONE launch
     for the fixed ray set of `normals` and `zsamples` [K,3] (no direction tensor is read or written) -> (transport [P,K,3],
     consts [P,16]); `transport` / `consts`: buffers to reuse (fully overwritten)."""
-    P, K, M = normals.shape[0], zsamples.shape[0], incidents.shape[1]
-    He, We = env.shape[0], env.shape[1]
-    f = dict(dtype=torch.float32, device=normals.device)
-    if transport is None:
-        transport = torch.empty(P, K, 3, **f)
-    elif transport.dtype != torch.float32 or transport.numel() != 3 * P * K or not transport.is_contiguous():
+    P, K = normals.shape[0], zsamples.shape[0]
+    if transport is not None and (transport.dtype != torch.float32 or transport.numel() != 3 * P * K or not transport.is_contiguous()):
         raise RuntimeError("transport must be a contiguous float32 [P,K,3] tensor")
-    if consts is None:
-        consts = torch.empty(P, 16, **f)
-    elif consts.dtype != torch.float32 or consts.numel() != 16 * P or not consts.is_contiguous():
-        raise RuntimeError("consts must be a contiguous float32 [P,16] tensor")
     if visibility.numel() != P * K:
         raise RuntimeError("visibility must hold P x K values")
     t = [_c(x) for x in (normals, incidents, visibility, zsamples, env)]
     tr = _c(env_transform) if env_transform is not None else None
-    with torch.cuda.device(normals.device):
-        _lib.check(_lib.lib().r3dg_shade_build_transport_rayset(
-            _lib.current_stream(), P, K, M, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
-            float(uniform_area), t[4].data_ptr(), int(He), int(We), _lib.ptr(tr), transport.data_ptr(), consts.data_ptr()),
-            "shade_build_transport_rayset")
-    return transport, consts
+    return _launch_ray_set_builder("shade_build_transport_rayset", *t, uniform_area, tr, transport, consts)
 
 
 def _visibility_sh(visibility_sh, P):
@@ -201,26 +208,13 @@ def build_transport_baked(normals, incidents, visibility_sh, zsamples, uniform_a
     overwritten)."""
     if normals.dim() != 2 or normals.shape[1] != 3 or zsamples.dim() != 2 or zsamples.shape[1] != 3 or incidents.dim() != 3:
         raise RuntimeError("build_transport_baked: normals must be [P,3], zsamples [K,3] and incidents [P,M,3]")
-    P, K, M = normals.shape[0], zsamples.shape[0], incidents.shape[1]
+    P, K = normals.shape[0], zsamples.shape[0]
     t = [_c(x) for x in (normals, incidents, zsamples, env)]
     v = _visibility_sh(visibility_sh, P)
     tr = _c(env_transform) if env_transform is not None else None
-    He, We = env.shape[0], env.shape[1]
-    f = dict(dtype=torch.float32, device=normals.device)
-    if transport is None:
-        transport = torch.empty(P, K, 3, **f)
-    elif transport.dtype != torch.float32 or tuple(transport.shape) != (P, K, 3) or not transport.is_contiguous():
+    if transport is not None and (transport.dtype != torch.float32 or tuple(transport.shape) != (P, K, 3) or not transport.is_contiguous()):
         raise RuntimeError("transport must be a contiguous float32 [P,K,3] tensor")
-    if consts is None:
-        consts = torch.empty(P, 16, **f)
-    elif consts.dtype != torch.float32 or consts.numel() != 16 * P or not consts.is_contiguous():
-        raise RuntimeError("consts must be a contiguous float32 [P,16] tensor")
-    with torch.cuda.device(normals.device):
-        _lib.check(_lib.lib().r3dg_shade_build_transport_baked(
-            _lib.current_stream(), P, K, M, t[0].data_ptr(), t[1].data_ptr(), v.data_ptr(), t[2].data_ptr(),
-            float(uniform_area), t[3].data_ptr(), int(He), int(We), _lib.ptr(tr), transport.data_ptr(), consts.data_ptr()),
-            "shade_build_transport_baked")
-    return transport, consts
+    return _launch_ray_set_builder("shade_build_transport_baked", t[0], t[1], v, t[2], t[3], uniform_area, tr, transport, consts)
 
 
 def shade_forward_transport(base_color, roughness, normals, viewdirs, transport, consts, zsamples, incident_dirs=None, out=None):

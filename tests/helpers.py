@@ -185,3 +185,120 @@ def stage_args(case, fwd_ref, d_mean2D, d_conic, d_colors):
     f32 = lambda a: to_np(a).astype(np.float32)
     return (c[1], c[5], c[6], c[7], c[8], c[17], c[18], c[9], c[10], c[11], c[12], c[19], case["W"], case["H"], fwd_ref[9],
             st["clamped"], f32(d_mean2D).reshape(-1, 3), f32(d_conic).reshape(-1, 4), f32(d_colors).reshape(-1, 3))
+
+
+# ---- the recording library of the relight CPU tests (tests/test_host_mirrors_cpu.py, tests/test_relight_device_visibility_cpu.py,
+# tests/test_relight_baked_cpu.py, tests/test_relight_call_sequences_cpu.py): RelightRenderer's host side with every C-ABI entry
+# point replaced by a recorder, so that nothing runs on a GPU -----------------------------------------------------------------
+class DeviceTensor(torch.Tensor):            # a CPU tensor that claims to be a device tensor
+    is_cuda = property(lambda self: True)
+
+
+def dt(t):
+    return t.as_subclass(DeviceTensor)
+
+
+class Recorder:
+    """Stands for the loaded library: every entry point appends (name, args) -- or what `convert(name, args)` makes of them --
+    to `calls` and returns 0.  `wanted` collects the `want_weights` of every rasterizer front end the fake below stood in for."""
+
+    def __init__(self, convert=None):
+        self.calls, self.wanted, self.convert = [], [], convert or (lambda name, args: (name, args))
+
+    def __getattr__(self, name):
+        def fn(*args):
+            self.calls.append(self.convert(name, args))
+            return 0
+        return fn
+
+    def names(self):
+        return [c[0] for c in self.calls]
+
+    def args_of(self, name):
+        return [c[1] for c in self.calls if c[0] == name]
+
+
+class FakePending:
+    """What rasterizer_ops.rasterize_gaussians_begin returns, for a 4x4 frame of P Gaussians of which 3 are rendered."""
+
+    def __init__(self, P):
+        self.P = P
+
+    def finish(self, ordering_stream=None):
+        z = torch.zeros
+        return (3, z(1), z(3, 4, 4), z(1, 4, 4), z(1, 4, 4), z(28, 4, 4), z(3, 4, 4), z(3, 4, 4), None, z(self.P))
+
+
+def recording_library(monkeypatch, P, convert=None):
+    """Puts a Recorder in the place of the library for the rest of the test and makes the host code around it run on CPU
+    tensors (the renderer's own buffers are CPU tensors here); the rasterizer front end returns a FakePending."""
+    import contextlib
+    from relightable3dgaussian_amd import _lib, rasterizer_ops, shading_ops
+    rec = Recorder(convert)
+    monkeypatch.setattr(_lib, "lib", lambda: rec)
+    monkeypatch.setattr(_lib, "current_stream", lambda: 0)
+    monkeypatch.setattr(shading_ops, "_c", lambda t: t.contiguous())
+    monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())
+    monkeypatch.setattr(rasterizer_ops, "rasterize_gaussians_begin",
+                        lambda *a, want_weights=True, **k: rec.wanted.append(want_weights) or FakePending(P))
+    return rec
+
+
+def relight_model(P, **extra):
+    """The raw parameters RelightRenderer reads, all zero; `xyz` claims to be on a device."""
+    import types
+    z = torch.zeros
+    return types.SimpleNamespace(xyz=dt(z(P, 3)), normal=z(P, 3), scaling=z(P, 3), rotation=z(P, 4), opacity=z(P, 1),
+                                 base_color=z(P, 3), roughness=z(P, 1), shs=z(P, 16, 3), incidents=z(P, 16, 3), **extra)
+
+
+def relight_camera():
+    import types
+    return types.SimpleNamespace(image_height=4, image_width=4, world_view_transform=torch.eye(4), full_proj_transform=torch.eye(4),
+                                 camera_center=torch.zeros(3), tanfovx=0.5, tanfovy=0.5, cx=2.0, cy=2.0)
+
+
+def z_rotation_by(a, device=None):
+    """A light rotation: `a` radians about z."""
+    import math
+    return torch.tensor([[math.cos(a), -math.sin(a), 0.0], [math.sin(a), math.cos(a), 0.0], [0.0, 0.0, 1.0]], device=device)
+
+
+def z_rotation(i):
+    """The light rotation of step i of a turning light in the recording-library tests: 0.3 i radians about z, on the host."""
+    return z_rotation_by(0.3 * i)
+
+
+# ---- the turning-light sequence of the relight GPU tests (tests/test_relight_gpu.py, tests/test_relight_device_visibility_gpu.py,
+# tests/test_relight_baked_gpu.py) -------------------------------------------------------------------------------------------------
+CACHED_PATTERN = [True, False, False, False, True, True]        # the first change still builds; a light that stops is cached again
+SPLIT_PATTERN = [False, True, True, True, True, True]           # built at the second consecutive change, kept
+
+
+def turning_light_frames(r, cam, bg, per_frame=None):
+    """Six frames of renderer `r` under a light on the device that turns four times and then stops (the last rotation three times
+    over), each into a NaN-filled shade_out.  -> (rotations, cached, split, frames): per frame whether the lookup cache was
+    live after it, whether a split cache was, and copies of the "feature" and "pbr_env" images.  `per_frame(tr, got)` runs
+    after each frame, while shade_out still holds it."""
+    trs = [z_rotation_by(a, device=cam.world_view_transform.device) for a in (0.1, 0.7, 1.3, 1.9)]
+    trs += [trs[-1], trs[-1]]
+    cached, split, frames = [], [], []
+    for tr in trs:
+        r.shade_out.fill_(float("nan"))
+        got = r.frame(cam, bg, env_transform=tr, outputs=("pbr_env",))
+        cached.append(r._taps_key == r._light_key)
+        split.append(bool(r._split))
+        frames.append({k: got[k].clone() for k in ("feature", "pbr_env")})
+        if per_frame is not None:
+            per_frame(tr, got)
+    return trs, cached, split, frames
+
+
+def assert_frame_matches_glue(r, cam, bg, tr, got):
+    """`got` against relight.frame_reference(exact_activations=True) under the light `tr`, which shades with the general HIP op:
+    two fp32 evaluations of the ill-conditioned GGX term."""
+    from relightable3dgaussian_amd import relight
+    want = relight.frame_reference(r, cam, bg, env_transform=tr, exact_activations=True)
+    for k, rtol, atol in (("feature", 1e-3, 1e-6), ("pbr_env", 0.0, 4e-4)):
+        ok, msg = report(k, got[k], want[k], rtol, atol)
+        assert ok, msg

@@ -173,45 +173,18 @@ def test_relight_renderer_host_logic_with_a_recording_library(monkeypatch):
     """RelightRenderer.frame's host side only (every C-ABI entry point replaced by a recorder, nothing runs on a GPU): which
     shading entry point a frame takes and with which cache -- transport cache (default), radiance cache, and no cache once
     the light turns with every frame."""
-    import types
-    from relightable3dgaussian_amd import _lib, rasterizer_ops, relight, shading_ops
-    calls = []
-
-    class Recorder:
-        def __getattr__(self, name):
-            def fn(*args):
-                calls.append((name, args))
-                return 0
-            return fn
-
-    class DeviceTensor(torch.Tensor):            # a CPU tensor that claims to be a device tensor
-        is_cuda = property(lambda self: True)
-
-    dt = lambda t: t.as_subclass(DeviceTensor)
+    from relightable3dgaussian_amd import relight, shading_ops
+    from tests.helpers import dt, recording_library, relight_camera, relight_model, z_rotation as rot
     P, K = 7, 8
-    monkeypatch.setattr(_lib, "lib", lambda: Recorder())
-    monkeypatch.setattr(_lib, "current_stream", lambda: 0)
-    monkeypatch.setattr(shading_ops, "_c", lambda t: t.contiguous())          # (the renderer's own buffers are CPU tensors here)
-    import contextlib
-    monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())
+    rec = recording_library(monkeypatch, P)
+    calls, names, wanted = rec.calls, rec.names, rec.wanted
     monkeypatch.setattr(relight, "update_visibility", lambda *a, **k: (torch.ones(P, K, 1), torch.ones(P, K, 3),
                                                                        torch.full((P, K, 1), 2.0), None))
     built = []
     monkeypatch.setattr(shading_ops, "build_taps", lambda dirs, He, We, tr=None, radiance_of=None:
                         built.append(tr) or torch.zeros(P * K * 3))
     z = torch.zeros
-    class _Pending:
-        def finish(self, ordering_stream=None):
-            return (3, z(1), z(3, 4, 4), z(1, 4, 4), z(1, 4, 4), z(28, 4, 4), z(3, 4, 4), z(3, 4, 4), None, z(P))
-    wanted = []
-    monkeypatch.setattr(rasterizer_ops, "rasterize_gaussians_begin",
-                        lambda *a, want_weights=True, **k: wanted.append(want_weights) or _Pending())
-    model = types.SimpleNamespace(xyz=dt(z(P, 3)), normal=z(P, 3), scaling=z(P, 3), rotation=z(P, 4), opacity=z(P, 1),
-                                  base_color=z(P, 3), roughness=z(P, 1), shs=z(P, 16, 3), incidents=z(P, 16, 3))
-    cam = types.SimpleNamespace(image_height=4, image_width=4, world_view_transform=torch.eye(4), full_proj_transform=torch.eye(4),
-                                camera_center=z(3), tanfovx=0.5, tanfovy=0.5, cx=2.0, cy=2.0)
-    env = dt(z(8, 16, 3))
-    names = lambda: [c[0] for c in calls]
+    model, cam, env = relight_model(P), relight_camera(), dt(z(8, 16, 3))
     # radiance cache, built once for a fixed light
     r = relight.RelightRenderer(model, env, K, cache="radiance")
     calls.clear()
@@ -226,11 +199,6 @@ def test_relight_renderer_host_logic_with_a_recording_library(monkeypatch):
     # lookup inside the per-frame kernel
     calls.clear()
     del built[:]
-    import math
-
-    def rot(i):
-        a = 0.3 * i
-        return torch.tensor([[math.cos(a), -math.sin(a), 0.0], [math.sin(a), math.cos(a), 0.0], [0.0, 0.0, 1.0]])
     for i in range(4):
         r.frame(cam, z(3), env_transform=rot(i))
     flags = [c[1][-2] for c in calls if c[0] == "r3dg_shade_forward_cached"]

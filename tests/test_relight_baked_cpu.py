@@ -3,7 +3,6 @@ r3dg_shade_build_transport_baked, their derived ctypes signatures and the built 
 mirrors and of the constructor, which must come before the library is touched; where the coefficients are taken from; and the
 renderer's host logic against a recording library (the technique of tests/test_relight_device_visibility_cpu.py): no trace, one
 baked builder launch under a fixed light, a transient expansion in front of the split cache under a turning one."""
-import contextlib
 import ctypes as C
 import math
 import os
@@ -11,6 +10,8 @@ import types
 
 import pytest
 import torch
+
+from tests.helpers import dt, recording_library, relight_camera, relight_model as _model, z_rotation as rot
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -39,11 +40,6 @@ def test_header_declares_both_functions_and_the_library_exports_them():
     assert L.r3dg_visibility_sh_expand is not None and L.r3dg_shade_build_transport_baked is not None
 
 
-class DeviceTensor(torch.Tensor):            # a CPU tensor that claims to be a device tensor
-    is_cuda = property(lambda self: True)
-
-
-dt = lambda t: t.as_subclass(DeviceTensor)
 z = torch.zeros
 
 
@@ -81,11 +77,6 @@ def test_mirrors_refuse_before_touching_the_library(monkeypatch):
         so.build_transport_baked(n, z(P, 16, 3), v, zs, 2.0 * math.pi, env)                              # CPU incident light
     with pytest.raises(RuntimeError):
         so.build_transport_baked(n, inc, v, zs, 2.0 * math.pi, z(8, 16, 3))                               # CPU map
-
-
-def _model(P, **extra):
-    return types.SimpleNamespace(xyz=dt(z(P, 3)), normal=z(P, 3), scaling=z(P, 3), rotation=z(P, 4), opacity=z(P, 1),
-                                 base_color=z(P, 3), roughness=z(P, 1), shs=z(P, 16, 3), incidents=z(P, 16, 3), **extra)
 
 
 def test_constructor_refuses_before_touching_the_library(monkeypatch):
@@ -131,36 +122,17 @@ def test_visibility_sh_of_reads_every_form_a_model_holds_them_in():
 
 
 def test_baked_host_logic_with_a_recording_library(monkeypatch):
-    from relightable3dgaussian_amd import _lib, rasterizer_ops, relight, shading_ops
-    calls = []
-
-    class Recorder:
-        def __getattr__(self, name):
-            def fn(*args):
-                calls.append((name, args))
-                return 0
-            return fn
-
+    from relightable3dgaussian_amd import relight, shading_ops
     P, K = 7, 8
-    monkeypatch.setattr(_lib, "lib", lambda: Recorder())
-    monkeypatch.setattr(_lib, "current_stream", lambda: 0)
-    monkeypatch.setattr(shading_ops, "_c", lambda t: t.contiguous())
-    monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())
+    rec = recording_library(monkeypatch, P)
+    calls, names = rec.calls, rec.names
     traced = []
     monkeypatch.setattr(relight, "update_visibility", lambda *a, **k: traced.append("glue"))
     monkeypatch.setattr(relight, "update_visibility_device", lambda *a, **k: traced.append("device"))
     monkeypatch.setattr(shading_ops, "build_taps", lambda *a, **k: traced.append("taps"))
-
-    class _Pending:
-        def finish(self, ordering_stream=None):
-            return (3, z(1), z(3, 4, 4), z(1, 4, 4), z(1, 4, 4), z(28, 4, 4), z(3, 4, 4), z(3, 4, 4), None, z(P))
-    monkeypatch.setattr(rasterizer_ops, "rasterize_gaussians_begin", lambda *a, **k: _Pending())
     coeffs = torch.randn(P, 16, generator=torch.Generator().manual_seed(1))
     model = _model(P, visibility_dc=coeffs[:, :1, None].clone(), visibility_rest=coeffs[:, 1:, None].clone())
-    cam = types.SimpleNamespace(image_height=4, image_width=4, world_view_transform=torch.eye(4), full_proj_transform=torch.eye(4),
-                                camera_center=z(3), tanfovx=0.5, tanfovy=0.5, cx=2.0, cy=2.0)
-    env = dt(z(8, 16, 3))
-    names = lambda: [c[0] for c in calls]
+    cam, env = relight_camera(), dt(z(8, 16, 3))
 
     # construction: a snapshot of the coefficients, no trace of either kind, nothing per sample
     r = relight.RelightRenderer(model, env, K, baked_visibility=True)
@@ -195,9 +167,6 @@ def test_baked_host_logic_with_a_recording_library(monkeypatch):
 
     # the light turns: one more baked build (with the rotation), then ONE expansion in front of ONE split build; the expansion
     # is not kept
-    def rot(i):
-        a = 0.3 * i
-        return torch.tensor([[math.cos(a), -math.sin(a), 0.0], [math.sin(a), math.cos(a), 0.0], [0.0, 0.0, 1.0]])
     calls.clear()
     for i in range(1, 5):
         r.frame(cam, z(3), env_transform=rot(i))

@@ -12,7 +12,7 @@ import math
 import pytest
 import torch
 
-from tests.helpers import report
+from tests.helpers import CACHED_PATTERN, SPLIT_PATTERN, assert_frame_matches_glue, report, turning_light_frames
 from tests.test_relight_device_visibility_gpu import (TWO_PI, _COLUMNS, _IMAGES, _builder_case, _compare_frames, _envmap,  # noqa: F401
                                                       _params, _rotation, _two_kernel_path)
 
@@ -162,32 +162,20 @@ def test_turning_light_on_a_baked_renderer(K):
     cam = syn.orbit_cameras(8, width=96, height=96)[2].to(DEV)
     bg = torch.zeros(3, device=DEV)
 
-    def rot(a):
-        return torch.tensor([[math.cos(a), -math.sin(a), 0.0], [math.sin(a), math.cos(a), 0.0], [0.0, 0.0, 1.0]], device=DEV)
-    trs = [rot(0.1), rot(0.7), rot(1.3), rot(1.9)]
-    trs += [trs[-1], trs[-1]]
-    cached, split, frames = [], [], []
-    for tr in trs:
-        b.shade_out.fill_(float("nan"))
-        got = b.frame(cam, bg, env_transform=tr, outputs=("pbr_env",))
-        cached.append(b._taps_key == b._light_key)
-        split.append(bool(b._split))
-        frames.append({k: got[k].clone() for k in ("feature", "pbr_env")})
+    def per_frame(tr, got):
         assert bool(torch.isfinite(b.shade_out).all())
+    trs, cached, split, frames = turning_light_frames(b, cam, bg, per_frame)
     splits = so.split_supported(K, b.M, 32, 64, b._uniform_area)
     assert splits == (K == 20)
-    assert cached == [True, False, False, False, True, True], cached
-    assert split == ([False, True, True, True, True, True] if splits else [False] * 6), split
+    assert cached == CACHED_PATTERN, cached
+    assert split == (SPLIT_PATTERN if splits else [False] * 6), split
     assert b.tracer is None and b.incident_areas is None
     if splits:
         assert b.visibility is None and b.incident_dirs is None              # (checked before frame_reference, which fills both)
     else:
         assert tuple(b.visibility.shape) == (b.P, 18, 1) and tuple(b.incident_dirs.shape) == (b.P, 18, 3)
     for tr, got in zip(trs, frames):
-        want = relight.frame_reference(b, cam, bg, env_transform=tr, exact_activations=True)
-        for k, rtol, atol in (("feature", 1e-3, 1e-6), ("pbr_env", 0.0, 4e-4)):
-            ok, msg = report(k, got[k], want[k], rtol, atol)
-            assert ok, msg
+        assert_frame_matches_glue(b, cam, bg, tr, got)
     assert tuple(b.visibility.shape) == (b.P, K, 1) and tuple(b.incident_dirs.shape) == (b.P, K, 3)
 
 

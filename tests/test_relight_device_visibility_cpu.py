@@ -2,14 +2,14 @@
 derived ctypes signature, and the renderer's host logic against a recording library (the technique of
 tests/test_host_mirrors_cpu.py): which trace it calls with which arguments, which builder, and that no direction pointer
 reaches the per-frame kernels."""
-import contextlib
 import ctypes as C
 import math
 import os
-import types
 
 import pytest
 import torch
+
+from tests.helpers import dt, recording_library, relight_camera, relight_model, z_rotation as rot
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -32,25 +32,10 @@ def test_header_declares_the_builder_and_the_binding_follows():
 
 
 def test_device_visibility_host_logic_with_a_recording_library(monkeypatch):
-    from relightable3dgaussian_amd import _lib, rasterizer_ops, relight, shading_ops
-    calls = []
-
-    class Recorder:
-        def __getattr__(self, name):
-            def fn(*args):
-                calls.append((name, args))
-                return 0
-            return fn
-
-    class DeviceTensor(torch.Tensor):            # a CPU tensor that claims to be a device tensor
-        is_cuda = property(lambda self: True)
-
-    dt = lambda t: t.as_subclass(DeviceTensor)
+    from relightable3dgaussian_amd import relight, shading_ops
     P, K = 7, 8
-    monkeypatch.setattr(_lib, "lib", lambda: Recorder())
-    monkeypatch.setattr(_lib, "current_stream", lambda: 0)
-    monkeypatch.setattr(shading_ops, "_c", lambda t: t.contiguous())
-    monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())
+    rec = recording_library(monkeypatch, P)
+    calls, names = rec.calls, rec.names
     glue, device, taps_built = [], [], []
     monkeypatch.setattr(relight, "update_visibility", lambda *a, **k: glue.append(k) or (
         torch.ones(P, K, 1), torch.ones(P, K, 3), torch.full((P, K, 1), 2.0), None))
@@ -60,17 +45,7 @@ def test_device_visibility_host_logic_with_a_recording_library(monkeypatch):
     monkeypatch.setattr(shading_ops, "build_taps", lambda dirs, He, We, tr=None, radiance_of=None:
                         taps_built.append(tr) or torch.zeros(P * K * 3))
     z = torch.zeros
-
-    class _Pending:
-        def finish(self, ordering_stream=None):
-            return (3, z(1), z(3, 4, 4), z(1, 4, 4), z(1, 4, 4), z(28, 4, 4), z(3, 4, 4), z(3, 4, 4), None, z(P))
-    monkeypatch.setattr(rasterizer_ops, "rasterize_gaussians_begin", lambda *a, **k: _Pending())
-    model = types.SimpleNamespace(xyz=dt(z(P, 3)), normal=z(P, 3), scaling=z(P, 3), rotation=z(P, 4), opacity=z(P, 1),
-                                  base_color=z(P, 3), roughness=z(P, 1), shs=z(P, 16, 3), incidents=z(P, 16, 3))
-    cam = types.SimpleNamespace(image_height=4, image_width=4, world_view_transform=torch.eye(4), full_proj_transform=torch.eye(4),
-                                camera_center=z(3), tanfovx=0.5, tanfovy=0.5, cx=2.0, cy=2.0)
-    env = dt(z(8, 16, 3))
-    names = lambda: [c[0] for c in calls]
+    model, cam, env = relight_model(P), relight_camera(), dt(z(8, 16, 3))
 
     # the default renderer never asks for the device trace
     relight.RelightRenderer(model, env, K)
@@ -117,9 +92,6 @@ def test_device_visibility_host_logic_with_a_recording_library(monkeypatch):
 
     # the light turns: first change builds once more (with the rotation), from the second on the split transport with NULL
     # directions, and still no direction tensor
-    def rot(i):
-        a = 0.3 * i
-        return torch.tensor([[math.cos(a), -math.sin(a), 0.0], [math.sin(a), math.cos(a), 0.0], [0.0, 0.0, 1.0]])
     calls.clear()
     for i in range(1, 5):
         r.frame(cam, z(3), env_transform=rot(i))

@@ -6,7 +6,7 @@ import os
 import pytest
 import torch
 
-from tests.helpers import report
+from tests.helpers import CACHED_PATTERN, SPLIT_PATTERN, assert_frame_matches_glue, report, turning_light_frames
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -68,8 +68,8 @@ def test_a_light_that_turns_every_frame_takes_the_split_transport_and_a_stopped_
     light-INDEPENDENT half of the transport is cached once (r3dg_shade_build_split) and the per-frame kernel looks the rotated
     directions up itself (r3dg_shade_forward_split, lane = Gaussian in normal order); a light that stops gets its cache back.
     All frames equal the PyTorch-glue frame, all 19 shading columns the float64 oracle."""
-    import math
-    from relightable3dgaussian_amd import relight, shading_ops as so, synthetic as syn
+    from oracle import shading
+    from relightable3dgaussian_amd import relight, synthetic as syn
     from relightable3dgaussian_amd.bench_core import GaussianParams
     scene = syn.make_scene(P=3001, seed=5, stage2=True, scale_log_mean=-3.0)
     envmap = (3.0 * torch.rand(32, 64, 3, generator=torch.Generator().manual_seed(11)) ** 2).to(DEV)
@@ -77,19 +77,9 @@ def test_a_light_that_turns_every_frame_takes_the_split_transport_and_a_stopped_
     cam = syn.orbit_cameras(8, width=96, height=96)[2].to(DEV)
     bg = torch.zeros(3, device=DEV)
 
-    def rot(a):
-        return torch.tensor([[math.cos(a), -math.sin(a), 0.0], [math.sin(a), math.cos(a), 0.0], [0.0, 0.0, 1.0]], device=DEV)
-    trs = [rot(0.1), rot(0.7), rot(1.3), rot(1.9)]
-    trs += [trs[-1], trs[-1]]                       # the light stops: cached again from the second repeat on
-    cached, split = [], []
-    for tr in trs:
-        r.shade_out.fill_(float("nan"))
-        got = r.frame(cam, bg, env_transform=tr, outputs=("pbr_env",))
-        cached.append(r._taps_key == r._light_key)
-        split.append(bool(r._split))
+    def per_frame(tr, got):
         # the 19 shading columns against the float64 oracle (oracle/shading.py, pinned to the reference's rendering_equation and
         # EnvLight.direct_light) on the cached directions, with the tolerances of tests/test_shading_gpu.py
-        from oracle import shading
         c64 = lambda t: t.detach().double().cpu()
         ref = shading.rendering_equation(c64(r.a_base), c64(r.a_rough), c64(r.a_normal), c64(r.a_viewdirs), c64(r.incidents),
                                          c64(r.envmap), c64(r.visibility), c64(r.incident_dirs), c64(r.incident_areas), c64(tr))
@@ -102,13 +92,10 @@ def test_a_light_that_turns_every_frame_takes_the_split_transport_and_a_stopped_
             assert ok, msg
         ok, msg = report("incident_visibility", r.shade_out[:, 18:19], ref["incident_visibility"], 1e-4, 1e-6)
         assert ok, msg
-        want = relight.frame_reference(r, cam, bg, env_transform=tr, exact_activations=True)
-        # (frame_reference shades with the general HIP op: two fp32 evaluations of the ill-conditioned GGX term)
-        for k, rtol, atol in (("feature", 1e-3, 1e-6), ("pbr_env", 0.0, 4e-4)):
-            ok, msg = report(k, got[k], want[k], rtol, atol)
-            assert ok, msg
-    assert cached == [True, False, False, False, True, True], cached
-    assert split == [False, True, True, True, True, True], split         # built at the second consecutive change, kept
+        assert_frame_matches_glue(r, cam, bg, tr, got)
+    _, cached, split, _ = turning_light_frames(r, cam, bg, per_frame)
+    assert cached == CACHED_PATTERN, cached
+    assert split == SPLIT_PATTERN, split
     # the order the split kernels visit the Gaussians in: a permutation, neighbours have neighbouring normals
     perm = r._split["perm"].long()
     assert sorted(perm.tolist()) == list(range(r.P))

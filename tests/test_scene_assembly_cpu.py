@@ -250,7 +250,10 @@ def test_assemble_host_logic_with_a_recording_library(monkeypatch):
     monkeypatch.setattr(_lib, "lib", lambda: Recorder())
     monkeypatch.setattr(_lib, "current_stream", lambda: 0)
     monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())
-    monkeypatch.setattr(compose, "_upload_placement", lambda pl, device: dt(pl.clone()))
+    # (the uploads are kept: assemble drops each after its launch, and the addresses compared below are only distinct while
+    # both tensors live)
+    placed = []
+    monkeypatch.setattr(compose, "_upload_placement", lambda pl, device: placed.append(dt(pl.clone())) or placed[-1])
 
     def upload(records, device):
         uploads.append(records.path)
@@ -280,6 +283,7 @@ def test_assemble_host_logic_with_a_recording_library(monkeypatch):
     assert [a[1:3] for a in rec] == [(97, 130), (97, 130), (33, 62), (33, 62)]
     assert rec[0][3] == rec[1][3] and rec[0][4] == rec[1][4]                             # placed twice from ONE device buffer
     assert rec[0][5] is not None and rec[0][5] != rec[1][5]                              # each under its own placement
+    assert [a[5] for a in rec] == [t.data_ptr() for t in placed[:4]]
     assert [a[6] for a in rec] == [3, 3, 3, 3] and grp[4] == 1 and grp[3] is None       # no transform: no SH rotation
     dst = [t.data_ptr() for t in out.values()]
     for a in rec:
