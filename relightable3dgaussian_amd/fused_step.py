@@ -26,10 +26,10 @@ concatenates features_dc / features_rest and incidents_dc / incidents_rest every
 The parity target is the unfused path (tests/test_fused_step_gpu.py compares loss and every gradient).
 
 Beside this module: fused_adam (the one-launch Adam), fused_base (what the two iterations share), grad_comm (the data-parallel
-bucket all-reduces and their measurement), fused_stage1 (the stage-1 iteration with densification)."""
+bucket all-reduces and their measurement), fused_samples (the owner of the traced visibility, the ray set and the lookup cache
+of the P x K samples), fused_stage1 (the stage-1 iteration with densification)."""
 import collections
 import contextlib
-import math
 import os
 
 import torch
@@ -38,6 +38,7 @@ import torch.nn.functional as F
 from . import _lib, rasterizer_ops, shading_ops
 from .fused_adam import AdamGroup, FusedAdam                                              # noqa: F401  (re-exported)
 from .fused_base import _STREAMS, SUM_SLOTS, FusedStepBase, _in_context, _world_of, grad_slab, learning_rates, shared_stream  # noqa: F401
+from .fused_samples import SampleSet, of_samples
 from .fused_stage1 import FusedStage1Step                                                 # noqa: F401  (re-exported)
 from .grad_comm import BucketComm
 from .shading_ops import LEAVE_ROOM, TRAIN_OUTPUTS
@@ -183,19 +184,12 @@ class FusedStage2Step(FusedStepBase):
         # R3DG_DP_BUCKETS=1 (A/B, message size against overlap): ONE all-reduce of the whole gradient slab behind the backward
         # and one Adam launch behind it, instead of the three buckets A / C / B each sent the moment it is final
         self._single_bucket = self.dp and os.environ.get("R3DG_DP_BUCKETS", "3") == "1"
-        self.device_visibility = bool(device_visibility)
-        self.visibility_refreshes = 0               # refresh_visibility() calls so far (key of the direction-free lookup cache)
+        # the P x K samples: traced visibility, direction caches, snapshot normals, ray set and lookup cache (fused_samples)
+        # (the two traces by THIS module's names: what tests replace here reaches the owner)
+        self._samples = SampleSet(sample_num, self.M, (update_visibility, update_visibility_device), process_group, device_visibility)
         with torch.no_grad(), self._ctx:
             self.refresh_activations()
-            if self.device_visibility:
-                self._trace_on_device()
-            else:
-                self.visibility, self.incident_dirs, self.incident_areas, self.tracer = update_visibility(
-                    self.xyz, self.a_scales, self.a_rot, self.a_opacity, self.a_normal, sample_num, group=process_group)
-            # the normals the ray set was generated from (the trained normal moves on; the cached directions do not)
-            self._ray_normals = self.a_normal.clone()
-        self._taps = self._taps_key = self._taps_size = self._taps_src = self._frs_built = self._uniform_area = None
-        self._frs = None                            # shading_ops.FixedRaySet of the current direction cache, or None
+            self._samples.acquire(self.xyz, self.a_scales, self.a_rot, self.a_opacity, self.a_normal)
         # incident-light chain of a whole single-GPU iteration: (ray set, coefficient tensor, its version) the rotated coefficients
         # in the ray set were computed FROM, when that was done ahead of the next iteration; work still running on the early stream
         self._pre_rotated = None
@@ -205,6 +199,12 @@ class FusedStage2Step(FusedStepBase):
         # Adam launches of an iteration: the groups of each gradient bucket that train
         live = lambda idx: tuple(i for i in idx if self._opt_order[i] not in self.frozen)
         self._groups_a, self._groups_c, self._groups_b = live((5,)), live((0, 1, 2, 3, 4, 6, 7, 9)), live((8,))
+
+    # what tests, tools, the training loop and the benchmark read, swap and drop on the step (SampleSet.select notices)
+    visibility, incident_dirs, incident_areas, tracer, device_visibility = map(of_samples, (
+        "visibility", "incident_dirs", "incident_areas", "tracer", "device_visibility"))
+    visibility_refreshes, _ray_normals, _frs, _taps, _taps_src, _uniform_area = map(of_samples, (
+        "refreshes", "ray_normals", "frs", "taps", "src", "uniform_area"))
 
     incidents_dc = property(lambda self: self.incidents[:, :1])
     incidents_rest = property(lambda self: self.incidents[:, 1:])
@@ -257,99 +257,22 @@ class FusedStage2Step(FusedStepBase):
                 0 if zero is None else zero.numel())
         _lib.check(st, "stage2_activate")
 
-    def _frs_wanted(self):
-        """The fixed-ray-set kernels are switched on and take this K and SH degree (the texture size is asked per size: taps)."""
-        return os.environ.get("R3DG_SHADE_FRS", "1") != "0" and shading_ops.FixedRaySet.supported(self.K, self.M, 16, 32)
-
-    def _trace_on_device(self):
-        """visibility (+ the direction cache only where the general shading kernels will read it) of the CURRENT activations, by
-        train_step.update_visibility_device."""
-        self.visibility, self.incident_dirs, self.tracer = update_visibility_device(
-            self.xyz, self.a_scales, self.a_rot, self.a_opacity, self.a_normal, self.K, group=self.group,
-            want_dirs=not self._frs_wanted())
-        self.incident_areas = None if self.incident_dirs is None else torch.full(
-            (self.P, self.K, 1), 2 * math.pi, dtype=torch.float32, device=self.dev)
-
-    def _materialise_dirs(self):
-        """The direction / area caches of the snapshot normals for the general kernels, when a step that holds none meets a texture
-        size the fixed-ray-set kernels do not take (chunked like update_visibility)."""
-        from . import sampling
-        chunk = max(1, self.P // ((self.K - 1) // 24 + 1))
-        self.incident_dirs = torch.cat([sampling.fibonacci_sphere_sampling(self._ray_normals[o:o + chunk], self.K)[0]
-                                        for o in range(0, self.P, chunk)], 0)
-        self.incident_areas = torch.full((self.P, self.K, 1), 2 * math.pi, dtype=torch.float32, device=self.dev)
-
     @_in_context
     def refresh_visibility(self):
         """Re-trace the visibility with the CURRENT parameters (the reference's commented-out "Every 1000 update visibility",
         train.py:110-112), on the device path whichever way the step was constructed: deferred work is completed, the activations
         are recomputed, the P x K rays are generated from the current normals and traced, the snapshot normals are replaced and
-        the ray set / lookup cache is rebuilt for the texture size in use.  Parameters, gradients, Adam moments and step counts
-        are untouched.  Data parallel: every rank calls it at the same iteration (one all-gather inside)."""
+        the ray set / lookup cache is rebuilt for the texture size in use (SampleSet.refresh).  Parameters, gradients, Adam moments
+        and step counts are untouched.  Data parallel: every rank calls it at the same iteration (one all-gather inside)."""
         self.flush()
-        size = self._taps_size
-        with torch.no_grad():
-            self.refresh_activations()
-            self._trace_on_device()
-            self._ray_normals = self.a_normal.clone()
-        self.visibility_refreshes += 1
-        self._taps = self._taps_key = self._taps_size = self._taps_src = self._frs_built = self._frs = None
+        self.refresh_activations()
+        self._samples.refresh(self.xyz, self.a_scales, self.a_rot, self.a_opacity, self.a_normal)
         self._pre_rotated = None                    # (the rotated coefficients belonged to the old ray set)
-        if size is not None:
-            self.taps(*size)
 
     def taps(self, He, We):
-        """The per-sample lookup cache of the general shading kernels for a He x We environment texture
-        (shading_ops.build_taps: 12 bytes per sample, read beside the [P,K,3] directions) -- or None when the direction cache IS
-        the Fibonacci set of the snapshot normals and the fixed-ray-set kernels run (`self._frs`: they read neither; their own
-        8-byte records come from the ray normals, shading_ops.FixedRaySet.taps).  Decided once per visibility update / texture
-        size."""
-        # keyed by the direction tensor ITSELF (held in _taps_src for as long as its taps are: a replaced cache can then never
-        # come back at the address of the old one and pass for it) + its version counter (in-place updates).  The texture size is a
-        # key of its own: only the lookup records depend on it, the ray set (P x K directions regenerated and classified, a host
-        # read-back) does not
-        src = self.incident_dirs
-        if src is None:
-            # no direction tensor (device_visibility / refresh_visibility): the ray set IS the Fibonacci set of the snapshot
-            # normals by construction -- nothing to regenerate and compare -- and it changes exactly when the visibility is re-traced
-            dir_key, size_key = ("device", self.visibility_refreshes), (He, We)
-            if self._taps_src is not None or self._taps_key != dir_key:
-                self._taps_key, self._taps_src, self._taps_size, self._taps = dir_key, None, None, None
-                self._uniform_area = float(torch.tensor(2 * math.pi, dtype=torch.float32))
-                self._frs_built = shading_ops.FixedRaySet(self._ray_normals, self.K) if self._frs_wanted() else None
-            if self._frs_built is None or not shading_ops.FixedRaySet.supported(self.K, self.M, He, We):
-                self._materialise_dirs()            # the general kernels after all: from here on as with a cached tensor
-                return self.taps(He, We)
-            if self._taps_size != size_key:
-                self._taps_size, self._frs = size_key, self._frs_built
-                self._frs.taps(He, We)
-            return None
-        dir_key, size_key = (src._version, tuple(src.shape)), (He, We)
-        fresh = self._taps_src is not src or self._taps_key != dir_key
-        if fresh:
-            self._taps_key, self._taps_src, self._taps_size = dir_key, src, None
-            # fibonacci_sphere_sampling gives every sample the area 2 pi: then the area cache need not be read at all
-            lo, hi = float(self.incident_areas.min()), float(self.incident_areas.max())
-            self._uniform_area = lo if lo == hi else None
-            # fixed-ray-set kernels (csrc/shading_frs.hip) when the cache IS the Fibonacci set of the snapshot normals --
-            # checked here, once per visibility update -- and fits their limits; otherwise (caches handed in from elsewhere,
-            # other K, R3DG_SHADE_FRS=0) the general kernels
-            self._frs_built, self._taps = None, None
-            if (os.environ.get("R3DG_SHADE_FRS", "1") != "0" and self._uniform_area is not None and
-                    shading_ops.FixedRaySet.supported(self.K, self.M, 16, 32)):      # (K and the SH degree; the size: below)
-                self._frs_built = shading_ops.FixedRaySet.try_build(self._ray_normals, src)
-        if fresh or self._taps_size != size_key:
-            # a new texture size: new lookup records for the ray set that is already there (FixedRaySet.taps is keyed on the size
-            # itself) if the fixed-ray-set kernels take that size, the general kernels' 12-byte taps otherwise
-            self._taps_size = size_key
-            built = self._frs_built
-            self._frs = built if built is not None and shading_ops.FixedRaySet.supported(self.K, self.M, He, We) else None
-            if self._frs is None:
-                self._taps = shading_ops.build_taps(src, He, We)
-            else:
-                self._taps = None
-                self._frs.taps(He, We)
-        return self._taps
+        """SampleSet.select: the general shading kernels' lookup cache for a He x We environment texture, or None when the
+        fixed-ray-set kernels run (`_samples.frs`)."""
+        return self._samples.select(He, We)
 
     def _rotation_is_current(self):
         """The ray set already holds the rotation of the CURRENT coefficients (queued on the early-Adam stream right behind their
@@ -357,7 +280,7 @@ class FusedStage2Step(FusedStepBase):
         edits the coefficients in between (a checkpoint load, a test) invalidates it -- the Adam kernel itself writes through the raw
         pointer and does not count."""
         pr = self._pre_rotated
-        return pr is not None and pr[0] is self._frs and pr[1] is self._incidents and pr[2] == self._incidents._version
+        return pr is not None and pr[0] is self._samples.frs and pr[1] is self._incidents and pr[2] == self._incidents._version
 
     def _early_stream(self):
         """The early-Adam stream (the process's shared "early" stream), created at first use."""
@@ -368,7 +291,7 @@ class FusedStage2Step(FusedStepBase):
     def _aux_stream(self):
         """The early-Adam stream, for the side work of the fixed-ray-set path on one GPU; None without that path and under data
         parallelism (the stream then carries the buckets' waits and the coefficients are updated late, in flush())."""
-        if self._frs is None or self.dp or self.serial_streams:
+        if self._samples.frs is None or self.dp or self.serial_streams:
             return None
         return self._early_stream()
 
@@ -376,7 +299,8 @@ class FusedStage2Step(FusedStepBase):
         """The early-Adam stream when the fixed-ray-set path has Gaussians off the rotated path: their general kernels run there in
         the forward, and the rasterizer's geometry backward beside them in the backward (data-parallel runs too: the stream is
         idle during the forward, and in the backward bucket A's all-reduce is issued from it, behind the geometry backward)."""
-        if self._frs is None or self._frs.n_invalid == 0 or self.serial_streams:
+        frs = self._samples.frs
+        if frs is None or frs.n_invalid == 0 or self.serial_streams:
             return None
         return self._early_stream()
 
@@ -430,10 +354,10 @@ class FusedStage2Step(FusedStepBase):
         if aux is not None:
             _lib.stream_wait(aux, v.main)
             # (normally the previous iteration's incident-light chain left the rotated coefficients in place: _run_chain)
+            rotated_for = self._samples.frs      # (the PREVIOUS iteration's choice: this one's texture size is asked in _shade_forward)
             if not self._rotation_is_current():
                 with torch.cuda.stream(aux):
-                    self._frs.rotate(self._incidents)
-            rotated_for = self._frs
+                    rotated_for.rotate(self._incidents)
         # softplus(environment texture) (DirectLightMap.get_env) [He,We,3]: filled by the activation launch below, read by the
         # shading kernels and the texture's chain rule
         if self._env_c is None or self._env_c.shape != self.env.shape[1:]:
@@ -473,32 +397,34 @@ class FusedStage2Step(FusedStepBase):
         """Shading integral + S=16 feature rows.  -> (the general kernels' lookup cache or None, a pack kernel wrote the rows?)."""
         L = _lib.lib()
         He, We = env_c.shape[0], env_c.shape[1]
-        taps = self.taps(He, We)
-        if self._frs is not None:
-            # (taps() may have rebuilt the ray set: then it rotates itself; data parallel: flush() above ran the chain kernel)
-            rotated = rotated_for is self._frs or (self.dp and self._rotation_is_current())
-            self._frs.forward(self.a_base, self.a_rough, self.a_normal, self.a_viewdirs, self._incidents, env_c,
-                              self.visibility, self.shade_out, uniform_area=self._uniform_area,
-                              # (one workgroup per CU beside the instance ordering while THAT is the longer path: 806 vs 801
-                              # it/s without the cap, frozen geometry (run_syn4.sh) 835 vs 826.  Not under data parallelism,
-                              # where the deferred incident-light update sits in front of this kernel: 558 -> 568 it/s on one
-                              # rank without the cap)
-                              leave_room=v.order_stream is not None and not self.dp,
-                              # the few hundred Gaussians off the rotated path: their general kernel on the (idle) early-Adam
-                              # stream beside the rotation and the main kernel, joined below before the features are packed
-                              listed_stream=self._listed_stream(), rotated=rotated,
-                              feature_rows=self.features if self._direct_rows else None)
+        sm = self._samples
+        taps = sm.select(He, We)
+        frs, area = sm.frs, sm.uniform_area         # (this iteration's choice, from here on)
+        if frs is not None:
+            # (select() may have rebuilt the ray set: then it rotates itself; data parallel: flush() above ran the chain kernel)
+            rotated = rotated_for is frs or (self.dp and self._rotation_is_current())
+            frs.forward(self.a_base, self.a_rough, self.a_normal, self.a_viewdirs, self._incidents, env_c,
+                        sm.visibility, self.shade_out, uniform_area=area,
+                        # (one workgroup per CU beside the instance ordering while THAT is the longer path: 806 vs 801
+                        # it/s without the cap, frozen geometry (run_syn4.sh) 835 vs 826.  Not under data parallelism,
+                        # where the deferred incident-light update sits in front of this kernel: 558 -> 568 it/s on one
+                        # rank without the cap)
+                        leave_room=v.order_stream is not None and not self.dp,
+                        # the few hundred Gaussians off the rotated path: their general kernel on the (idle) early-Adam
+                        # stream beside the rotation and the main kernel, joined below before the features are packed
+                        listed_stream=self._listed_stream(), rotated=rotated,
+                        feature_rows=self.features if self._direct_rows else None)
         else:
             _lib.check(L.r3dg_shade_forward_cached(
                 v.raw, self.P, self.K, self.M, self.a_base.data_ptr(), self.a_rough.data_ptr(), self.a_normal.data_ptr(),
                 self.a_viewdirs.data_ptr(), self._incidents.data_ptr(), env_c.data_ptr(), He, We, None,
-                self.visibility.data_ptr(), self.incident_dirs.data_ptr(),
-                None if self._uniform_area is not None else self.incident_areas.data_ptr(), self._uniform_area or 0.0,
+                sm.visibility.data_ptr(), sm.incident_dirs.data_ptr(),
+                None if area is not None else sm.incident_areas.data_ptr(), area or 0.0,
                 taps.data_ptr(), TRAIN_OUTPUTS | (LEAVE_ROOM if v.order_stream is not None else 0),
                 self.shade_out.data_ptr()), "shade_forward")
-        if self._frs is not None and self._listed_stream() is not None:
+        if frs is not None and self._listed_stream() is not None:
             _lib.stream_wait(v.main, self._listed_stream())
-        packed = not (self._frs is not None and self._direct_rows)
+        packed = not (frs is not None and self._direct_rows)
         if packed:
             _lib.check(L.r3dg_stage2_pack_features(v.raw, self.P, self.xyz.data_ptr(), v.vm.data_ptr(), self.a_normal.data_ptr(),
                 self.a_base.data_ptr(), self.a_rough.data_ptr(), self.shade_out.data_ptr(), self.features.data_ptr(),
@@ -628,7 +554,7 @@ class FusedStage2Step(FusedStepBase):
           replaces stream 2112 bytes per Gaussian, the chain 1741.
         a_late: the chain is queued but the SH group is updated with the others in optimizer_step."""
         a_early = early_adam and bool(self._groups_a) and (handle_a is not None or not self.dp)
-        b_early = (not self.dp and self._frs is not None and v.order_stream is not None and use_bounded and
+        b_early = (not self.dp and self._samples.frs is not None and v.order_stream is not None and use_bounded and
                    (a_early or (bool(self._groups_b) and (self.P * self.K <= 40_000_000 if early_adam else chain_incidents))))
         self._early, self._b_early, self._a_late = a_early or b_early, b_early, b_early and not a_early
         if self._early:
@@ -670,7 +596,9 @@ class FusedStage2Step(FusedStepBase):
         # scale from the unpack kernel: nothing sits between that kernel and the shading backward
         if self._d_env is None or self._d_env.shape != env_c.shape:
             self._d_env = torch.zeros_like(env_c)
-        if self._frs is not None:
+        sm = self._samples
+        frs = sm.frs
+        if frs is not None:
             # the incident-light chain kernel rotates the coefficient gradient back itself: the main shading backward then
             # leaves it in the rotated frame (a frozen group: the chain is only the rotation of the coefficients)
             chain = b_early and bool(self._groups_b)
@@ -682,24 +610,24 @@ class FusedStage2Step(FusedStepBase):
             # between its arrival and the shading forward.  Whole iterations only (`chain_incidents`).
             dp_chain = (self.dp and chain_incidents and bool(self._groups_b) and not self._single_bucket
                         and os.environ.get("R3DG_DP_CHAIN", "1") != "0")
-            d_base, d_rough, d_view, _d_inc, d_env = self._frs.backward(
-                self.a_base, self.a_rough, self.a_normal, self.a_viewdirs, self._incidents, env_c, self.visibility,
-                self.d_pbr, self.d_diffuse, uniform_area=self._uniform_area,
-                out_incidents=self._frs.dcprime_rows() if dp_chain else gr["incidents"], out_env=self._d_env,
+            d_base, d_rough, d_view, _d_inc, d_env = frs.backward(
+                self.a_base, self.a_rough, self.a_normal, self.a_viewdirs, self._incidents, env_c, sm.visibility,
+                self.d_pbr, self.d_diffuse, uniform_area=sm.uniform_area,
+                out_incidents=frs.dcprime_rows() if dp_chain else gr["incidents"], out_env=self._d_env,
                 block_absmax=self._absmax,
                 # whole iterations: the rotation back of the coefficient gradient goes to the stream that already carries the
                 # SH group's early Adam (optimizer_step joins it before any Adam launch reads the gradient; under data
                 # parallelism bucket B's all-reduce is issued from it) and runs beside the activation chain rule
                 rotate_stream=self._adam_stream if self._early else None, rotation_back=not (chain or dp_chain))
-            self._dp_chain = self._frs if dp_chain else None
+            self._dp_chain = frs if dp_chain else None
             if b_early:
                 # optimizer_step queues the chain BEHIND the other groups' Adam.  Both are HBM streams; side by side the
                 # activation chain rule + that Adam -- which the whole front end of the next iteration waits for -- took 68 + 45
                 # us instead of 20 + 40, while the chain only gates the shading forward (801-806 vs 793-796 it/s, HISTORY.md)
-                self._chain_deferred = (self._frs, self._skip_cur, self.opt.step_count)
+                self._chain_deferred = (frs, self._skip_cur, self.opt.step_count)
         else:
             d_base, d_rough, d_view, _d_inc, d_env = shading_ops.shade_backward(self.a_base, self.a_rough, self.a_normal,
-                self.a_viewdirs, self._incidents, env_c, self.visibility, self.incident_dirs, self.incident_areas, self.d_pbr,
+                self.a_viewdirs, self._incidents, env_c, sm.visibility, sm.incident_dirs, sm.incident_areas, self.d_pbr,
                 self.d_diffuse, out_incidents=gr["incidents"], taps=taps, out_env=self._d_env, block_absmax=self._absmax)
         if geo_stream is not None:                                       # join the geometry backward (and nothing
             v.main.wait_event(self._geo_done)       # queued behind it on that stream)

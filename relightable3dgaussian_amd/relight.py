@@ -110,11 +110,7 @@ class _Samples:
 
     def directions(self, r):
         if self.incident_dirs is None:      # in the chunks of update_visibility: a transient of about three chunks
-            dirs = torch.empty(r.P, r.K, 3, dtype=torch.float32, device=r.dev)
-            chunk = max(1, r.P // ((r.K - 1) // 24 + 1))
-            for off in range(0, r.P, chunk):
-                dirs[off:off + chunk] = sampling.fibonacci_sphere_sampling(r.a_normal[off:off + chunk], r.K)[0]
-            self.incident_dirs = dirs
+            self.incident_dirs = sampling.fibonacci_directions(r.a_normal, r.K)[0]
         return self.incident_dirs
 
 

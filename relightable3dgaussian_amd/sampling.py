@@ -36,3 +36,19 @@ def fibonacci_sphere_sampling(normals, sample_num):
     dirs = F.normalize(dirs, dim=-2).transpose(-1, -2).contiguous()
     areas = torch.ones_like(dirs[..., 0:1]) * 2 * math.pi
     return dirs, areas
+
+
+def direction_chunk(P, sample_num):
+    """Rows per chunk of everything that walks the P x K samples as the reference does (gaussian_model.py:312-342)."""
+    return max(1, P // ((sample_num - 1) // 24 + 1))
+
+
+def fibonacci_directions(normals, sample_num, want_areas=False):
+    """fibonacci_sphere_sampling of all P normals -> ([P,K,3] directions, [P,K,1] areas or None), in chunks of direction_chunk
+    rows written into a preallocated result: the transient is one chunk's.  The areas are that function's: 2 pi to all."""
+    P = normals.shape[0]
+    dirs = normals.new_empty(P, sample_num, 3)
+    chunk = direction_chunk(P, sample_num)
+    for off in range(0, P, chunk):
+        dirs[off:off + chunk] = fibonacci_sphere_sampling(normals[off:off + chunk], sample_num)[0]
+    return dirs, normals.new_full((P, sample_num, 1), 2 * math.pi) if want_areas else None

@@ -31,7 +31,7 @@ def inverse_covariance(scales, rotations):
 @torch.no_grad()
 def update_visibility(xyz, scales, rotations, opacity, normal, sample_num, group=None, tracer_cls=None):
     """-> (visibility[P,K,1], incident_dirs[P,K,3], incident_areas[P,K,1], tracer); chunked like the reference
-    (chunk = P // ((K-1)//24 + 1)) so the transient [chunk,K,3] ray tensors stay bounded.
+    (sampling.direction_chunk) so the transient [chunk,K,3] ray tensors stay bounded.
 
     Data parallel: with an initialised process group of W > 1 ranks every rank builds the same BVH
     (replicated, deterministic), traces only ITS contiguous block of ceil(P/W) ray bundles (of the Morton-ordered bundle
@@ -51,18 +51,13 @@ def update_visibility(xyz, scales, rotations, opacity, normal, sample_num, group
     P = xyz.shape[0]
     per = -(-P // world)                                   # rows per rank (the last block may be short or empty)
     lo, hi = min(P, rank * per), min(P, (rank + 1) * per)
-    chunk = max(1, P // ((sample_num - 1) // 24 + 1))
+    chunk = sampling.direction_chunk(P, sample_num)
     # The bundles are traced in MORTON order of their origin Gaussian (the leaf order of the tree just built): consecutive
     # ray blocks then start next to each other and walk the same subtrees, which is what the trace kernel's per-XCD L2s
     # need (csrc/bvh_trace.hip).  Results are scattered back to the caller's order; values are those of any other order.
     order = getattr(tracer, "tree", None)
     order = order[P - 1:, 3].long() if (order is not None and P > 1) else torch.arange(P, device=xyz.device)
-    dirs_all, areas_all = [], []
-    for off in range(0, P, chunk):
-        dirs, areas = sampling.fibonacci_sphere_sampling(normal[off:off + chunk], sample_num)
-        dirs_all.append(dirs)
-        areas_all.append(areas)
-    dirs_all, areas_all = torch.cat(dirs_all, 0), torch.cat(areas_all, 0)
+    dirs_all, areas_all = sampling.fibonacci_directions(normal, sample_num, want_areas=True)
     mine = order[lo:hi]                                        # this rank's share of the Morton-ordered bundles
     vis_mine = torch.empty(mine.numel(), sample_num, 1, dtype=torch.float32, device=xyz.device)
     for a in range(0, mine.numel(), chunk):
@@ -116,8 +111,8 @@ def update_visibility_device(xyz, scales, rotations, opacity, normal, sample_num
     tracer._records_key = tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in arrays)
     zsamples = sampling.fibonacci_z_samples(K, dev)[0].t().contiguous()                    # [K,3]
     vis = torch.empty(P, K, 1, dtype=torch.float32, device=dev)
-    dirs = torch.empty(P, K, 3, dtype=torch.float32, device=dev) if want_dirs else None
     if not gather:
+        dirs = torch.empty(P, K, 3, dtype=torch.float32, device=dev) if want_dirs else None
         bvh_ops.trace_bundles(records, tracer.tree, zsamples, vis, 0, P, dirs_out=dirs)
         return vis, dirs, tracer
     per = -(-P // world)
@@ -129,11 +124,7 @@ def update_visibility_device(xyz, scales, rotations, opacity, normal, sample_num
     gathered = torch.empty(world * per, K, 1, dtype=torch.float32, device=dev)
     dist.all_gather(list(gathered.view(world, per, K, 1).unbind(0)), padded, group=group)
     vis[order] = gathered[:P]
-    if want_dirs:
-        chunk = max(1, P // ((K - 1) // 24 + 1))
-        for off in range(0, P, chunk):
-            dirs[off:off + chunk] = sampling.fibonacci_sphere_sampling(normal[off:off + chunk], K)[0]
-    return vis, dirs, tracer
+    return vis, sampling.fibonacci_directions(normal, K)[0] if want_dirs else None, tracer
 
 
 LAMBDA_DSSIM = 0.2          # arguments/__init__.py:125

@@ -188,8 +188,8 @@ def stage_args(case, fwd_ref, d_mean2D, d_conic, d_colors):
 
 
 # ---- the recording library of the relight CPU tests (tests/test_host_mirrors_cpu.py, tests/test_relight_device_visibility_cpu.py,
-# tests/test_relight_baked_cpu.py, tests/test_relight_call_sequences_cpu.py): RelightRenderer's host side with every C-ABI entry
-# point replaced by a recorder, so that nothing runs on a GPU -----------------------------------------------------------------
+# tests/test_relight_baked_cpu.py, tests/test_relight_call_sequences_cpu.py) and of tests/test_fused_samples_call_sequences_cpu.py:
+# the host side of a renderer or a step with every C-ABI entry point replaced by a recorder, so that nothing runs on a GPU -----------------------------------------------------------------
 class DeviceTensor(torch.Tensor):            # a CPU tensor that claims to be a device tensor
     is_cuda = property(lambda self: True)
 
@@ -200,15 +200,17 @@ def dt(t):
 
 class Recorder:
     """Stands for the loaded library: every entry point appends (name, args) -- or what `convert(name, args)` makes of them --
-    to `calls` and returns 0.  `wanted` collects the `want_weights` of every rasterizer front end the fake below stood in for."""
+    to `calls` and returns 0 (or `returns[name]`).  `wanted` collects the `want_weights` of every rasterizer front end the fake
+    below stood in for."""
 
-    def __init__(self, convert=None):
+    def __init__(self, convert=None, returns=None):
         self.calls, self.wanted, self.convert = [], [], convert or (lambda name, args: (name, args))
+        self.returns = returns or {}
 
     def __getattr__(self, name):
         def fn(*args):
             self.calls.append(self.convert(name, args))
-            return 0
+            return self.returns.get(name, 0)
         return fn
 
     def names(self):
@@ -229,12 +231,12 @@ class FakePending:
         return (3, z(1), z(3, 4, 4), z(1, 4, 4), z(1, 4, 4), z(28, 4, 4), z(3, 4, 4), z(3, 4, 4), None, z(self.P))
 
 
-def recording_library(monkeypatch, P, convert=None):
+def recording_library(monkeypatch, P, convert=None, returns=None):
     """Puts a Recorder in the place of the library for the rest of the test and makes the host code around it run on CPU
     tensors (the renderer's own buffers are CPU tensors here); the rasterizer front end returns a FakePending."""
     import contextlib
     from relightable3dgaussian_amd import _lib, rasterizer_ops, shading_ops
-    rec = Recorder(convert)
+    rec = Recorder(convert, returns)
     monkeypatch.setattr(_lib, "lib", lambda: rec)
     monkeypatch.setattr(_lib, "current_stream", lambda: 0)
     monkeypatch.setattr(shading_ops, "_c", lambda t: t.contiguous())
