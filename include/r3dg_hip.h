@@ -797,6 +797,17 @@ int r3dg_scene_pack_records(void* stream, int P, int columns, void** src_groups,
  *   NaN quantises to 0.  The driver copies d_bytes asynchronously into its ring of pinned host buffers. */
 int r3dg_relight_quantize(void* stream, int width, int height, int channels, const float* d_image, uint8_t* d_bytes);
 
+/* r3dg_view_unpack: one ground-truth view of the device view store, d_pixels [H,W,C] uint8 as the image file holds them (C = 4:
+ *   RGBA, C = 3: RGB) -> d_image [3,H,W] float composited onto d_background (3 floats on the device) and d_mask [1,H,W] float (the
+ *   alpha channel; ones for C = 3; NULL: not wanted), bit for bit what the reference's reader makes of the file
+ *   (scene/utils.py:47-48, dataset_readers.py:246-249, camera_utils.py:35,56, cameras.py:34): u = byte / 255 and a = alpha / 255 in
+ *   float64, x = u * a + bg * (1 - a) in float64 with every operation rounded on its own, x rounded to float32 and clamped to
+ *   [0,1]; mask = (float)a.  One launch, flat over the H*W pixels (a lane = 4 consecutive pixels: one 16-byte load, one 16-byte
+ *   store per plane); pointers that are not 16-byte aligned (4-byte for RGB pixels) take narrower accesses; nothing outside the
+ *   three arrays is read or written.  Nothing synchronises; no atomics.  Same size limits as r3dg_relight_quantize. */
+int r3dg_view_unpack(void* stream, int width, int height, int channels, const uint8_t* d_pixels, const float* d_background,
+                     float* d_image, float* d_mask);
+
 /* ---- densification bookkeeping -------------------------------------------------------------------
  * r3dg_densify_accumulate: GaussianModel.add_densification_stats (scene/gaussian_model.py:931-937) + the max-radii
  *   update of train.py:164-165, one pass.  The visibility filter is radii > 0 (render.py / neilf.py `visibility_filter`).

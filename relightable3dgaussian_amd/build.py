@@ -36,6 +36,7 @@ EXTRA = {
     "bvh_trace.hip": BVH_FLAGS,
     "simple_knn.hip": ["-ffp-contract=off"],
     "densify.hip": ["-ffp-contract=off"],         # clone / split / prune decisions are fp32 comparisons
+    "view_store.hip": ["-ffp-contract=off"],      # the reader's float64 composite, every operation rounded on its own
     "shading.hip": SHADING_FLAGS,
     "shading_frs.hip": SHADING_FLAGS,
     "shading_relight.hip": SHADING_FLAGS,

@@ -1,5 +1,6 @@
-// C ABI of the scene assembly (include/r3dg_hip.h): PLY records <-> parameter groups, objects into a composite, and the 8-bit
-// quantisation of a frame.  Set-up and output paths, outside the per-stage timing of a training iteration or a relight frame.
+// C ABI of the scene assembly (include/r3dg_hip.h): PLY records <-> parameter groups, objects into a composite, the 8-bit
+// quantisation of a frame, and its counterpart on the input side, the unpacking of a stored 8-bit ground-truth view.  Set-up,
+// input and output paths, outside the per-stage timing of a training iteration or a relight frame.
 #include "capi_internal.hpp"
 
 using namespace r3dg;
@@ -86,6 +87,19 @@ int r3dg_relight_quantize(void* stream_, int width, int height, int channels, co
     if (!image || !bytes) return invalid("relight_quantize: null buffer");
     return guarded([&]() -> int {
         launch_relight_quantize((hipStream_t)stream_, width, height, channels, image, bytes);
+        return R3DG_OK;
+    });
+}
+
+int r3dg_view_unpack(void* stream_, int width, int height, int channels, const uint8_t* pixels, const float* background,
+                     float* image, float* mask)
+{
+    if (width < 0 || height < 0 || (channels != 3 && channels != 4)) return invalid("view_unpack: bad shape (3 or 4 channels)");
+    if ((long long)width * height == 0) return R3DG_OK;
+    if ((long long)width * height >= (1ll << 31)) return invalid("view_unpack: image too large");
+    if (!pixels || !background || !image) return invalid("view_unpack: null buffer");
+    return guarded([&]() -> int {
+        launch_view_unpack((hipStream_t)stream_, width, height, channels, pixels, background, image, mask);
         return R3DG_OK;
     });
 }

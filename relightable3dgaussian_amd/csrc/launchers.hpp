@@ -230,6 +230,9 @@ void launch_scene_place_groups(hipStream_t s, int P, const SceneGroups& src, con
                                long long row_offset, const SceneGroups& dst);
 void launch_scene_pack_records(hipStream_t s, int P, int columns, const SceneGroups& src, float* records);
 void launch_relight_quantize(hipStream_t s, int W, int H, int C, const float* image, uint8_t* bytes);
+// view_store.hip: 8-bit pixels [H,W,C] of a stored ground-truth view -> image [3,H,W] over the background + mask [1,H,W] (or NULL)
+void launch_view_unpack(hipStream_t s, int W, int H, int C, const uint8_t* pixels, const float* background, float* image,
+                        float* mask);
 // ssim.hip: the value-only SSIM tiling; tile_sums [C * ceil(W/32) * ceil(H/32)][2]
 void launch_eval_metric_tiles(hipStream_t s, int W, int H, int C, const float* pred, const float* gt, const float* mask,
                               const float* fill, int fill_is_image, double* tile_sums);

@@ -8,8 +8,9 @@ Stage 2 (`train_stage2`): the fused stage-2 iteration with the per-group rates o
 DirectLightMap.training_setup and, optionally, a periodic re-trace of the visibility on the device -- the hook the reference
 keeps commented out (train.py:110-112, "Every 1000 update visibility").
 
-Only what the hot path needs: no dataset readers, logging, checkpoints or evaluation -- cameras and ground-truth images
-are whatever the caller hands in (synthetic.py in the tests and tools).  Data parallel: every rank runs this loop on its
+Only what the hot path needs: no dataset readers, logging, checkpoints or evaluation here -- cameras and ground-truth images
+are whatever the caller hands in (synthetic.py in the tests and tools; dataset.ViewStore's lazy sequences in training.py, the
+driver that reads a Blender-format dataset directory and writes the reference's checkpoints).  Data parallel: every rank runs this loop on its
 own view shard; gradients and densification statistics are reduced inside FusedStage1Step, and the split's random
 table comes from a generator seeded identically on all ranks, so the replicas stay identical.
 """
@@ -81,9 +82,10 @@ def create_from_points(points, colors, normals=None, device="cuda"):
 
 def train_stage1(init, cameras, images, background, extent, schedule=None, iterations=None, seed=0,
                  white_background=True, process_group=None, on_iteration=None, masks=None, loss_weights=None,
-                 poll_interval=32, replay_dropped=True):
+                 poll_interval=32, replay_dropped=True, view_order=None):
     """Runs `iterations` fused stage-1 iterations over the (camera, image) pairs in round-robin order (the reference
-    draws a random permutation, train.py:115-119; the order is the caller's) with the reference's densification
+    draws a random permutation, train.py:115-119: `view_order`, a callable iteration -> view index, e.g.
+    dataset.reference_view_order; None = round robin) with the reference's densification
     schedule.  Returns (FusedStage1Step, history) where history lists (iteration, event, rows) for every
     densify / reset.  The objective is the reference's stage-1 loss with the lambdas of script/run_nerf.sh:7-14
     (train_step.STAGE1_WEIGHTS; `loss_weights` overrides them); `masks[v]` [1,H,W] is view v's object mask
@@ -119,7 +121,7 @@ def train_stage1(init, cameras, images, background, extent, schedule=None, itera
         # gaussians.update_learning_rate(iteration) (train.py:101): the position rate decays log-linearly
         xyz_group["lr"] = position_lr(it, sch.position_lr_init * extent, sch.position_lr_final * extent,
                                       sch.position_lr_delay_mult, sch.position_lr_max_steps)
-        v = (it - 1) % len(cameras)
+        v = (it - 1) % len(cameras) if view_order is None else int(view_order(it))
         collecting = it < sch.densify_until_iter
         if not collecting and step.stats is not None:
             step.stats = None                                                # train.py:160: statistics only while densifying
@@ -201,10 +203,21 @@ def visibility_refresh_iterations(iterations, visibility_interval):
     return list(range(visibility_interval, iterations + 1, visibility_interval))
 
 
+def stage2_position_lr(schedule, extent, iteration, first_iteration=0, scale=1.0):
+    """The xyz rate train_stage2 sets for its iteration `iteration` (1-based): `scale` x position_lr(first_iteration + iteration).
+    The reference's stage 2 continues the count of the checkpoint it starts from (train.py:37,97-101: iterations 30001..40000,
+    where the decay has reached position_lr_final); first_iteration = 0 restarts the decay from position_lr_init."""
+    sch = schedule
+    return scale * position_lr(first_iteration + iteration, sch.position_lr_init * extent, sch.position_lr_final * extent,
+                               sch.position_lr_delay_mult, sch.position_lr_max_steps)
+
+
 def train_stage2(restored_or_params, cameras, images, background, extent, sample_num, schedule=None, iterations=None,
                  visibility_interval=0, masks=None, loss_weights=None, lrs=None, process_group=None, on_iteration=None,
-                 poll_interval=32):
-    """Runs `iterations` fused stage-2 iterations over the (camera, image) pairs in round-robin order.  Returns
+                 poll_interval=32, view_order=None, first_iteration=0):
+    """Runs `iterations` fused stage-2 iterations over the (camera, image) pairs in round-robin order (`view_order`: a callable
+    iteration -> view index instead, as in train_stage1; `first_iteration`: the iteration count of the checkpoint the run starts
+    from, which only moves the xyz rate along its decay -- stage2_position_lr; `on_iteration` still counts from 1).  Returns
     (FusedStage2Step, history).  `restored_or_params`: the raw parameters of a stage-2 model -- checkpoint.restore(..., pbr=True)
     with an `env` texture [1,He,We,3] added, or a bench_core.GaussianParams.  `sample_num`: rays per Gaussian.
     Learning rates: stage2_learning_rates(schedule, extent) under the caller's `lrs` (the frozen-geometry scripts pass zeros:
@@ -228,9 +241,8 @@ def train_stage2(restored_or_params, cameras, images, background, extent, sample
     for it in range(1, n_iter + 1):
         if "xyz" not in step.frozen:
             # (a caller's own xyz rate scales the whole decay curve)
-            xyz_group["lr"] = xyz_scale * position_lr(it, sch.position_lr_init * extent, sch.position_lr_final * extent,
-                                                      sch.position_lr_delay_mult, sch.position_lr_max_steps)
-        v = (it - 1) % len(cameras)
+            xyz_group["lr"] = stage2_position_lr(sch, extent, it, first_iteration, xyz_scale)
+        v = (it - 1) % len(cameras) if view_order is None else int(view_order(it))
         step(cameras[v], background, images[v], image_mask=None if masks is None else masks[v])
         if (poll_interval and it % poll_interval == 0) or it == n_iter:
             dropped = step.poll_overflow()
