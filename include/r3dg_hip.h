@@ -391,12 +391,19 @@ int r3dg_shade_frs_backward(void* stream, int P, int K, const float* d_base_colo
  * their rows of d_dcprime instead of d_dL_dincidents -- for a caller that handed d_dcprime to r3dg_shade_frs_backward as
  * d_dL_dincidents too, so that ONE [P,48] buffer holds the whole coefficient gradient (rotated frame on the rotated path, world
  * frame off it) and can be summed over ranks as it is: the rotation is linear and the same on every rank (data-parallel
- * iterations, round 6: grad_scale = 1 / world). */
+ * iterations, round 6: grad_scale = 1 / world).  The last argument is a set of R3DG_CHAIN_* bits; LISTED_ROWS_IN_DCPRIME is 1,
+ * what callers passed for "true" before there were two.
+ * R3DG_CHAIN_NO_GRADIENT_OUT: the world-frame gradient row is NOT written to d_dL_dincidents (192 of the pass's 1728 bytes per
+ * Gaussian) -- for a caller whose gradient has no reader behind the update, e.g. a whole single-GPU iteration.  Parameters,
+ * moments and d_cprime are bit for bit the same; d_dL_dincidents is then only READ, on the rows of the Gaussians off the
+ * rotated path (unless those are in d_dcprime), and keeps whatever it held everywhere else. */
 #define R3DG_SHADE_NO_ROTATION_BACK ((void*)(intptr_t)-1)
+#define R3DG_CHAIN_LISTED_ROWS_IN_DCPRIME 1
+#define R3DG_CHAIN_NO_GRADIENT_OUT 2
 int r3dg_shade_frs_incident_chain(void* stream, int P, const float* d_ray_normals, const uint8_t* d_valid,
                                   const float* d_dcprime, float* d_dL_dincidents, float* d_incidents, float* d_exp_avg,
                                   float* d_exp_avg_sq, float* d_cprime, float lr, float lr_tail, float beta1, float beta2,
-                                  float eps, int step, float grad_scale, const float* d_skip_flag, int listed_rows_in_dcprime);
+                                  float eps, int step, float grad_scale, const float* d_skip_flag, int chain_flags);
 /*   Launch order on `stream`: the kernel on the listed Gaussians, then the main kernel (a caller that has other work
  *   running on another stream when it calls this gets the small launch beside that work).
  *   rotate_stream: NULL, or a second stream for the rotation of the coefficient gradient back to d_dL_dincidents (ordered after the
@@ -695,6 +702,35 @@ typedef struct r3dg_adam_group {
 } r3dg_adam_group;
 int r3dg_adam_step(void* stream, int n_groups, const r3dg_adam_group* groups, float beta1, float beta2, float eps,
                    int step, float grad_scale, const float* d_skip_flag);
+
+/* r3dg_rasterize_backward_split whose per-Gaussian geometry backward applies the Adam step of the SH colour group ITSELF
+ * (whole single-GPU training iterations): `sh_adam` describes the group -- param == d_shs ([P,M,3], n = 3 M P), both moments,
+ * lr / lr_tail / period / split as for r3dg_adam_step; its `grad` is not read -- and step, betas, eps, grad_scale and
+ * d_skip_flag mean what they mean there.  The gradient rows, which that kernel holds in on-chip memory, are consumed where they
+ * are: d_dL_dsh is NOT written (it may be NULL) and no r3dg_adam_step launch reads it and the parameter row again -- per Gaussian
+ * 3 x 12 M bytes less through device memory and one launch less.  Parameters and moments come out bit for bit as from
+ * r3dg_rasterize_backward_split followed by r3dg_adam_step on the one group (the same update statements, compiled with the
+ * same flags); Gaussians outside the view take part with a zero gradient, as there; every other output is what
+ * r3dg_rasterize_backward_split writes, also when *d_skip_flag != 0 (then parameters and moments are left untouched).  d_shs
+ * and the moments are final only after joining geometry_stream.  Needs SH input (d_colors_precomp == NULL), 16-byte aligned
+ * arrays and r3dg_rasterize_backward_sh_adam_supported(M) == 1 (M a multiple of 4 up to 16 while R3DG_OPT_STAGE_SH_ROWS is
+ * on); R3DG_EINVAL otherwise -- there is no fallback. */
+int r3dg_rasterize_backward_sh_adam_supported(int M);
+int r3dg_rasterize_backward_split_sh_adam(void* stream, void* geometry_stream, int P, int S, int D, int M, int R,
+                                          const float* d_background, int width, int height, const float* d_means3D,
+                                          const float* d_shs, const float* d_features, const float* d_colors_precomp,
+                                          const float* d_scales, float scale_modifier, const float* d_rotations,
+                                          const float* d_cov3D_precomp, const float* d_viewmatrix,
+                                          const float* d_projmatrix, const float* d_campos, float tan_fovx, float tan_fovy,
+                                          const int32_t* d_radii, const void* d_geom_buffer, const void* d_binning_buffer,
+                                          const void* d_img_buffer, const float* d_dL_dpix, const float* d_dL_dpix_o,
+                                          const float* d_dL_dpix_d, const float* d_dL_dpix_f, float* d_dL_dmean2D,
+                                          float* d_dL_dconic, float* d_dL_dopacity, float* d_dL_dcolor,
+                                          float* d_dL_dfeature, float* d_dL_dmean3D, float* d_dL_dcov3D, float* d_dL_dsh,
+                                          float* d_dL_dscale, float* d_dL_drot, int backward_geometry, int debug,
+                                          int n_active_features, const int* active_features,
+                                          const r3dg_adam_group* sh_adam, float beta1, float beta2, float eps, int step,
+                                          float grad_scale, const float* d_skip_flag);
 
 /* ---- relight / eval frame glue (relighting.py:114-170 -> gaussian_renderer/neilf.py:74-209 with is_training=False) -----
  * r3dg_relight_pack_features: the S=28 eval feature row (neilf.py:124-130) from the activated parameters and the 19

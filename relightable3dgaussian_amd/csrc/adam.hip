@@ -1,6 +1,7 @@
 // Multi-group Adam step: all parameter groups in one launch (gaussian_model.py:465-497).
 #include <cmath>
 
+#include "adam_update.hpp"
 #include "launchers.hpp"
 #include "r3dg_hip.h"
 
@@ -21,33 +22,8 @@ struct AdamTable {
 #ifndef R3DG_ADAM_UNROLL
 #define R3DG_ADAM_UNROLL 1
 #endif
-#ifndef R3DG_ADAM_NT
-#define R3DG_ADAM_NT 1              // the moments are read and written ONCE per iteration: nontemporal accesses
-#endif
 constexpr int ADAM_UNROLL = R3DG_ADAM_UNROLL;
 constexpr int ADAM_BLOCK_FLOATS = 1024 * ADAM_UNROLL;
-
-__device__ __forceinline__ float4 adam_load(const float* p, bool nt)
-{
-    if (nt && R3DG_ADAM_NT) {
-        const float4* q = reinterpret_cast<const float4*>(p);
-        return make_float4(__builtin_nontemporal_load(&q->x), __builtin_nontemporal_load(&q->y), __builtin_nontemporal_load(&q->z),
-                           __builtin_nontemporal_load(&q->w));
-    }
-    return *reinterpret_cast<const float4*>(p);
-}
-__device__ __forceinline__ void adam_store(float* p, const float (&v)[4], bool nt)
-{
-    if (nt && R3DG_ADAM_NT) {
-        float4* q = reinterpret_cast<float4*>(p);
-        __builtin_nontemporal_store(v[0], &q->x);
-        __builtin_nontemporal_store(v[1], &q->y);
-        __builtin_nontemporal_store(v[2], &q->z);
-        __builtin_nontemporal_store(v[3], &q->w);
-        return;
-    }
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
 
 __global__ void __launch_bounds__(256)
 adam_kernel(AdamTable t, float beta1, float beta2, float eps, float bias1, float inv_sqrt_bias2, float grad_scale,
@@ -86,15 +62,9 @@ adam_kernel(AdamTable t, float beta1, float beta2, float eps, float bias1, float
         if (base >= grp.n) continue;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            // two learning rates per group: elements whose index modulo `period` is below `split` use lr, the rest lr_tail
-            // (one [P,16,3] SH tensor = dc columns + rest columns with different rates, gaussian_model.py:470-471)
-            float lr = grp.lr;
-            if (grp.period != 0 && ((unsigned int)(base + k) % grp.period) >= grp.split) lr = grp.lr_tail;   // n < 2^32
-            float gk = gv[u][k] * grad_scale;                  // e.g. 1 / world_size after a sum all-reduce
-            mv[u][k] = mv[u][k] + (gk - mv[u][k]) * (1.f - beta1);
-            vv[u][k] = beta2 * vv[u][k] + (1.f - beta2) * gk * gk;
-            const float denom = sqrtf(vv[u][k]) * inv_sqrt_bias2 + eps;
-            pv[u][k] -= (lr / bias1) * (mv[u][k] / denom);
+            // (the rate by column and the update itself: adam_update.hpp, shared with the projection backward's fused variant)
+            const float lr = adam_rate((unsigned int)(base + k), grp.lr, grp.lr_tail, grp.period, grp.split);   // n < 2^32
+            adam_update(pv[u][k], gv[u][k], mv[u][k], vv[u][k], lr, beta1, beta2, eps, bias1, inv_sqrt_bias2, grad_scale);
         }
         if (base + 4 <= grp.n) {
             *reinterpret_cast<float4*>(p + base) = *reinterpret_cast<float4*>(pv[u]);
@@ -105,6 +75,12 @@ adam_kernel(AdamTable t, float beta1, float beta2, float eps, float bias1, float
                 if (base + k < grp.n) { p[base + k] = pv[u][k]; m[base + k] = mv[u][k]; v[base + k] = vv[u][k]; }
         }
     }
+}
+
+AdamBias adam_bias(float beta1, float beta2, int step)
+{
+    const double b1 = 1.0 - pow((double)beta1, (double)step), b2 = 1.0 - pow((double)beta2, (double)step);
+    return {(float)b1, (float)(1.0 / sqrt(b2))};
 }
 
 void launch_adam(hipStream_t s, int n_groups, const r3dg_adam_group* groups, float beta1, float beta2, float eps,
@@ -120,8 +96,8 @@ void launch_adam(hipStream_t s, int n_groups, const r3dg_adam_group* groups, flo
     }
     t.first_block[n_groups] = blocks;
     if (blocks == 0) return;
-    const double b1 = 1.0 - pow((double)beta1, (double)step), b2 = 1.0 - pow((double)beta2, (double)step);
-    adam_kernel<<<blocks, 256, 0, s>>>(t, beta1, beta2, eps, (float)b1, (float)(1.0 / sqrt(b2)), grad_scale, skip_flag);
+    const AdamBias b = adam_bias(beta1, beta2, step);
+    adam_kernel<<<blocks, 256, 0, s>>>(t, beta1, beta2, eps, b.bias1, b.inv_sqrt_bias2, grad_scale, skip_flag);
     check_launch(s, false, "adam_kernel");
 }
 

@@ -1,6 +1,7 @@
 // C ABI of the rasterizer (include/r3dg_hip.h): state-buffer layouts, orchestration of the forward (one call, two-phase or
 // bounded) and of the backward.  Mirrors CudaRasterizer::Rasterizer::forward/backward (rasterizer_impl.cu:199-380, :384-491)
 // in the order of work, not in code.
+#include "adam_update.hpp"
 #include "capi_internal.hpp"
 
 #include <mutex>
@@ -534,7 +535,9 @@ static int check_active_features(const char* name, int n, const int* list, int S
     return R3DG_OK;
 }
 
-int r3dg_rasterize_backward_split(void* stream_, void* geometry_stream_, int P, int S, int D, int M, int R,
+// the backward behind r3dg_rasterize_backward_split and _split_sh_adam (`adam` != nullptr: the geometry kernel applies the SH
+// colour group's Adam and does not write dL_dsh)
+static int backward_split_impl(void* stream_, void* geometry_stream_, int P, int S, int D, int M, int R,
                                   const float* background, int width, int height, const float* means3D,
                                   const float* shs, const float* features, const float* colors_precomp,
                                   const float* scales, float scale_modifier, const float* rotations,
@@ -545,7 +548,8 @@ int r3dg_rasterize_backward_split(void* stream_, void* geometry_stream_, int P, 
                                   const float* dL_dpix_f, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
                                   float* dL_dcolor, float* dL_dfeature, float* dL_dmean3D, float* dL_dcov3D,
                                   float* dL_dsh, float* dL_dscale, float* dL_drot, int backward_geometry, int debug_,
-                                  int n_active_features, const int* active_features)
+                                  int n_active_features, const int* active_features,
+                                  const ShAdamArgs* adam)
 {
     if (P < 0 || width <= 0 || height <= 0 || R < 0) return invalid("rasterize_backward: bad P/R/width/height");
     if (S < 0 || S > R3DG_MAX_S_BWD) return invalid("rasterize_backward: feature channels S must be in [0,36]");
@@ -597,12 +601,69 @@ int r3dg_rasterize_backward_split(void* stream_, void* geometry_stream_, int P, 
                                    (const uint8_t*)(gbuf + G.clamped), cov3D_precomp == nullptr ? scales : nullptr,
                                    rotations, scale_modifier, cov3D_ptr, viewmatrix, projmatrix, focal_x, focal_y,
                                    tan_fovx, tan_fovy, campos, dL_dmean2D, dL_dconic, (const float*)(gbuf + G.conic_opacity),
-                                   width, height, dL_dmean3D, dL_dcolor, dL_dcov3D, dL_dsh, dL_dscale, dL_drot);
+                                   width, height, dL_dmean3D, dL_dcolor, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, adam);
         check_launch(stream, debug, "preprocess_backward");
         t_pb.stop();
         return R3DG_OK;
     });
 }
+
+#define R3DG_BACKWARD_SPLIT_ARGS                                                                                              \
+    stream_, geometry_stream_, P, S, D, M, R, background, width, height, means3D, shs, features, colors_precomp, scales,        \
+        scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer,       \
+        binning_buffer, img_buffer, dL_dpix, dL_dpix_o, dL_dpix_d, dL_dpix_f, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,    \
+        dL_dfeature, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, backward_geometry, debug_, n_active_features,           \
+        active_features
+
+int r3dg_rasterize_backward_split(void* stream_, void* geometry_stream_, int P, int S, int D, int M, int R,
+                                  const float* background, int width, int height, const float* means3D,
+                                  const float* shs, const float* features, const float* colors_precomp,
+                                  const float* scales, float scale_modifier, const float* rotations,
+                                  const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                  const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
+                                  const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
+                                  const float* dL_dpix, const float* dL_dpix_o, const float* dL_dpix_d,
+                                  const float* dL_dpix_f, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                                  float* dL_dcolor, float* dL_dfeature, float* dL_dmean3D, float* dL_dcov3D,
+                                  float* dL_dsh, float* dL_dscale, float* dL_drot, int backward_geometry, int debug_,
+                                  int n_active_features, const int* active_features)
+{
+    return backward_split_impl(R3DG_BACKWARD_SPLIT_ARGS, nullptr);
+}
+
+int r3dg_rasterize_backward_sh_adam_supported(int M) { return preprocess_backward_applies_adam(M) ? 1 : 0; }
+
+int r3dg_rasterize_backward_split_sh_adam(void* stream_, void* geometry_stream_, int P, int S, int D, int M, int R,
+                                  const float* background, int width, int height, const float* means3D,
+                                  const float* shs, const float* features, const float* colors_precomp,
+                                  const float* scales, float scale_modifier, const float* rotations,
+                                  const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                  const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
+                                  const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
+                                  const float* dL_dpix, const float* dL_dpix_o, const float* dL_dpix_d,
+                                  const float* dL_dpix_f, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                                  float* dL_dcolor, float* dL_dfeature, float* dL_dmean3D, float* dL_dcov3D,
+                                  float* dL_dsh, float* dL_dscale, float* dL_drot, int backward_geometry, int debug_,
+                                  int n_active_features, const int* active_features,
+                                  const r3dg_adam_group* sh_adam, float beta1, float beta2, float eps, int step,
+                                  float grad_scale, const float* skip_flag)
+{
+    const char* me = "rasterize_backward_split_sh_adam: ";
+    if (P < 0 || M < 0) return invalid(std::string(me) + "bad P/M");
+    if (!sh_adam) return invalid(std::string(me) + "null group");
+    if (step < 1) return invalid(std::string(me) + "step counts from 1");
+    if (!preprocess_backward_applies_adam(M)) return invalid(std::string(me) + "no such kernel for this M / with STAGE_SH_ROWS off");
+    if (!shs || colors_precomp) return invalid(std::string(me) + "needs SH input");
+    const r3dg_adam_group& g = *sh_adam;
+    if (g.param != shs || g.n != (uint64_t)P * 3 * (uint64_t)M || g.n >= (1ull << 32))
+        return invalid(std::string(me) + "the group must be the [P,M,3] SH tensor itself (below 2^32 elements)");
+    if (P > 0 && (!g.exp_avg || !g.exp_avg_sq || (((uintptr_t)g.param | (uintptr_t)g.exp_avg | (uintptr_t)g.exp_avg_sq) & 15)))
+        return invalid(std::string(me) + "null or unaligned buffer in group");
+    const AdamBias b = adam_bias(beta1, beta2, step);
+    const ShAdamArgs adam = {g, beta1, beta2, eps, b.bias1, b.inv_sqrt_bias2, grad_scale, skip_flag};
+    return backward_split_impl(R3DG_BACKWARD_SPLIT_ARGS, &adam);
+}
+#undef R3DG_BACKWARD_SPLIT_ARGS
 
 int r3dg_rasterize_backward_features(void* stream_, int P, int S, int R, int width, int height, const void* geom_buffer,
                                      const void* binning_buffer, const void* img_buffer, const float* dL_dpix_f,

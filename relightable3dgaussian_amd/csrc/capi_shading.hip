@@ -366,9 +366,11 @@ int r3dg_shade_frs_backward(void* stream_, int P, int K, const float* base_color
 int r3dg_shade_frs_incident_chain(void* stream_, int P, const float* ray_normals, const uint8_t* valid, const float* dcprime,
                                   float* dL_dincidents, float* incidents, float* exp_avg, float* exp_avg_sq, float* cprime,
                                   float lr, float lr_tail, float beta1, float beta2, float eps, int step, float grad_scale,
-                                  const float* skip_flag, int listed_rows_in_dcprime)
+                                  const float* skip_flag, int chain_flags)
 {
     if (P < 0) return invalid("shade_frs_incident_chain: bad sizes");
+    if (chain_flags & ~(R3DG_CHAIN_LISTED_ROWS_IN_DCPRIME | R3DG_CHAIN_NO_GRADIENT_OUT))
+        return invalid("shade_frs_incident_chain: unknown R3DG_CHAIN_* bit");
     if (step < 1) return invalid("shade_frs_incident_chain: step counts from 1");
     if (P == 0) return R3DG_OK;
     if (!ray_normals || !dcprime || !dL_dincidents || !incidents || !exp_avg || !exp_avg_sq || !cprime)
@@ -378,7 +380,8 @@ int r3dg_shade_frs_incident_chain(void* stream_, int P, const float* ray_normals
         StageTimer t(stream, ST_SHADE_AUX);
         launch_shade_frs_incident_chain(stream, P, ray_normals, valid, dcprime, dL_dincidents, incidents, exp_avg, exp_avg_sq,
                                         cprime, lr, lr_tail, beta1, beta2, eps, step, grad_scale, skip_flag,
-                                        listed_rows_in_dcprime != 0 ? 1 : 0);
+                                        (chain_flags & R3DG_CHAIN_LISTED_ROWS_IN_DCPRIME) ? 1 : 0,
+                                        !(chain_flags & R3DG_CHAIN_NO_GRADIENT_OUT));
         return R3DG_OK;
     });
 }

@@ -41,12 +41,22 @@ void launch_render_backward_features(hipStream_t s, int W, int H, int S, int n_a
                                      const uint32_t* tile_order, const uint32_t* ranges, const uint32_t* point_list,
                                      const float* splat, const float* final_Ts, const uint32_t* n_contrib,
                                      const float* dL_dpix_f, float* dL_dfeature);
+// the SH colour group's Adam step as the projection backward applies it itself (`g.param` IS its `shs`; `g.grad` is not read:
+// the gradient rows are in LDS); the bias corrections from adam_bias (adam_update.hpp)
+struct ShAdamArgs {
+    r3dg_adam_group g;
+    float beta1, beta2, eps, bias1, inv_sqrt_bias2, grad_scale;
+    const float* skip_flag;
+};
+bool preprocess_backward_applies_adam(int M);
+// `adam` != nullptr: dL_dsh is NOT written; parameters and moments of the group are updated in place instead
 void launch_preprocess_backward(hipStream_t s, int P, int D, int M, const float* means, const int* radii, const float* shs,
                                 const uint8_t* clamped, const float* scales, const float* rotations, float scale_modifier,
                                 const float* cov3Ds, const float* vm, const float* proj, float h_x, float h_y,
                                 float tan_fovx, float tan_fovy, const float* campos, float* dL_dmean2D,
                                 const float* dL_dconic, const float* conic_opacity, int W, int H, float* dL_dmeans,
-                                const float* dL_dcolor, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot);
+                                const float* dL_dcolor, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                const ShAdamArgs* adam);
 void launch_shade_forward(hipStream_t s, int P, int K, int M, const float* base_color, const float* roughness,
                           const float* normals, const float* viewdirs, const float* incidents, const float* env, int He,
                           int We, const float* tr, const float* visibility, const float* dirs, const float* areas,
@@ -72,7 +82,7 @@ void launch_shade_frs_forward_listed(hipStream_t s, int K, const float* base_col
 void launch_shade_frs_incident_chain(hipStream_t s, int P, const float* ray_normals, const uint8_t* valid, const float* dcp,
                                      float* d_inc, float* incidents, float* exp_avg, float* exp_avg_sq, float* cprime,
                                      float lr, float lr_tail, float beta1, float beta2, float eps, int step,
-                                     float grad_scale, const float* skip_flag, int listed_in_dcprime);
+                                     float grad_scale, const float* skip_flag, int listed_in_dcprime, bool write_gradient);
 const unsigned int* launch_shade_frs_backward_aux(hipStream_t s, int P, const float* g_pbr, const float* g_diff,
                                                   const float* block_absmax, int n_block_absmax, int* gmax_n);
 void launch_shade_frs_backward_main(hipStream_t s, int P, int K, const float* base_color, const float* roughness,

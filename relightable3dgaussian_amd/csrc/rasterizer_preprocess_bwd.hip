@@ -6,6 +6,13 @@
 // 192 B dL_dsh row written).  Those two rows travel through LDS (STAGED): the block moves its 256 rows with coalesced
 // 16-byte accesses (common.hpp stage_rows_*), each thread walks its own row in LDS; a thread-per-Gaussian walk straight
 // in HBM makes every wave load/store touch 64 different cache lines.
+// WITH THE SH GROUP'S ADAM (whole single-GPU training iterations): the dL_dsh rows never leave LDS.  In place of streaming
+// them out, the block walks its run of the [P,3M] parameter and moment arrays in adam_kernel's coalesced float4 pattern and
+// applies the SH colour group's
+// Adam update itself (adam_update.hpp: adam_kernel's statements): per Gaussian 192 B of gradient written and 192 + 192 B of
+// gradient and parameter read again by a separate Adam launch are gone, and that launch with them.  The parameter row is read
+// a second time here (an L2 hit: the block staged it a few microseconds ago) rather than kept as a second 49 KB copy in LDS.
+#include "adam_update.hpp"
 #include "launchers.hpp"
 
 namespace r3dg {
@@ -41,6 +48,12 @@ __device__ const float bSH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0
                                     0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
                                     -0.5900435899266435f};
 
+// `adam` (STAGED only; adam.g.exp_avg != NULL switches it on): the tail applies the SH group's Adam instead of writing dL_dsh.
+// A RUN-TIME switch, uniform over the grid and taken once, behind the last barrier, when nothing is in flight -- NOT a template
+// parameter: as two instantiations the compiler contracted the geometry arithmetic above differently (369 against 352 fused
+// multiply-adds in the per-Gaussian part), so dL_dmeans3D came out a few ulp apart with and without the update; one instruction
+// stream for that part keeps every geometry output bit for bit the same whichever tail runs.
+// `shs` IS the parameter array the tail updates -- through a pointer derived from `shs`, which is what its no-alias promise allows.
 template <bool STAGED>
 __global__ void __launch_bounds__(256)
 preprocess_backward_kernel(int P, int D, int M, const float* __restrict__ means, const int* __restrict__ radii,
@@ -52,10 +65,13 @@ preprocess_backward_kernel(int P, int D, int M, const float* __restrict__ means,
                            const float4* __restrict__ conic_opacity, float half_w, float half_h,
                            float* __restrict__ dL_dmeans, const float* __restrict__ dL_dcolor,
                            float* __restrict__ dL_dcov3D, float* __restrict__ dL_dsh, float* __restrict__ dL_dscale,
-                           float* __restrict__ dL_drot)
+                           float* __restrict__ dL_drot, ShAdamArgs adam)
 {
     extern __shared__ float s_rows[];                  // STAGED: 256 SH rows in, the same 256 dL_dsh rows out
     __shared__ uint8_t s_live[256];
+    const bool apply_adam = STAGED && adam.g.exp_avg != nullptr;
+    // a view the bounded forward dropped gets no update (adam_kernel's rule; read here, far ahead of its use)
+    const bool skip_update = apply_adam && adam.skip_flag != nullptr && *adam.skip_flag != 0.0f;
     const int idx = blockIdx.x * 256 + threadIdx.x;
     const bool in_range = idx < P;
     const bool visible = in_range && radii[idx] > 0;
@@ -299,34 +315,83 @@ preprocess_backward_kernel(int P, int D, int M, const float* __restrict__ means,
 #undef D_
     }
     } while (0);
-    if (STAGED) {
-        __syncthreads();
+    if (!STAGED) return;
+    __syncthreads();
+    if (!apply_adam) {
         stage_rows_out_256(dL_dsh, blockIdx.x * 256, P, 3 * M, s_rows);
+    } else if (!skip_update) {
+        // the block's run of the [P,3M] arrays (launcher: 3M % 4 == 0, 16-byte aligned arrays), float4 number q of the run per
+        // thread and round: adam_kernel's access pattern.  Culled Gaussians hold a zero row: their moments decay as there.
+        const int row_floats = 3 * M, stride = staged_row_stride(row_floats), q_per_row = row_floats >> 2;
+        const int nq = min(256, P - blockIdx.x * 256) * q_per_row;
+        const size_t run = (size_t)blockIdx.x * 256 * row_floats;
+        float* p = const_cast<float*>(shs) + run;               // (== adam.g.param + run: the C-ABI wrapper checked)
+        float* __restrict__ m = adam.g.exp_avg + run;
+        float* __restrict__ v = adam.g.exp_avg_sq + run;
+        // four float4 per array in flight per thread, NO branch around a load (a slot past the run reads its last float4)
+        constexpr int B = 4;
+        for (int q0 = threadIdx.x; q0 < nq; q0 += 256 * B) {
+            float pv[B][4], mv[B][4], vv[B][4];
+#pragma unroll
+            for (int j = 0; j < B; j++) {
+                const size_t at = 4 * (size_t)min(q0 + j * 256, nq - 1);
+                *reinterpret_cast<float4*>(pv[j]) = *reinterpret_cast<const float4*>(p + at);
+                *reinterpret_cast<float4*>(mv[j]) = adam_load(m + at, true);
+                *reinterpret_cast<float4*>(vv[j]) = adam_load(v + at, true);
+            }
+#pragma unroll
+            for (int j = 0; j < B; j++) {
+                const int q = q0 + j * 256;
+                if (q >= nq) break;
+                const int r = q / q_per_row, c = (q - r * q_per_row) * 4;
+                const float* d = s_rows + r * stride + c;
+                const size_t at = 4 * (size_t)q;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const float lr = adam_rate((unsigned int)(run + at + k), adam.g.lr, adam.g.lr_tail, adam.g.period, adam.g.split);
+                    adam_update(pv[j][k], d[k], mv[j][k], vv[j][k], lr, adam.beta1, adam.beta2, adam.eps, adam.bias1,
+                                adam.inv_sqrt_bias2, adam.grad_scale);
+                }
+                *reinterpret_cast<float4*>(p + at) = *reinterpret_cast<float4*>(pv[j]);
+                adam_store(m + at, mv[j], true);
+                adam_store(v + at, vv[j], true);
+            }
+        }
     }
 }
 
 static inline int staged_row_stride_host(int row_floats) { return row_floats | 1; }
+
+// the variant that applies the SH group's Adam exists where the rows go through LDS and are whole float4s
+bool preprocess_backward_applies_adam(int M)
+{
+    return opt(R3DG_OPT_STAGE_SH_ROWS) && M >= 1 && M <= 16 && (3 * M) % 4 == 0;
+}
 
 void launch_preprocess_backward(hipStream_t s, int P, int D, int M, const float* means, const int* radii,
                                 const float* shs, const uint8_t* clamped, const float* scales, const float* rotations,
                                 float scale_modifier, const float* cov3Ds, const float* vm, const float* proj, float h_x,
                                 float h_y, float tan_fovx, float tan_fovy, const float* campos, float* dL_dmean2D,
                                 const float* dL_dconic, const float* conic_opacity, int W, int H, float* dL_dmeans,
-                                const float* dL_dcolor, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot)
+                                const float* dL_dcolor, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                const ShAdamArgs* adam)
 {
     if (P <= 0) return;
     // SH rows through LDS when there are SH coefficients of at most degree 3 (256 x 49 words = 49 KB per block)
     const bool staged = opt(R3DG_OPT_STAGE_SH_ROWS) && shs != nullptr && M >= 1 && M <= 16;
+    // (adam != nullptr: the C-ABI wrapper refused the call unless preprocess_backward_applies_adam(M) and shs != NULL, so the
+    // staged kernel runs: there is no other kernel to fall back to)
+    const ShAdamArgs none = {};
     if (staged)
         preprocess_backward_kernel<true><<<(P + 255) / 256, 256, 256 * staged_row_stride_host(3 * M) * sizeof(float), s>>>(
             P, D, M, means, radii, shs, clamped, scales, rotations, scale_modifier, cov3Ds, vm, proj, h_x, h_y, tan_fovx,
             tan_fovy, campos, dL_dmean2D, dL_dconic, (const float4*)conic_opacity, 0.5f * W, 0.5f * H, dL_dmeans, dL_dcolor, dL_dcov3D,
-            dL_dsh, dL_dscale, dL_drot);
+            dL_dsh, dL_dscale, dL_drot, adam != nullptr ? *adam : none);
     else
         preprocess_backward_kernel<false><<<(P + 255) / 256, 256, 0, s>>>(
             P, D, M, means, radii, shs, clamped, scales, rotations, scale_modifier, cov3Ds, vm, proj, h_x, h_y, tan_fovx,
             tan_fovy, campos, dL_dmean2D, dL_dconic, (const float4*)conic_opacity, 0.5f * W, 0.5f * H, dL_dmeans, dL_dcolor, dL_dcov3D,
-            dL_dsh, dL_dscale, dL_drot);
+            dL_dsh, dL_dscale, dL_drot, none);
 }
 
 }  // namespace r3dg

@@ -241,6 +241,9 @@ __device__ __forceinline__ void frs_nt_store4(float4* q, const float4& v)
     __builtin_nontemporal_store(v.w, &q->w);
 }
 
+// WRITE_GRAD = false (a caller nobody reads the gradient of behind the update: whole single-GPU iterations): the world-frame
+// gradient row lives in LDS only -- 1536 bytes per Gaussian instead of 1728; everything else is the same instruction stream.
+template <bool WRITE_GRAD>
 __global__ void __launch_bounds__(256)
 frs_incident_chain_kernel(int P, const float* __restrict__ ray_normals, const uint8_t* __restrict__ valid,
                           const float* __restrict__ dcprime, float* __restrict__ dL_dincidents, float* __restrict__ incidents,
@@ -336,7 +339,7 @@ frs_incident_chain_kernel(int P, const float* __restrict__ ray_normals, const ui
                 p4[e4] = p;
                 frs_nt_store4(m4 + e4, m);
                 frs_nt_store4(v4 + e4, v);
-                g4[e4] = gr;
+                if (WRITE_GRAD) g4[e4] = gr;
                 d[0] = p.x; d[1] = p.y; d[2] = p.z; d[3] = p.w;
             }
         }
@@ -1378,7 +1381,7 @@ void launch_shade_frs_backward_rotate(hipStream_t s, int P, const float* ray_nor
 void launch_shade_frs_incident_chain(hipStream_t s, int P, const float* ray_normals, const uint8_t* valid, const float* dcp,
                                      float* d_inc, float* incidents, float* exp_avg, float* exp_avg_sq, float* cprime, float lr,
                                      float lr_tail, float beta1, float beta2, float eps, int step, float grad_scale,
-                                     const float* skip_flag, int listed_in_dcprime)
+                                     const float* skip_flag, int listed_in_dcprime, bool write_gradient)
 {
     if (P == 0) return;
     // (bias corrections exactly as launch_adam forms them, adam.hip)
@@ -1388,8 +1391,12 @@ void launch_shade_frs_incident_chain(hipStream_t s, int P, const float* ray_norm
     // activation / projection kernels running beside it but make the chain the longer path: 805 / 797 / 771 it/s
     const size_t lds = 4 * 64 * FRS_CHAIN_LD * sizeof(float);
     // (49 KB of dynamic LDS: under the 64 KB every launch may ask for, so no per-device function attribute is needed)
-    frs_incident_chain_kernel<<<(P + 255) / 256, 256, lds, s>>>(P, ray_normals, valid, dcp, d_inc, incidents, exp_avg, exp_avg_sq,
-                                                                cprime, a, skip_flag, listed_in_dcprime);
+    if (write_gradient)
+        frs_incident_chain_kernel<true><<<(P + 255) / 256, 256, lds, s>>>(P, ray_normals, valid, dcp, d_inc, incidents, exp_avg,
+                                                                          exp_avg_sq, cprime, a, skip_flag, listed_in_dcprime);
+    else
+        frs_incident_chain_kernel<false><<<(P + 255) / 256, 256, lds, s>>>(P, ray_normals, valid, dcp, d_inc, incidents, exp_avg,
+                                                                           exp_avg_sq, cprime, a, skip_flag, listed_in_dcprime);
     check_launch(s, false, "frs_incident_chain_kernel");
 }
 

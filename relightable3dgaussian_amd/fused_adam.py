@@ -38,6 +38,17 @@ class FusedAdam:
     def begin_step(self):
         self.step_count += 1
 
+    def fused_step_of(self, i, step, grad_scale=1.0, skip_flag=None):
+        """The trailing arguments of an entry point whose kernel applies group i's update as step `step` itself, where the
+        gradient is produced (r3dg_rasterize_backward_split_sh_adam): (group descriptor, betas, eps, step, grad_scale, skip flag).
+        The descriptor names no gradient buffer; it lives until the next call."""
+        g = self.groups[i]
+        p = g["param"]
+        self._fused_desc = AdamGroup(p.data_ptr(), None, g["exp_avg"].data_ptr(), g["exp_avg_sq"].data_ptr(), p.numel(),
+                                     g["lr"], g["lr_tail"], g.get("period", 0), g.get("split", 0))
+        return (C.addressof(self._fused_desc), self.betas[0], self.betas[1], self.eps, int(step), float(grad_scale),
+                skip_flag.data_ptr() if skip_flag is not None else None)
+
     def step_groups(self, indices, grads, grad_scale=1.0, skip_flag=None):
         """Adam update of a subset of the groups for the current step (begin_step() first); `grads[i]` belongs to group i.
         Lets a data-parallel caller update each gradient bucket as soon as its all-reduce has landed.  `skip_flag`: float32

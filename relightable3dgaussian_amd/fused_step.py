@@ -306,8 +306,11 @@ class FusedStage2Step(FusedStepBase):
 
     @_in_context
     def forward_backward(self, cam, bg, gt, early_adam=False, image_mask=None, split_geometry=None, chain_incidents=False,
-                         gt_depth=None, mvs_normal=None):
+                         gt_depth=None, mvs_normal=None, sh_adam_in_backward=False):
         """One forward + loss + backward; gradients land in self.grads.  Returns the rasterizer's 10 public outputs.
+        A bare call leaves EVERY entry of `grads` holding this view's gradient.  As part of a whole iteration (__call__) two
+        entries do not: grads["shs"] and grads["incidents"] are then not written at all (see `sh_adam_in_backward` and
+        optimizer_step) -- they keep whatever an earlier bare call or schedule left in them.
         `image_mask` [1,H,W]: the view's object mask (Camera.image_mask; None = all ones) of the normal and smoothness terms.
         `gt_depth` [1,H,W], `mvs_normal` [3,H,W]: the view's MVS depth map and the normals derived from it (Camera.depth /
         Camera.normal); required by the `depth` / `normal_mvs_depth` terms (both need the depth map), ignored without them.
@@ -319,7 +322,10 @@ class FusedStage2Step(FusedStepBase):
         off: 160.7 vs 166.3 it/s -- both kernels stream from HBM there and slow each other by more than the overlap buys.)
         `chain_incidents` (whole iterations only, see __call__; implied by `early_adam`): the incident-light gradient may stay in
         the rotated frame for the chain kernel that optimizer_step launches -- a caller of a bare forward_backward reads
-        grads["incidents"] in the world frame, always."""
+        grads["incidents"] in the world frame, always.
+        `sh_adam_in_backward` (whole iterations only, see __call__ and _fuses_sh_adam): the rasterizer's per-Gaussian geometry
+        backward applies the SH colour group's Adam itself, from the gradient rows it holds on chip; there is no Adam launch for
+        the group and grads["shs"] is not written."""
         H, W = cam.image_height, cam.image_width
         if self._supervised and (gt_depth is None or (self.w["normal_mvs_depth"] != 0.0 and mvs_normal is None)):
             raise RuntimeError("FusedStage2Step: the depth / normal_mvs_depth terms need gt_depth%s" % (
@@ -335,9 +341,10 @@ class FusedStage2Step(FusedStepBase):
             # read a snapshot of the flag taken after bucket A's all-reduce (_schedule_early / optimizer_step)
             self._skip_cur = flag_cur
             g, active = self._image_loss(v, fw)
+            fused_a = sh_adam_in_backward and self._fuses_sh_adam()
             dL_dfeatures, bw, geo_stream, handle_a = self._raster_backward(
-                v, fw, g, active, early_adam if split_geometry is None else split_geometry)
-            b_early = self._schedule_early(v, handle_a, geo_stream, use_bounded, early_adam, chain_incidents)
+                v, fw, g, active, early_adam if split_geometry is None else split_geometry, fused_a)
+            b_early = self._schedule_early(v, handle_a, geo_stream, use_bounded, early_adam, chain_incidents, fused_a)
             self._shade_backward(v, env_c, taps, packed, dL_dfeatures, bw, geo_stream, b_early, chain_incidents)
             self._remaining_buckets(handle_a)
         return self._end_forward_backward(fw, None if bw is None else bw[0], use_bounded, v.N)
@@ -499,10 +506,21 @@ class FusedStage2Step(FusedStepBase):
         self._sup_counts[key] = (v.gt_depth, v.mask, (v.gt_depth._version, mv), count)
         return count
 
-    def _raster_backward(self, v, fw, g, active, split_geometry):
+    def _fuses_sh_adam(self):
+        """A whole iteration lets the geometry backward apply the SH colour group's Adam (r3dg_rasterize_backward_split_sh_adam:
+        the gradient rows never reach device memory, the group gets no Adam launch)?  Single GPU (under data parallelism the
+        gradient has to travel in bucket A, and replicas must stay bit-identical through ONE kernel), the group trains, the
+        geometry backward runs at all, the backward in use has the kernel for this SH size (asked every iteration: it depends on
+        an option), and R3DG_SH_ADAM_IN_BACKWARD is not 0 (the A/B switch: 0 restores the separate launch)."""
+        can = getattr(rasterizer_ops.rasterize_gaussians_backward, "sh_adam_supported", None)
+        return (not self.dp and bool(self._groups_a) and not self.frozen_geometry and can is not None
+                and os.environ.get("R3DG_SH_ADAM_IN_BACKWARD", "1") != "0" and can(self.M))
+
+    def _raster_backward(self, v, fw, g, active, split_geometry, fused_a=False):
         """-> (dL_dfeatures, ALL outputs of the geometry backward or None with frozen geometry, the stream the geometry backward
         went to or None, the work handle of bucket A's all-reduce or None).  The caller holds every output until that stream is
-        joined: the allocator would hand the memory of a dropped one to the next launch of the main stream."""
+        joined: the allocator would hand the memory of a dropped one to the next launch of the main stream.
+        `fused_a`: the geometry backward applies the SH group's Adam as the step _schedule_early is about to begin."""
         cam, empty = v.cam, torch.Tensor([])
         R, radii, geom, binning, img = fw[0], fw[9], fw[10], fw[11], fw[12]
         geo_stream = None
@@ -519,12 +537,15 @@ class FusedStage2Step(FusedStepBase):
             # latency-bound launch that r3dg_shade_frs_backward queues FIRST) instead of in front of them; the main shading
             # backward, which fills the register file, starts when both are about done
             geo_stream = self._listed_stream() if split_geometry else None
+            # (fused: the step count opt.begin_step() gives this iteration in _schedule_early, this iteration's own skip flag)
+            fused = dict(sh_adam=self.opt.fused_step_of(self._groups_a[0], self.opt.step_count + 1, 1.0, self._skip_cur)) \
+                if fused_a else {}
             bw = rasterizer_ops.rasterize_gaussians_backward(
                 v.bg, self.xyz, self.features, radii, empty, self.a_scales, self.a_rot, 1.0, empty, v.vm,
                 # (no depth gradient: an EMPTY tensor = NULL = the caller's promise that the depth image carries no loss term)
                 cam.full_proj_transform, cam.tanfovx, cam.tanfovy, g[0:3], g[3:4], empty, g[4:20],
                 self.shs, 3, v.campos, geom, R, binning, img, True, False, dL_dsh_out=self.grads["shs"],
-                geometry_stream=geo_stream, active_features=sorted(active), zeroed_accumulators=self._acc)
+                geometry_stream=geo_stream, active_features=sorted(active), zeroed_accumulators=self._acc, **fused)
             dL_dfeatures = bw[4]
             if geo_stream is not None:
                 if self._geo_done is None:
@@ -537,7 +558,7 @@ class FusedStage2Step(FusedStepBase):
                 handle_a = self._comm.allreduce_async(self._bucket_a, "A", self._iter)
         return dL_dfeatures, bw, geo_stream, handle_a
 
-    def _schedule_early(self, v, handle_a, geo_stream, use_bounded, early_adam, chain_incidents):
+    def _schedule_early(self, v, handle_a, geo_stream, use_bounded, early_adam, chain_incidents, fused_a=False):
         """SCHEDULE of the two large groups' updates (`_early`, `_b_early`, `_a_late`, read by optimizer_step), and the SH
         group's early Adam.  -> b_early.
         a_early: the SH group's Adam on the early stream UNDER the shading backward, behind the geometry backward that
@@ -552,16 +573,25 @@ class FusedStage2Step(FusedStepBase):
           sample_num 384: there the shading forward is the long path of the forward window and the chain in front of it
           costs more than the launches it saves); above a million Gaussians (no early Adam: __call__) the launches it
           replaces stream 2112 bytes per Gaussian, the chain 1741.
-        a_late: the chain is queued but the SH group is updated with the others in optimizer_step."""
-        a_early = early_adam and bool(self._groups_a) and (handle_a is not None or not self.dp)
+        a_late: the chain is queued but the SH group is updated with the others in optimizer_step.
+        fused_a (_fuses_sh_adam): the geometry backward has applied the SH group's Adam already, on `geo_stream` or the main
+          stream, as the step begun here: a_early without the launch -- with or without `early_adam`, so also above a
+          million Gaussians -- and the choice of b_early is what it would be without it."""
+        a_launch = early_adam and bool(self._groups_a) and (handle_a is not None or not self.dp)
         b_early = (not self.dp and self._samples.frs is not None and v.order_stream is not None and use_bounded and
-                   (a_early or (bool(self._groups_b) and (self.P * self.K <= 40_000_000 if early_adam else chain_incidents))))
+                   (a_launch or (bool(self._groups_b) and (self.P * self.K <= 40_000_000 if early_adam else chain_incidents))))
+        a_early = a_launch or fused_a
         self._early, self._b_early, self._a_late = a_early or b_early, b_early, b_early and not a_early
         if self._early:
             side = self._early_stream()
             self.opt.begin_step()
             self._early_pending = not self.dp
-        if a_early:
+        if fused_a:
+            if b_early:
+                # (as below: the next projection reads the SH colour coefficients; the kernel that wrote them is the geometry
+                # backward, the last thing queued on its stream)
+                _lib.stream_wait(v.order_stream, geo_stream if geo_stream is not None else v.main)
+        elif a_early:
             if geo_stream is None and not self.dp:
                 side.wait_stream(v.main)
             with torch.cuda.stream(side):
@@ -684,7 +714,12 @@ class FusedStage2Step(FusedStepBase):
     @_in_context
     def optimizer_step(self):
         """Adam on every group that trains (groups with learning rate 0 get no launch): _groups_a = shs, _groups_c = the small
-        per-Gaussian groups + env, _groups_b = incidents -- indices into self.opt.groups, one tuple per gradient bucket."""
+        per-Gaussian groups + env, _groups_b = incidents -- indices into self.opt.groups, one tuple per gradient bucket.
+        Behind a forward_backward that ran as part of a whole single-GPU iteration two groups are not updated from `grads`:
+        the SH colour group was updated inside the geometry backward (`sh_adam_in_backward`), the incident-light group is
+        updated by the chain kernel queued here, which keeps the rotated-back gradient on chip -- grads["shs"] and
+        grads["incidents"] do NOT hold that iteration's gradient afterwards (data-parallel runs and a bare forward_backward
+        write both)."""
         grads = [self.grads[k] for k in self._opt_order]
         if not self.dp:
             if self._b_early:
@@ -739,7 +774,8 @@ class FusedStage2Step(FusedStepBase):
     def _incident_chain(self, frs, count, scale, skip, **listed):
         """The incident-light chain on the current stream, ONE kernel: rotation back of the group's gradient (into
         grads["incidents"]) + its Adam update as step `count` + rotation of the new coefficients, where the next shading forward
-        finds them.  `listed`: FixedRaySet.incident_chain's `listed_in_dcprime` (data parallel)."""
+        finds them.  `listed`: FixedRaySet.incident_chain's `listed_in_dcprime` (data parallel) / `write_gradient` (False in
+        whole single-GPU iterations: grads["incidents"] is then not written)."""
         grp = self.opt.groups[self._groups_b[0]]
         frs.incident_chain(self._incidents, self.grads["incidents"], grp["exp_avg"], grp["exp_avg_sq"], grp["lr"],
                            grp["lr_tail"], self.opt.betas, self.opt.eps, count, scale, skip_flag=skip, **listed)
@@ -754,7 +790,11 @@ class FusedStage2Step(FusedStepBase):
         _lib.stream_wait(early, torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(early):
             if self._groups_b:
-                self._incident_chain(frs, count, 1.0, skip)
+                # (nobody reads the world-frame gradient of a whole single-GPU iteration behind the update: the kernel keeps the
+                # row on chip, 192 of its 1728 bytes per Gaussian; R3DG_CHAIN_WRITES_GRADIENT=1 is the A/B switch)
+                lean = (getattr(frs, "chain_gradient_optional", False)
+                        and os.environ.get("R3DG_CHAIN_WRITES_GRADIENT", "0") == "0")
+                self._incident_chain(frs, count, 1.0, skip, **(dict(write_gradient=False) if lean else {}))
             else:
                 frs.rotate(self._incidents)
                 self._pre_rotated = (frs, self._incidents, self._incidents._version)
@@ -782,11 +822,14 @@ class FusedStage2Step(FusedStepBase):
 
     @_in_context
     def __call__(self, cam, bg, gt, image_mask=None, gt_depth=None, mvs_normal=None):
-        # the SH group's Adam under the shading backward: pays while the group's 64 bytes x 48 per Gaussian mostly live in the
+        """One whole training iteration: forward_backward + optimizer_step.  On one GPU, grads["shs"] and grads["incidents"] do
+        NOT hold this iteration's gradient afterwards: the kernels that produce those two [P,48] gradients apply their groups'
+        Adam themselves and never write them out (_fuses_sh_adam, _run_chain); every other entry of `grads` does."""
+        # the SH group's Adam as a launch of its own (where the geometry backward does not apply it itself: _fuses_sh_adam) under the shading backward: pays while the group's 64 bytes x 48 per Gaussian mostly live in the
         # 256 MB last-level cache (300k Gaussians: 58 us of Adam for 31 us of slower shading backward); streamed from HBM it
         # costs the latency-sensitive shading kernel nearly its whole duration (2M: 0.99 ms of Adam for +0.85 ms, 159 vs 163 it/s)
         early = os.environ.get("R3DG_EARLY_ADAM", "1" if self.P <= 1_000_000 else "0") != "0" and not self.serial_streams
         outs = self.forward_backward(cam, bg, gt, early_adam=early, image_mask=image_mask, chain_incidents=True,
-                                     gt_depth=gt_depth, mvs_normal=mvs_normal)
+                                     gt_depth=gt_depth, mvs_normal=mvs_normal, sh_adam_in_backward=True)
         self.optimizer_step()
         return outs

@@ -195,7 +195,7 @@ def rasterize_gaussians_backward(background, means3D, features, radii, colors, s
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                  dL_dout_opacity, dL_dout_depth, dL_dout_feature, sh, degree, campos, geomBuffer, R,
                                  binningBuffer, imageBuffer, backward_geometry, debug, dL_dsh_out=None,
-                                 geometry_stream=None, active_features=None, zeroed_accumulators=None):
+                                 geometry_stream=None, active_features=None, zeroed_accumulators=None, sh_adam=None):
     """`dL_dsh_out` (not in the reference signature): optional preallocated [P,M,3] buffer the SH gradient is written
     into (every element is written), e.g. a view of a flat gradient bucket.  `geometry_stream`: optional torch stream
     for the per-Gaussian geometry backward (dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations are then only
@@ -203,7 +203,11 @@ def rasterize_gaussians_backward(background, means3D, features, radii, colors, s
     the feature channels whose upstream gradient can be non-zero -- the caller's promise that all other channels of
     dL_dout_feature are zero; they are then skipped by the tile kernel (same results).  `zeroed_accumulators`: optional float32
     tensor of (11 + S) * P floats (any contents since round 5 -- the name is from when it had to be zeros) that takes the place
-    of the slab allocated here; dL_dmeans2D, dL_dconic, dL_dopacity, dL_dcolors and dL_dfeatures are views of it."""
+    of the slab allocated here; dL_dmeans2D, dL_dconic, dL_dopacity, dL_dcolors and dL_dfeatures are views of it.
+    `sh_adam` (FusedAdam.fused_step_of(group of `sh`, ...); r3dg_rasterize_backward_split_sh_adam): the per-Gaussian geometry
+    backward applies the Adam step of the SH group itself -- `sh` and its two moment tensors are updated in place and the
+    returned dL_dsh is NOT written (it keeps whatever it held).  Raises where the library has no such kernel
+    (sh_adam_supported)."""
     L = _lib.lib()
     P = means3D.size(0)
     S = features.size(1)
@@ -258,7 +262,13 @@ def rasterize_gaussians_backward(background, means3D, features, radii, colors, s
             else:
                 n_act = len(active_features)
                 act = (C.c_int * max(1, n_act))(*[int(a) for a in active_features])
-            st = L.r3dg_rasterize_backward_split(
+            if sh_adam is not None:
+                if sh_ is not sh or not have_sh:
+                    raise RuntimeError("sh_adam: needs the contiguous float32 SH tensor itself as `sh`")
+                entry, tail = L.r3dg_rasterize_backward_split_sh_adam, sh_adam
+            else:
+                entry, tail = L.r3dg_rasterize_backward_split, ()
+            st = entry(
                 cur, gs, P, S, int(degree), M, int(R), _lib.ptr(bg_), W, H, _lib.ptr(means_),
                 _lib.ptr(sh_), _lib.ptr(feat_), _lib.ptr(col_), _lib.ptr(sc_), float(scale_modifier), _lib.ptr(rot_),
                 _lib.ptr(cov_), _lib.ptr(vm_), _lib.ptr(pm_), _lib.ptr(cam_), float(tan_fovx), float(tan_fovy),
@@ -266,10 +276,21 @@ def rasterize_gaussians_backward(background, means3D, features, radii, colors, s
                 _lib.ptr(gO), _lib.ptr(gD), _lib.ptr(gF), dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(),
                 dL_dopacity.data_ptr(), dL_dcolors.data_ptr(), _lib.ptr(dL_dfeatures), dL_dmeans3D.data_ptr(),
                 dL_dcov3D.data_ptr(), _lib.ptr(dL_dsh), dL_dscales.data_ptr(), dL_drotations.data_ptr(),
-                int(bool(backward_geometry)), int(bool(debug)), n_act, act)
+                int(bool(backward_geometry)), int(bool(debug)), n_act, act, *tail)
         _lib.check(st, "rasterize_gaussians_backward")
     return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dfeatures, dL_dcov3D, dL_dsh, dL_dscales,
             dL_drotations)
+
+
+def _sh_adam_supported(M):
+    """rasterize_gaussians_backward(sh_adam=...) has a kernel for [P,M,3] SH coefficients
+    (r3dg_rasterize_backward_sh_adam_supported: it depends on M and on the STAGE_SH_ROWS option)?"""
+    return bool(_lib.lib().r3dg_rasterize_backward_sh_adam_supported(int(M)))
+
+
+# (asked of the FUNCTION, so that whatever stands in its place -- a wrapper, a recorder -- answers for itself; one without the
+# attribute takes no `sh_adam`)
+rasterize_gaussians_backward.sh_adam_supported = _sh_adam_supported
 
 
 def rasterize_gaussians_backward_features(P, S, image_height, image_width, dL_dout_feature, geomBuffer, R, binningBuffer,

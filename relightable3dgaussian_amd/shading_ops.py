@@ -18,6 +18,7 @@ _K = _abi.constants
 TRAIN_OUTPUTS, TAPS_ARE_RADIANCE = _K["R3DG_SHADE_TRAIN_OUTPUTS"], _K["R3DG_SHADE_TAPS_ARE_RADIANCE"]
 LEAVE_ROOM, ROTATED = _K["R3DG_SHADE_LEAVE_ROOM"], _K["R3DG_SHADE_ROTATED"]
 NO_ROTATION_BACK = ctypes.c_void_p(_K["R3DG_SHADE_NO_ROTATION_BACK"])
+_CHAIN_LISTED, _CHAIN_NO_GRADIENT = _K["R3DG_CHAIN_LISTED_ROWS_IN_DCPRIME"], _K["R3DG_CHAIN_NO_GRADIENT_OUT"]
 
 
 def _c(t):
@@ -288,6 +289,9 @@ class FixedRaySet:
     shade_forward(..., train_outputs=True) / shade_backward(...) compute for caches that ARE
     sampling.fibonacci_sphere_sampling(ray_normals, K); `try_build` checks that and returns None otherwise."""
 
+    # incident_chain takes write_gradient=False (a ray-set object without the attribute always writes the gradient)
+    chain_gradient_optional = True
+
     def __init__(self, ray_normals, K):
         from . import sampling
         L = _lib.lib()
@@ -421,12 +425,14 @@ class FixedRaySet:
         return d_base, d_rough, d_view, d_inc, d_env
 
     def incident_chain(self, incidents, dL_dincidents, exp_avg, exp_avg_sq, lr, lr_tail, betas, eps, step, grad_scale=1.0,
-                       skip_flag=None, listed_in_dcprime=False):
+                       skip_flag=None, listed_in_dcprime=False, write_gradient=True):
         """r3dg_shade_frs_incident_chain on the current stream, behind backward(rotation_back=False): the gradient rotated back
         into `dL_dincidents`, the Adam step of the incident-light group (`incidents`, its two moment tensors; FusedAdam's
         arithmetic), the NEW coefficients rotated into `self.cprime` for the next forward.  `listed_in_dcprime`: backward() was
         given `out_incidents=self.dcprime_rows()` -- the world-frame rows of the Gaussians off the rotated path sit in `dcprime`
-        too (ONE buffer to all-reduce under data parallelism)."""
+        too (ONE buffer to all-reduce under data parallelism).  `write_gradient=False` (R3DG_CHAIN_NO_GRADIENT_OUT): nobody reads
+        the gradient behind the update, so the rotated-back rows are not written -- `dL_dincidents` is only read (the rows of the
+        Gaussians off the rotated path) and otherwise keeps what it held; everything else is bit for bit the same."""
         for t in (incidents, dL_dincidents, exp_avg, exp_avg_sq):
             if tuple(t.shape) != (self.P, 16, 3) or t.dtype != torch.float32 or not t.is_contiguous():
                 raise RuntimeError("FixedRaySet.incident_chain: needs contiguous float32 [P,16,3] tensors")
@@ -435,7 +441,8 @@ class FixedRaySet:
                 _lib.current_stream(), self.P, self.ray_normals.data_ptr(), self.valid.data_ptr(), self.dcprime.data_ptr(),
                 dL_dincidents.data_ptr(), incidents.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), self.cprime.data_ptr(),
                 float(lr), float(lr_tail), float(betas[0]), float(betas[1]), float(eps), int(step), float(grad_scale),
-                skip_flag.data_ptr() if skip_flag is not None else None, 1 if listed_in_dcprime else 0)
+                skip_flag.data_ptr() if skip_flag is not None else None,
+                (_CHAIN_LISTED if listed_in_dcprime else 0) | (0 if write_gradient else _CHAIN_NO_GRADIENT))
         _lib.check(st, "shade_frs_incident_chain")
 
     def dcprime_rows(self):
