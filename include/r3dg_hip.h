@@ -844,6 +844,29 @@ int r3dg_relight_quantize(void* stream, int width, int height, int channels, con
 int r3dg_view_unpack(void* stream, int width, int height, int channels, const uint8_t* d_pixels, const float* d_background,
                      float* d_image, float* d_mask);
 
+/* r3dg_view_unpack_masked: the same for a view whose mask is a file of its own (the NeILF layout: scene/utils.py:52-57,
+ *   dataset_readers.py:358-364): d_pixels [H,W,3] uint8 and d_mask_bytes [H,W] uint8 (the mask file as 8-bit grey) -> d_image
+ *   [3,H,W] and d_mask [1,H,W] (NULL: not wanted).  m = (byte > 0) ? 1 : 0 (`mask[mask > 0.5] = 1` on the float of the byte),
+ *   image = (float)((byte / 255 in float64) * m) clamped to [0,1], mask = m.  No background: the reader composites none for this
+ *   layout.  One launch, a lane = 4 consecutive pixels (12 bytes of pixels and 4 mask bytes in, one 16-byte store per plane);
+ *   misaligned pointers and the last lane take narrower accesses of their own bytes only.  Nothing synchronises; no atomics. */
+int r3dg_view_unpack_masked(void* stream, int width, int height, const uint8_t* d_pixels, const uint8_t* d_mask_bytes,
+                            float* d_image, float* d_mask);
+
+/* r3dg_view_resize: a stored view at another resolution, as the reference's loadCam makes it (utils/camera_utils.py:13-58,
+ *   scene/cameras.py:34): d_pixels [H,W,C] uint8 (C = 4: RGBA over d_background; C = 3: RGB, d_background not read) and
+ *   d_mask_bytes [H,W] uint8 (C = 3 only; NULL: no mask file) -> d_image [3,out_height,out_width] and d_mask
+ *   [1,out_height,out_width] (NULL: not wanted; all ones for RGB without a mask file).  Order: the composite of r3dg_view_unpack /
+ *   r3dg_view_unpack_masked at full size rounded to float32, the separable antialiased bilinear filter of
+ *   torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=True) with float64 weights and float32 sums,
+ *   clamp to [0,1]; the mask by nearest neighbour from the full-size float mask, src = min(floor(dst * float32(in / out)), in - 1).
+ *   1 <= in / out <= R3DG_VIEW_RESIZE_MAX_SCALE on both axes (no upscaling; the tap count is bounded); d_pixels and d_mask_bytes
+ *   16-byte aligned; no byte outside the arrays is read.  One launch (64 x 8 output pixels per workgroup, both passes through
+ *   LDS).  Nothing synchronises; no atomics.  Same size limits as r3dg_relight_quantize. */
+#define R3DG_VIEW_RESIZE_MAX_SCALE 16
+int r3dg_view_resize(void* stream, int width, int height, int channels, const uint8_t* d_pixels, const uint8_t* d_mask_bytes,
+                     const float* d_background, int out_width, int out_height, float* d_image, float* d_mask);
+
 /* ---- densification bookkeeping -------------------------------------------------------------------
  * r3dg_densify_accumulate: GaussianModel.add_densification_stats (scene/gaussian_model.py:931-937) + the max-radii
  *   update of train.py:164-165, one pass.  The visibility filter is radii > 0 (render.py / neilf.py `visibility_filter`).

@@ -37,6 +37,7 @@ EXTRA = {
     "simple_knn.hip": ["-ffp-contract=off"],
     "densify.hip": ["-ffp-contract=off"],         # clone / split / prune decisions are fp32 comparisons
     "view_store.hip": ["-ffp-contract=off"],      # the reader's float64 composite, every operation rounded on its own
+    "view_resize.hip": ["-ffp-contract=off"],     # the same composite in front of the filter; float64 tap weights as written
     "shading.hip": SHADING_FLAGS,
     "shading_frs.hip": SHADING_FLAGS,
     "shading_relight.hip": SHADING_FLAGS,

@@ -104,4 +104,36 @@ int r3dg_view_unpack(void* stream_, int width, int height, int channels, const u
     });
 }
 
+int r3dg_view_unpack_masked(void* stream_, int width, int height, const uint8_t* pixels, const uint8_t* mask_bytes, float* image,
+                            float* mask)
+{
+    if (width < 0 || height < 0) return invalid("view_unpack_masked: bad shape");
+    if ((long long)width * height == 0) return R3DG_OK;
+    if ((long long)width * height >= (1ll << 31)) return invalid("view_unpack_masked: image too large");
+    if (!pixels || !mask_bytes || !image) return invalid("view_unpack_masked: null buffer");
+    return guarded([&]() -> int {
+        launch_view_unpack_masked((hipStream_t)stream_, width, height, pixels, mask_bytes, image, mask);
+        return R3DG_OK;
+    });
+}
+
+int r3dg_view_resize(void* stream_, int width, int height, int channels, const uint8_t* pixels, const uint8_t* mask_bytes,
+                     const float* background, int out_width, int out_height, float* image, float* mask)
+{
+    if (width < 1 || height < 1 || (channels != 3 && channels != 4)) return invalid("view_resize: bad shape (3 or 4 channels)");
+    if (out_width < 1 || out_height < 1 || out_width > width || out_height > height)
+        return invalid("view_resize: the target is 1 x 1 at least and no larger than the source (no upscaling)");
+    if ((long long)out_width * R3DG_VIEW_RESIZE_MAX_SCALE < width || (long long)out_height * R3DG_VIEW_RESIZE_MAX_SCALE < height)
+        return invalid("view_resize: a scale above 16");
+    if ((long long)width * height >= (1ll << 31)) return invalid("view_resize: image too large");
+    if (!pixels || !image || (channels == 4 && !background)) return invalid("view_resize: null buffer");
+    if (channels == 4 && mask_bytes) return invalid("view_resize: an RGBA view has its mask in the alpha channel");
+    if (((size_t)pixels & 15) || ((size_t)mask_bytes & 15)) return invalid("view_resize: the byte arrays must be 16-byte aligned");
+    return guarded([&]() -> int {
+        launch_view_resize((hipStream_t)stream_, width, height, channels, pixels, mask_bytes, background, out_width, out_height,
+                           image, mask);
+        return R3DG_OK;
+    });
+}
+
 }  // extern "C"

@@ -243,6 +243,13 @@ void launch_relight_quantize(hipStream_t s, int W, int H, int C, const float* im
 // view_store.hip: 8-bit pixels [H,W,C] of a stored ground-truth view -> image [3,H,W] over the background + mask [1,H,W] (or NULL)
 void launch_view_unpack(hipStream_t s, int W, int H, int C, const uint8_t* pixels, const float* background, float* image,
                         float* mask);
+// ... the same for RGB pixels [H,W,3] with a one-byte mask plane [H,W] of their own (no background)
+void launch_view_unpack_masked(hipStream_t s, int W, int H, const uint8_t* pixels, const uint8_t* mask_bytes, float* image,
+                               float* mask);
+// view_resize.hip: composite at full size, antialiased bilinear downscale to [3,OH,OW], clamp; the mask (or NULL) by nearest
+// neighbour.  C = 4: RGBA over the background; C = 3: RGB, with mask_bytes [H,W] or NULL.  Both byte arrays 16-byte aligned.
+void launch_view_resize(hipStream_t s, int W, int H, int C, const uint8_t* pixels, const uint8_t* mask_bytes, const float* background,
+                        int OW, int OH, float* image, float* mask);
 // ssim.hip: the value-only SSIM tiling; tile_sums [C * ceil(W/32) * ceil(H/32)][2]
 void launch_eval_metric_tiles(hipStream_t s, int W, int H, int C, const float* pred, const float* gt, const float* mask,
                               const float* fill, int fill_is_image, double* tile_sums);

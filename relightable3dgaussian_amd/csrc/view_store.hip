@@ -12,6 +12,11 @@
 //       store    one 16-byte store per plane: a wave writes 1 KB contiguous per plane.  A plane whose lane address is not 16-byte
 //                aligned (the output pointer itself, or N % 4 != 0 for planes 1 and 2) and the last lane store single floats.
 //   256-thread workgroups, no LDS, no atomics; the 4 pixels live in named registers (no indexed local array): no scratch.
+//
+//   view_unpack_masked_kernel   (r3dg_hip.h "r3dg_view_unpack_masked") a view whose mask is a file of its own -- the NeILF layout,
+//       scene/utils.py:52-57, dataset_readers.py:358-364: RGB pixels [H,W,3] and a one-byte mask plane [H,W].  Same lane shape:
+//       three 4-byte loads of the pixels and one 4-byte load of the mask bytes, one 16-byte store per plane.  m = byte > 0,
+//       image = (float)((byte / 255 in float64) * m) clamped, mask = m; no background (the reader composites none here).
 #include "launchers.hpp"
 
 namespace r3dg {
@@ -98,7 +103,67 @@ view_unpack_kernel(uint32_t N, const uint8_t* __restrict__ pixels, const float* 
     if (mask) store_lane(mask + first, n, m0, m1, m2, m3);
 }
 
+// a pixel of the NeILF layout: px as unpack_pixel takes it (alpha bits unused), mb its mask byte
+__device__ __forceinline__ void unpack_masked_pixel(uint32_t px, uint32_t mb, float& r, float& g, float& b, float& m)
+{
+    const double md = mb ? 1.0 : 0.0;                                           // mask[mask > 0.5] = 1 on the float of the byte
+    r = clamp01((float)__dmul_rn(__ddiv_rn((double)(px & 255u), 255.0), md));
+    g = clamp01((float)__dmul_rn(__ddiv_rn((double)((px >> 8) & 255u), 255.0), md));
+    b = clamp01((float)__dmul_rn(__ddiv_rn((double)((px >> 16) & 255u), 255.0), md));
+    m = (float)md;
+}
+
+__global__ void __launch_bounds__(256)
+view_unpack_masked_kernel(uint32_t N, const uint8_t* __restrict__ pixels, const uint8_t* __restrict__ mask_bytes,
+                          float* __restrict__ image, float* __restrict__ mask)
+{
+    const size_t first = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;          // the lane's first pixel
+    if (first >= N) return;
+    const int n = (N - first < 4) ? (int)(N - first) : 4;
+    const uint8_t* src = pixels + first * 3;
+    const uint8_t* msrc = mask_bytes + first;
+    uint32_t p0 = 0, p1 = 0, p2 = 0, p3 = 0, mw = 0;
+    if (n == 4 && ((size_t)src & 3) == 0) {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(src);
+        const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];                          // bytes r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+        p0 = w0 & 0x00ffffffu;
+        p1 = (w0 >> 24) | ((w1 & 0x0000ffffu) << 8);
+        p2 = (w1 >> 16) | ((w2 & 0x000000ffu) << 16);
+        p3 = w2 >> 8;
+    } else {
+        p0 = load_pixel_bytes<3>(src);
+        if (n > 1) p1 = load_pixel_bytes<3>(src + 3);
+        if (n > 2) p2 = load_pixel_bytes<3>(src + 6);
+        if (n > 3) p3 = load_pixel_bytes<3>(src + 9);
+    }
+    if (n == 4 && ((size_t)msrc & 3) == 0) {
+        mw = *reinterpret_cast<const uint32_t*>(msrc);
+    } else {
+        mw = msrc[0];
+        if (n > 1) mw |= (uint32_t)msrc[1] << 8;
+        if (n > 2) mw |= (uint32_t)msrc[2] << 16;
+        if (n > 3) mw |= (uint32_t)msrc[3] << 24;
+    }
+    float r0, g0, b0, m0, r1, g1, b1, m1, r2, g2, b2, m2, r3, g3, b3, m3;
+    unpack_masked_pixel(p0, mw & 255u, r0, g0, b0, m0);
+    unpack_masked_pixel(p1, (mw >> 8) & 255u, r1, g1, b1, m1);
+    unpack_masked_pixel(p2, (mw >> 16) & 255u, r2, g2, b2, m2);
+    unpack_masked_pixel(p3, mw >> 24, r3, g3, b3, m3);
+    store_lane(image + first, n, r0, r1, r2, r3);
+    store_lane(image + (size_t)N + first, n, g0, g1, g2, g3);
+    store_lane(image + 2 * (size_t)N + first, n, b0, b1, b2, b3);
+    if (mask) store_lane(mask + first, n, m0, m1, m2, m3);
+}
+
 }  // namespace
+
+void launch_view_unpack_masked(hipStream_t s, int W, int H, const uint8_t* pixels, const uint8_t* mask_bytes, float* image,
+                               float* mask)
+{
+    const size_t N = (size_t)W * H, lanes = (N + 3) / 4;                         // (N < 2^31: the caller has checked)
+    view_unpack_masked_kernel<<<(unsigned)((lanes + 255) / 256), 256, 0, s>>>((uint32_t)N, pixels, mask_bytes, image, mask);
+    check_launch(s, false, "view_unpack_masked_kernel");
+}
 
 void launch_view_unpack(hipStream_t s, int W, int H, int C, const uint8_t* pixels, const float* background, float* image,
                         float* mask)

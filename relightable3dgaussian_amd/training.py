@@ -1,10 +1,17 @@
-"""The reference's train.py for a NeRF-synthetic (Blender) dataset directory, on the fused iterations:
+"""The reference's train.py for a NeRF-synthetic (Blender) or a NeILF-format (DTU / TnT) dataset directory, on the fused iterations:
 
     python -m relightable3dgaussian_amd.training -s DATA -m OUT -t render --eval
     python -m relightable3dgaussian_amd.training -s DATA -m OUT/neilf -t neilf -c OUT/chkpnt30000.pth --iterations 40000 --eval
 
-Stage 1 (`-t render`): `transforms_train.json` and its images into a dataset.ViewStore (the views stay on the device as 8-bit
-pixels; one unpack launch per iteration), the extent of synthetic.cameras_extent, dataset.initial_points ->
+The layout is picked as scene/__init__.py:43-61 picks it: `transforms_train.json` -> Blender (dataset.read_transforms,
+dataset.initial_points); `inputs/sfm_scene.json` -> NeILF (dataset.read_neilf_scene, dataset.initial_points_neilf, the views' mask
+files, the off-centre projection of their fx, fy, cx, cy); anything else raises.  `-r / --resolution` (default -1, as
+arguments/__init__.py:45) is loadCam's, for both layouts and for the test split: dataset.ViewStore resizes such views once, at load.
+UNDER THE DEFAULT, FILES WIDER THAN 1600 PIXELS ARE NOW RESCALED TO 1600 as the reference rescales them (before, every file trained
+at its own size); files up to 1600 pixels wide are treated exactly as before.
+
+Stage 1 (`-t render`): the train split's images into a dataset.ViewStore (the views stay on the device as 8-bit
+pixels; one unpack launch per iteration), the extent of synthetic.cameras_extent, the initial points ->
 train_loop.create_from_points -> train_loop.train_stage1 with the view pick of train.py:115-119.  Stage 2 (`-t neilf -c CKPT`,
 train.py:52-72): checkpoint.restore(CKPT, pbr=True), the environment texture light_init * rand(1, R, 2R, 3) (or the texture of
 `env_light_<basename of CKPT>` beside CKPT), train_loop.train_stage2 for `--iterations` minus the checkpoint's iteration count,
@@ -19,7 +26,7 @@ One progress line every --log_interval iterations (step.loss(): the only host re
 Arguments carry the names and defaults of the reference's arguments/__init__.py.  The lambdas the fused steps implement become
 their loss weights; every other non-zero lambda RAISES before anything is loaded (`loss_weights_of`).
 
-Out of scope: the COLMAP / NeILF / Synthetic4Relight / Stanford-ORB readers; `--resolution` other than the files' own; MVS depth /
+Out of scope: the COLMAP / Synthetic4Relight / Stanford-ORB readers; `resolution_scale` other than 1 and upscaling; MVS depth /
 normal maps (hence no lambda_depth / lambda_normal_mvs_depth); cfg_args, cameras.json, TensorBoard, LPIPS; data parallelism in this
 driver (train_loop's loops take a process group; this command does not start one).  THE ONE KNOWN DIFFERENCE FROM THE REFERENCE
 SCHEDULE: train.py:107-108 raises the active SH degree by one every 1000 iterations, the fused steps train degree 3 from the
@@ -74,8 +81,13 @@ def loss_weights_of(args):
 
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m relightable3dgaussian_amd.training",
-                                description="Train Relightable 3D Gaussians from a Blender-format dataset on the fused iterations")
-    p.add_argument("-s", "--source_path", required=True, help="dataset root (transforms_train.json, transforms_test.json)")
+                                description="Train Relightable 3D Gaussians from a Blender- or NeILF-format dataset on the fused "
+                                            "iterations")
+    p.add_argument("-s", "--source_path", required=True,
+                   help="dataset root: Blender format (transforms_train.json, transforms_test.json) or NeILF format "
+                        "(inputs/sfm_scene.json)")
+    p.add_argument("-r", "--resolution", type=int, default=-1,
+                   help="1, 2, 4, 8: downscale by that factor; -1: rescale files wider than 1600 pixels to 1600; else the target width")
     p.add_argument("-m", "--model_path", required=True, help="output directory")
     p.add_argument("-t", "--type", choices=["render", "neilf"], default="render")
     p.add_argument("-c", "--checkpoint", default=None, help="chkpnt<it>.pth to start from (required for -t neilf)")
@@ -149,10 +161,24 @@ class _Stage1Model:
         return self.step.shs.detach()
 
 
-def _split(args, split, device):
-    records = dataset.read_transforms(args.source_path, split)
-    store = dataset.ViewStore([r["path"] for r in records], device)
-    return records, store, dataset.cameras_of(records, store.sizes, device)
+def _split(args, records, device, background):
+    """records -> (records, ViewStore at --resolution, cameras with the intrinsics of the resized views)."""
+    store = dataset.ViewStore([r["path"] for r in records], device, mask_paths=[r.get("mask_path") for r in records],
+                              resolution=args.resolution, background=background)
+    return records, store, dataset.cameras_of(records, store.sizes, device, store.scales)
+
+
+def read_scene(args):
+    """(layout, train records, test records or None, initial points callable) of --source_path, the layout picked as
+    scene/__init__.py:43-61 picks it: transforms_train.json -> Blender, inputs/sfm_scene.json -> NeILF, else a RuntimeError."""
+    root = args.source_path
+    layout = dataset.detect_layout(root)
+    if layout == "blender":
+        train = dataset.read_transforms(root, "train")
+        test = dataset.read_transforms(root, "test") if args.eval else None
+        return layout, train, test, lambda: dataset.initial_points(root, args.seed)
+    train, test = dataset.read_neilf_scene(root, args.eval)
+    return layout, train, (test if args.eval else None), lambda: dataset.initial_points_neilf(root, args.seed)
 
 
 @torch.no_grad()
@@ -173,7 +199,7 @@ def evaluate_step(step, args, cameras, store, background):
     for v, cam in enumerate(cameras):
         pbr = renderer.frame(cam, background, outputs=("pbr",))["pbr"]
         gt, mask = store.fetch(v, background)
-        if store.has_alpha:
+        if store.has_masks:
             ev.add("pbr", pbr, gt, mask, background)
         else:
             ev.add("pbr", pbr, gt)
@@ -183,7 +209,8 @@ def evaluate_step(step, args, cameras, store, background):
 
 def train(args):
     """Run the command described by `args` (build_parser().parse_args(...)).  -> namespace: step, history, views (the view of
-    every iteration), files (what was written), metrics (None without --eval), first_iteration, env_init (stage 2)."""
+    every iteration), files (what was written), metrics (None without --eval), first_iteration, env_init (stage 2), store, cameras,
+    test_cameras (None without --eval)."""
     weights = loss_weights_of(args)                                   # (raises before anything is loaded)
     stage2 = args.type == "neilf"
     if stage2 and not args.checkpoint:
@@ -194,8 +221,9 @@ def train(args):
     sch = schedule_of(args)
     value = 1.0 if args.white_background else 0.0
     background = torch.full((3,), value, dtype=torch.float32, device=device)
-    records, store, cameras = _split(args, "train", device)
-    test = _split(args, "test", device) if args.eval else None
+    _layout, train_records, test_records, initial_points = read_scene(args)
+    records, store, cameras = _split(args, train_records, device, background)
+    test = _split(args, test_records, device, background) if args.eval else None
     extent, _ = synthetic.cameras_extent(cameras)
     masks = store.masks(background)
     seen, files = [], []
@@ -206,7 +234,8 @@ def train(args):
         return seen[-1]
 
     os.makedirs(args.model_path, exist_ok=True)
-    result = types.SimpleNamespace(views=seen, files=files, metrics=None, env_init=None, store=store, extent=extent)
+    result = types.SimpleNamespace(views=seen, files=files, metrics=None, env_init=None, store=store, extent=extent, cameras=cameras,
+                                   test_cameras=test[2] if test else None)
     first = 0
 
     def on_iteration(it, step):
@@ -237,7 +266,7 @@ def train(args):
                 files.append(path)
 
     if not stage2:
-        points, colors, normals = dataset.initial_points(args.source_path, args.seed)
+        points, colors, normals = initial_points()
         init = train_loop.create_from_points(torch.from_numpy(points.copy()), torch.from_numpy(colors.copy()),
                                              torch.from_numpy(normals.copy()), device=device)
         step, history = train_loop.train_stage1(init, cameras, store.images(background), background, extent, schedule=sch,
