@@ -185,10 +185,13 @@ s1_activate_backward_kernel(int P, const float* __restrict__ xyz, const float* _
         const float g[4] = {dL_drot[i4], dL_drot[i4 + 1], dL_drot[i4 + 2], dL_drot[i4 + 3]};
         const float n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
         if (n > 1e-12f) {
+            // u = q / n by DIVISION: a quaternion along one axis gives u = +-1 exactly, so its radial gradient g - u (u.g) is exactly
+            // 0, as in exact arithmetic (q * (1/n) * (1/n) left a rounding residue of 1e-7 |g| there: tests/test_glue_kernels_gpu.py)
             const float inv = 1.f / n;
-            const float d = (q[0] * g[0] + q[1] * g[1] + q[2] * g[2] + q[3] * g[3]) * inv * inv;
+            const float u[4] = {q[0] / n, q[1] / n, q[2] / n, q[3] / n};
+            const float d = u[0] * g[0] + u[1] * g[1] + u[2] * g[2] + u[3] * g[3];
 #pragma unroll
-            for (int c = 0; c < 4; c++) g_rotation[i4 + c] = (g[c] - q[c] * d) * inv;
+            for (int c = 0; c < 4; c++) g_rotation[i4 + c] = (g[c] - u[c] * d) * inv;
         } else {
 #pragma unroll
             for (int c = 0; c < 4; c++) g_rotation[i4 + c] = g[c] * 1e12f;
