@@ -867,6 +867,39 @@ int r3dg_view_unpack_masked(void* stream, int width, int height, const uint8_t* 
 int r3dg_view_resize(void* stream, int width, int height, int channels, const uint8_t* d_pixels, const uint8_t* d_mask_bytes,
                      const float* d_background, int out_width, int out_height, float* d_image, float* d_mask);
 
+/* r3dg_exr_unpack_chunks: the chunks of one OpenEXR scanline view (NONE / ZIPS / ZIP compression, HALF or FLOAT samples) after the
+ *   host's zlib inflate -> the planar view d_planes [kept,height,width] in the file's own sample type (bytes_per_sample = 2: half
+ *   bit patterns, 4: float bit patterns), never converted: bit for bit what exr.decode_reference makes of the file, NaN payloads
+ *   and denormals included.  d_inflated: `inflated_bytes` bytes, every chunk at a 16-byte-aligned offset; d_chunk_table
+ *   [chunks,4] int32 per chunk: byte offset into d_inflated, first row, row count, stored-raw flag (non-zero: the chunk was not
+ *   compressed and carries no predictor and no byte split; every chunk of an uncompressed file).  A chunk holds `row count` rows
+ *   of `file_channels` planes of `width` little-endian samples; d_kept_channels [kept] int32: the file-channel index of each
+ *   output plane.  The device undoes the predictor (t[i] = t[i-1] + d[i] - 128 mod 256 over the whole chunk), the split (raw[2j]
+ *   = t[j], raw[2j+1] = t[half+j]) and the row / channel planarisation, by a two-pass tile-sum scan: d_tile_sums (scratch, at
+ *   least chunks * 2 * ceil(max_chunk_rows * width * file_channels * bytes_per_sample / 2 / R3DG_EXR_TILE) uint32,
+ *   `tile_sums_count` of them offered) takes the byte sums of every tile in the first launch, the second scans, interleaves and
+ *   stores.  max_chunk_rows: 16 for ZIP, 1 for ZIPS / NONE; a table row with more rows, with rows outside [0, height), with an
+ *   offset off the 16-byte grid or with bytes outside d_inflated is SKIPPED (nothing is read or written for it); rows no chunk
+ *   covers keep what d_planes held.  Two launches; nothing synchronises; no atomics. */
+#define R3DG_EXR_TILE 4096
+#define R3DG_EXR_MAX_KEPT 8
+#define R3DG_EXR_MAX_TILES 32768
+int r3dg_exr_unpack_chunks(void* stream, int width, int height, int file_channels, int bytes_per_sample, int chunks,
+                           int max_chunk_rows, const uint8_t* d_inflated, long long inflated_bytes, const int32_t* d_chunk_table,
+                           int kept, const int32_t* d_kept_channels, uint32_t* d_tile_sums, long long tile_sums_count,
+                           void* d_planes);
+
+/* r3dg_view_unpack_hdr: one resident HDR view of the device view store, d_view [3,H,W] planar R, G, B (is_half != 0: half, else
+ *   float: what r3dg_exr_unpack_chunks wrote), d_mask_bytes [H,W] uint8 (the view's mask file as 8-bit grey; NULL: no mask file),
+ *   d_background 3 floats -> d_image [3,H,W] float and d_mask [1,H,W] float (NULL: not wanted), as the reference's
+ *   Synthetic4Relight reader makes them (scene/utils.py:40-46, dataset_readers.py:551-555, cameras.py:34): y = x > 0.0031308 ?
+ *   pow(x, 1/2.4) * 1.055 - 0.055 : 12.92 * x in float32 with the constants rounded to float32 and every operation rounded on its
+ *   own, m = byte > 0, image = m ? clamp(y, 0, 1) : background, mask = m.  Without d_mask_bytes the image alone and an all-ones
+ *   mask.  A NaN sample stays NaN.  One launch, a lane = one pixel; nothing synchronises; no atomics.  Same size limits as
+ *   r3dg_relight_quantize. */
+int r3dg_view_unpack_hdr(void* stream, int width, int height, int is_half, const void* d_view, const uint8_t* d_mask_bytes,
+                         const float* d_background, float* d_image, float* d_mask);
+
 /* ---- densification bookkeeping -------------------------------------------------------------------
  * r3dg_densify_accumulate: GaussianModel.add_densification_stats (scene/gaussian_model.py:931-937) + the max-radii
  *   update of train.py:164-165, one pass.  The visibility filter is radii > 0 (render.py / neilf.py `visibility_filter`).

@@ -38,6 +38,7 @@ EXTRA = {
     "densify.hip": ["-ffp-contract=off"],         # clone / split / prune decisions are fp32 comparisons
     "view_store.hip": ["-ffp-contract=off"],      # the reader's float64 composite, every operation rounded on its own
     "view_resize.hip": ["-ffp-contract=off"],     # the same composite in front of the filter; float64 tap weights as written
+    "exr_unpack.hip": ["-ffp-contract=off"],      # the reader's float32 sRGB curve: the multiply and the subtraction round apart
     "shading.hip": SHADING_FLAGS,
     "shading_frs.hip": SHADING_FLAGS,
     "shading_relight.hip": SHADING_FLAGS,

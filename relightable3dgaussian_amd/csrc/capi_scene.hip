@@ -136,4 +136,45 @@ int r3dg_view_resize(void* stream_, int width, int height, int channels, const u
     });
 }
 
+int r3dg_exr_unpack_chunks(void* stream_, int width, int height, int file_channels, int bytes_per_sample, int chunks,
+                           int max_chunk_rows, const uint8_t* inflated, long long inflated_bytes, const int32_t* chunk_table,
+                           int kept, const int32_t* kept_channels, uint32_t* tile_sums, long long tile_sums_count, void* planes)
+{
+    if (width < 1 || height < 1 || file_channels < 1 || chunks < 0 || max_chunk_rows < 1 || inflated_bytes < 0)
+        return invalid("exr_unpack_chunks: bad shape");
+    if (bytes_per_sample != 2 && bytes_per_sample != 4) return invalid("exr_unpack_chunks: samples are 2 (half) or 4 (float) bytes");
+    if (kept < 1 || kept > R3DG_EXR_MAX_KEPT) return invalid("exr_unpack_chunks: 1 to 8 kept channels");
+    if (chunks > 65535) return invalid("exr_unpack_chunks: more than 65535 chunks");
+    if ((long long)width * height >= (1ll << 31)) return invalid("exr_unpack_chunks: image too large");
+    if ((long long)max_chunk_rows * width * file_channels * bytes_per_sample >= (1ll << 31) ||
+        inflated_bytes >= (1ll << 32))
+        return invalid("exr_unpack_chunks: chunk or view too large");
+    if (chunks == 0) return R3DG_OK;
+    const size_t tiles = exr_tiles_per_chunk(width, file_channels, bytes_per_sample, max_chunk_rows);
+    if (tiles > R3DG_EXR_MAX_TILES) return invalid("exr_unpack_chunks: chunk too large");
+    if (tile_sums_count < 0 || (size_t)tile_sums_count < (size_t)chunks * 2 * tiles)
+        return invalid("exr_unpack_chunks: the tile sum scratch is too small");
+    if (!inflated || !chunk_table || !kept_channels || !tile_sums || !planes) return invalid("exr_unpack_chunks: null buffer");
+    if (((size_t)inflated & 15) || ((size_t)planes & 3)) return invalid("exr_unpack_chunks: misaligned buffer");
+    return guarded([&]() -> int {
+        launch_exr_unpack_chunks((hipStream_t)stream_, width, height, file_channels, bytes_per_sample, chunks, max_chunk_rows,
+                                 inflated, inflated_bytes, chunk_table, kept, kept_channels, tile_sums, planes);
+        return R3DG_OK;
+    });
+}
+
+int r3dg_view_unpack_hdr(void* stream_, int width, int height, int is_half, const void* view, const uint8_t* mask_bytes,
+                         const float* background, float* image, float* mask)
+{
+    if (width < 0 || height < 0) return invalid("view_unpack_hdr: bad shape");
+    if ((long long)width * height == 0) return R3DG_OK;
+    if ((long long)width * height >= (1ll << 31)) return invalid("view_unpack_hdr: image too large");
+    if (!view || !background || !image) return invalid("view_unpack_hdr: null buffer");
+    if ((size_t)view & (is_half ? 1 : 3)) return invalid("view_unpack_hdr: misaligned view");
+    return guarded([&]() -> int {
+        launch_view_unpack_hdr((hipStream_t)stream_, width, height, is_half, view, mask_bytes, background, image, mask);
+        return R3DG_OK;
+    });
+}
+
 }  // extern "C"

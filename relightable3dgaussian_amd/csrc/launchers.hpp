@@ -250,6 +250,15 @@ void launch_view_unpack_masked(hipStream_t s, int W, int H, const uint8_t* pixel
 // neighbour.  C = 4: RGBA over the background; C = 3: RGB, with mask_bytes [H,W] or NULL.  Both byte arrays 16-byte aligned.
 void launch_view_resize(hipStream_t s, int W, int H, int C, const uint8_t* pixels, const uint8_t* mask_bytes, const float* background,
                         int OW, int OH, float* image, float* mask);
+// exr_unpack.hip: inflated OpenEXR chunks -> the planar view [kept,H,W] in the file's sample type (B bytes per sample); tile_sums
+// holds chunks * 2 * exr_tiles_per_chunk(...) uint32 of scratch
+size_t exr_tiles_per_chunk(int W, int C, int B, int max_rows);
+void launch_exr_unpack_chunks(hipStream_t s, int W, int H, int C, int B, int chunks, int max_rows, const uint8_t* inflated,
+                              long long inflated_bytes, const int32_t* table, int kept, const int32_t* kept_channels,
+                              uint32_t* tile_sums, void* planes);
+// ... and a resident planar HDR view [3,H,W] (half or float) + its mask bytes (or NULL) -> image [3,H,W] + mask [1,H,W] (or NULL)
+void launch_view_unpack_hdr(hipStream_t s, int W, int H, int is_half, const void* view, const uint8_t* mask_bytes,
+                            const float* background, float* image, float* mask);
 // ssim.hip: the value-only SSIM tiling; tile_sums [C * ceil(W/32) * ceil(H/32)][2]
 void launch_eval_metric_tiles(hipStream_t s, int W, int H, int C, const float* pred, const float* gt, const float* mask,
                               const float* fill, int fill_is_image, double* tile_sums);

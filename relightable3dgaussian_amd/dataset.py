@@ -21,8 +21,12 @@ installed where this was written; tools/reference_shims.py stands in for it with
 `initial_points_neilf` are the readers' point clouds (fetchPly / storePly, :125-160; the 100 000 random points of :288-299; the
 bbox-rescaled sparse.ply of :408-425), `reference_view_order` the view pick of train.py:115-119.
 
-Out of scope: the COLMAP, Synthetic4Relight and Stanford-ORB readers; `resolution_scale` other than 1 and upscaling; MVS depth /
-normal maps (`<root>/extra`); `cfg_args`, `cameras.json`.
+`read_syn4relight` is the Synthetic4Relight reader (readCamerasFromTransforms3, :526-565): its train split is OpenEXR views
+(`<file_path>_rgb.exr` + `<file_path>_mask.png`), which hdr_views.HdrViewStore keeps on the device in the files' own sample type
+(exr.py parses the container, csrc/exr_unpack.hip decodes); its test split (`<file_path>_rgba.png`) goes through ViewStore.
+
+Out of scope: the COLMAP and Stanford-ORB readers; `resolution_scale` other than 1 and upscaling; MVS depth / normal maps
+(`<root>/extra`); `cfg_args`, `cameras.json`.
 """
 import collections
 import collections.abc
@@ -87,13 +91,48 @@ NEILF_TEST_INDEXES = (2, 12, 17, 30, 34)      # readNeILFInfo's validation_index
 
 
 def detect_layout(root):
-    """"blender" or "neilf", decided as scene/__init__.py:43-61 decides it; RuntimeError naming both for anything else."""
+    """"blender", "syn4relight" or "neilf", decided as scene/__init__.py:43-61 decides it (a transforms_train.json under a path that
+    contains "Synthetic4Relight" is that dataset, :51); RuntimeError naming the layouts for anything else."""
     if os.path.exists(os.path.join(root, "transforms_train.json")):
-        return "blender"
+        return "syn4relight" if "Synthetic4Relight" in str(root) else "blender"
     if os.path.exists(os.path.join(root, "inputs", "sfm_scene.json")):
         return "neilf"
     raise RuntimeError("%s: neither a Blender-format dataset (transforms_train.json) nor a NeILF-format one "
                        "(inputs/sfm_scene.json); these are the two layouts this driver reads" % root)
+
+
+def read_syn4relight(root, split):
+    """`<root>/transforms_<split>.json` of a Synthetic4Relight scene -> records as read_transforms makes them, restating
+    readCamerasFromTransforms3 (scene/dataset_readers.py:526-565): the same flip of columns 1..2, inverse and transposed R; FovX =
+    camera_angle_x and FovY = focal2fov(fov2focal(FovX, H), W) exactly as :557 writes it (the image HEIGHT is the focal-length
+    base and the WIDTH goes back in).  split "train": path = `<file_path>_rgb.exr` (its size from the EXR header: exr.read_header,
+    which raises for a file it cannot decode) and mask_path = `<file_path>_mask.png` when that file exists (else None) -- the views
+    of hdr_views.HdrViewStore.  Any other split: path = `<file_path>_rgba.png`, no mask_path -- the views of ViewStore, whose mask
+    is the alpha channel (the reference thresholds the file's grey value instead, :536,552; the two agree wherever colour sits
+    only under non-zero alpha)."""
+    from . import exr
+    with open(os.path.join(root, "transforms_%s.json" % split)) as fh:
+        contents = json.load(fh)
+    fovx = contents["camera_angle_x"]
+    records = []
+    for frame in contents["frames"]:
+        stem = os.path.join(root, frame["file_path"])
+        c2w = np.array(frame["transform_matrix"], dtype=np.float64)
+        c2w[:3, 1:3] *= -1                                    # OpenGL/Blender camera axes -> COLMAP (Y down, Z forward)
+        w2c = np.linalg.inv(c2w)
+        if split == "train":
+            path, mask_path = stem + "_rgb.exr", stem + "_mask.png"
+            header = exr.read_header(path)
+            h, w = header.height, header.width
+        else:
+            path, mask_path = stem + "_rgba.png", None
+            h, w, _ = probe(path)
+        focal = h / (2 * math.tan(fovx / 2))                  # fov2focal(fovx, image.shape[0])
+        fovy = 2 * math.atan(w / (2 * focal))                 # focal2fov(., image.shape[1])
+        records.append(dict(name=os.path.splitext(os.path.basename(path))[0], path=path, R=np.transpose(w2c[:3, :3]).copy(),
+                            T=w2c[:3, 3].copy(), FovX=fovx, FovY=fovy, width=w, height=h,
+                            mask_path=mask_path if mask_path and os.path.exists(mask_path) else None))
+    return records
 
 
 def _bbox_transform(sfm_scene):

@@ -16,8 +16,9 @@ Arguments are those of relighting.py:88-101 plus --rotate-sh (compose.assemble),
 capture raises.
 
 Environment maps: `.npy` ([He,We,3] linear radiance) and Radiance `.hdr` (RGBE, flat or run-length encoded scanlines) are read
-as LINEAR radiance; `.exr` raises.  Note the difference: the reference treats every non-EXR file as an 8-bit sRGB image
-(scene/envmap.py:23-24: srgb_to_rgb(imread(path) / 255)); this tool does not."""
+as LINEAR radiance; `.exr` raises (np.save("envmap3.npy", exr.read_image("envmap3.exr")) is the bridge for the
+NONE / ZIPS / ZIP scanline files exr.py decodes; PIZ files, the reference's envmap6 / envmap12, are not decoded).  Note the
+difference: the reference treats every non-EXR file as an 8-bit sRGB image (scene/envmap.py:23-24: srgb_to_rgb(imread(path) / 255)); this tool does not."""
 import argparse
 import math
 import os

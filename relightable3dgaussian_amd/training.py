@@ -1,12 +1,15 @@
-"""The reference's train.py for a NeRF-synthetic (Blender) or a NeILF-format (DTU / TnT) dataset directory, on the fused iterations:
+"""The reference's train.py for a NeRF-synthetic (Blender), a Synthetic4Relight or a NeILF-format (DTU / TnT) dataset directory, on
+the fused iterations:
 
     python -m relightable3dgaussian_amd.training -s DATA -m OUT -t render --eval
     python -m relightable3dgaussian_amd.training -s DATA -m OUT/neilf -t neilf -c OUT/chkpnt30000.pth --iterations 40000 --eval
 
 The layout is picked as scene/__init__.py:43-61 picks it: `transforms_train.json` -> Blender (dataset.read_transforms,
-dataset.initial_points); `inputs/sfm_scene.json` -> NeILF (dataset.read_neilf_scene, dataset.initial_points_neilf, the views' mask
+dataset.initial_points), or Synthetic4Relight when the path contains that name (:51; dataset.read_syn4relight: the train split
+is OpenEXR views, kept on the device as half / float samples by hdr_views.HdrViewStore and decoded there; the test split's
+`_rgba.png` files go through dataset.ViewStore; the same initial points); `inputs/sfm_scene.json` -> NeILF (dataset.read_neilf_scene, dataset.initial_points_neilf, the views' mask
 files, the off-centre projection of their fx, fy, cx, cy); anything else raises.  `-r / --resolution` (default -1, as
-arguments/__init__.py:45) is loadCam's, for both layouts and for the test split: dataset.ViewStore resizes such views once, at load.
+arguments/__init__.py:45) is loadCam's, for the 8-bit layouts and for the test split (an HdrViewStore raises for a scale other than 1): dataset.ViewStore resizes such views once, at load.
 UNDER THE DEFAULT, FILES WIDER THAN 1600 PIXELS ARE NOW RESCALED TO 1600 as the reference rescales them (before, every file trained
 at its own size); files up to 1600 pixels wide are treated exactly as before.
 
@@ -26,7 +29,7 @@ One progress line every --log_interval iterations (step.loss(): the only host re
 Arguments carry the names and defaults of the reference's arguments/__init__.py.  The lambdas the fused steps implement become
 their loss weights; every other non-zero lambda RAISES before anything is loaded (`loss_weights_of`).
 
-Out of scope: the COLMAP / Synthetic4Relight / Stanford-ORB readers; `resolution_scale` other than 1 and upscaling; MVS depth /
+Out of scope: the COLMAP / Stanford-ORB readers; OpenEXR files other than NONE / ZIPS / ZIP scanline files (PIZ above all); `resolution_scale` other than 1 and upscaling; MVS depth /
 normal maps (hence no lambda_depth / lambda_normal_mvs_depth); cfg_args, cameras.json, TensorBoard, LPIPS; data parallelism in this
 driver (train_loop's loops take a process group; this command does not start one).  THE ONE KNOWN DIFFERENCE FROM THE REFERENCE
 SCHEDULE: train.py:107-108 raises the active SH degree by one every 1000 iterations, the fused steps train degree 3 from the
@@ -81,7 +84,7 @@ def loss_weights_of(args):
 
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m relightable3dgaussian_amd.training",
-                                description="Train Relightable 3D Gaussians from a Blender- or NeILF-format dataset on the fused "
+                                description="Train Relightable 3D Gaussians from a Blender-, Synthetic4Relight- or NeILF-format dataset on the fused "
                                             "iterations")
     p.add_argument("-s", "--source_path", required=True,
                    help="dataset root: Blender format (transforms_train.json, transforms_test.json) or NeILF format "
@@ -162,20 +165,28 @@ class _Stage1Model:
 
 
 def _split(args, records, device, background):
-    """records -> (records, ViewStore at --resolution, cameras with the intrinsics of the resized views)."""
-    store = dataset.ViewStore([r["path"] for r in records], device, mask_paths=[r.get("mask_path") for r in records],
-                              resolution=args.resolution, background=background)
+    """records -> (records, view store at --resolution, cameras with the intrinsics of the resized views).  Records of OpenEXR
+    files (the Synthetic4Relight train split) get an hdr_views.HdrViewStore, all others a dataset.ViewStore."""
+    if all(r["path"].endswith(".exr") for r in records):
+        from . import hdr_views
+        kind = hdr_views.HdrViewStore
+    else:
+        kind = dataset.ViewStore
+    store = kind([r["path"] for r in records], device, mask_paths=[r.get("mask_path") for r in records],
+                 resolution=args.resolution, background=background)
     return records, store, dataset.cameras_of(records, store.sizes, device, store.scales)
 
 
 def read_scene(args):
     """(layout, train records, test records or None, initial points callable) of --source_path, the layout picked as
-    scene/__init__.py:43-61 picks it: transforms_train.json -> Blender, inputs/sfm_scene.json -> NeILF, else a RuntimeError."""
+    scene/__init__.py:43-61 picks it: transforms_train.json -> Blender (Synthetic4Relight under a path of that name),
+    inputs/sfm_scene.json -> NeILF, else a RuntimeError."""
     root = args.source_path
     layout = dataset.detect_layout(root)
-    if layout == "blender":
-        train = dataset.read_transforms(root, "train")
-        test = dataset.read_transforms(root, "test") if args.eval else None
+    if layout in ("blender", "syn4relight"):
+        read = dataset.read_transforms if layout == "blender" else dataset.read_syn4relight
+        train = read(root, "train")
+        test = read(root, "test") if args.eval else None
         return layout, train, test, lambda: dataset.initial_points(root, args.seed)
     train, test = dataset.read_neilf_scene(root, args.eval)
     return layout, train, (test if args.eval else None), lambda: dataset.initial_points_neilf(root, args.seed)
