@@ -588,6 +588,22 @@ int r3dg_stage2_normals_srgb(void* stream, int width, int height, const float* d
                              float cx, float cy, const float* d_opacity, const float* d_depth, float* d_pseudo_normal,
                              float* d_surface_xyz, const float* d_feature, const int32_t* d_n_contrib,
                              const float* d_background, float* d_srgb);
+/* The image-space tail of a stage-2 iteration in ONE launch: r3dg_stage2_normals_srgb, r3dg_ssim_forward_pair,
+ * r3dg_ssim_backward_pair (scales scale_image / scale_pbr) and r3dg_stage2_loss with sparse_feature_gradients != 0 and the two
+ * SSIM gradients as its extras -- same inputs, same outputs, same sums (d_sums[0..2], d_ssim_sum_image, d_ssim_sum_pbr), the
+ * same per-pixel arithmetic -- without their intermediates: the sRGB PBR image, the SSIM partials and the SSIM gradients are
+ * never stored.  d_pseudo_normal / d_surface_xyz [3,HW] are fully written; d_dL_dimage [3,HW], d_dL_dopacity [HW] and of
+ * d_dL_dfeature [16,HW] the maps 2-4 (5-7 too when w_normal != 0) are written, the other maps are left untouched; with
+ * w_normal == 0 the normal maps and d_image_mask are not read and d_sums[2] is not accumulated.  d_image_mask may be NULL.
+ * r3dg_stage2_image_tail_supported: 1 where the kernel applies (callers fall back to the four calls elsewhere). */
+int r3dg_stage2_image_tail_supported(int width, int height);
+int r3dg_stage2_image_tail(void* stream, int width, int height, const float* d_viewmatrix, float tan_fovx, float tan_fovy,
+                           float cx, float cy, const float* d_image, const float* d_opacity, const float* d_depth,
+                           const float* d_feature, const int32_t* d_n_contrib, const float* d_gt, const float* d_background,
+                           const float* d_image_mask, float w_l1, float w_pbr, float w_normal, float scale_image,
+                           float scale_pbr, float* d_pseudo_normal, float* d_surface_xyz, float* d_dL_dimage,
+                           float* d_dL_dopacity, float* d_dL_dfeature, float* d_sums, float* d_ssim_sum_image,
+                           float* d_ssim_sum_pbr);
 
 /* SSIM (utils/loss_utils.py:20-63: 11x11 Gaussian window, sigma 1.5, zero padding) of x against y, both [C,H,W].
  * _forward: *d_sum += sum of the SSIM map (divide by C*H*W for the reference's mean); d_partials [C,3,H,W] receives the

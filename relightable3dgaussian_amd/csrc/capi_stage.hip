@@ -289,6 +289,32 @@ int r3dg_stage2_normals_srgb(void* stream_, int width, int height, const float* 
     });
 }
 
+int r3dg_stage2_image_tail_supported(int width, int height) { return image_tail_applies(width, height) ? 1 : 0; }
+
+int r3dg_stage2_image_tail(void* stream_, int width, int height, const float* viewmatrix, float tan_fovx, float tan_fovy, float cx,
+                           float cy, const float* image, const float* opacity, const float* depth, const float* feature,
+                           const int32_t* n_contrib, const float* gt, const float* bg, const float* image_mask, float w_l1,
+                           float w_pbr, float w_normal, float scale_image, float scale_pbr, float* pseudo_normal,
+                           float* surface_xyz, float* dL_dimage, float* dL_dopacity, float* dL_dfeature, float* sums,
+                           float* ssim_sum_image, float* ssim_sum_pbr)
+{
+    if (width < 0 || height < 0) return invalid("stage2_image_tail: bad image size");
+    if ((long long)width * height == 0) return R3DG_OK;
+    if (!image_tail_applies(width, height)) return invalid("stage2_image_tail: image too large");
+    if (!viewmatrix || !image || !opacity || !depth || !feature || !n_contrib || !gt || !bg || !pseudo_normal || !surface_xyz ||
+        !dL_dimage || !dL_dopacity || !dL_dfeature || !sums || !ssim_sum_image || !ssim_sum_pbr)
+        return invalid("stage2_image_tail: null buffer");
+    return guarded([&]() -> int {
+        StageTimer t((hipStream_t)stream_, ST_S2_LOSS);
+        // focal lengths exactly as the rasterizer forward derives them (rasterizer_impl.cu:239-240)
+        const float focal_y = height / (2.0f * tan_fovy), focal_x = width / (2.0f * tan_fovx);
+        launch_s2_image_tail((hipStream_t)stream_, width, height, viewmatrix, focal_x, focal_y, cx, cy, image, opacity, depth,
+                             feature, n_contrib, gt, bg, image_mask, w_l1, w_pbr, w_normal, scale_image, scale_pbr, pseudo_normal,
+                             surface_xyz, dL_dimage, dL_dopacity, dL_dfeature, sums, ssim_sum_image, ssim_sum_pbr);
+        return R3DG_OK;
+    });
+}
+
 int r3dg_ssim_forward_pair(void* stream_, int width, int height, int channels, const float* x0, const float* x1,
                            const float* y, float* partials0, float* partials1, float* sum0, float* sum1)
 {

@@ -177,6 +177,12 @@ void launch_s2_pbr_srgb(hipStream_t s, int HW, const float* opacity, const float
 void launch_s2_normals_srgb(hipStream_t s, int W, int H, const float* vm, float focal_x, float focal_y, float cx, float cy,
                             const float* opacity, const float* depths, float* normals, float* surface_xyz,
                             const float* feature, const int* n_contrib, const float* bg, float* srgb);
+bool image_tail_applies(int W, int H);
+void launch_s2_image_tail(hipStream_t s, int W, int H, const float* vm, float focal_x, float focal_y, float cx, float cy,
+                          const float* image, const float* opacity, const float* depths, const float* feature, const int* n_contrib,
+                          const float* gt, const float* bg, const float* image_mask, float w_l1, float w_pbr, float w_normal,
+                          float scale_image, float scale_pbr, float* pseudo_normal, float* surface_xyz, float* dL_dimage,
+                          float* dL_dopacity, float* dL_dfeature, float* sums, float* ssim_sum_image, float* ssim_sum_pbr);
 void launch_ssim_forward(hipStream_t s, int W, int H, int C, int n_images, const float* const* x, const float* y,
                          float* const* partials, float* const* sum);
 void launch_ssim_backward(hipStream_t s, int W, int H, int C, int n_images, const float* const* x, const float* y,

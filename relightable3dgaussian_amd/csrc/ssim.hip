@@ -13,20 +13,16 @@
 //                         SSIM sum as two doubles -- no atomics; eval_metrics.hip adds them up in a fixed order.
 // HBM-bound streaming kernels: 5 map reads + 3 writes forward, 5 reads + 1 write backward per channel.
 #include "launchers.hpp"
+#include "ssim_window.hpp"
 
 namespace r3dg {
 
-constexpr int SSIM_R = 5;                    // window radius (window_size 11)
 constexpr int SSIM_T = 32;                   // tile edge (outputs)
 constexpr int SSIM_E = SSIM_T + 2 * SSIM_R;  // 42: tile + halo
 constexpr int SSIM_B = 4;                    // outputs per thread along the filtered axis (sliding window in registers)
 constexpr int SSIM_NLOAD = (SSIM_E * SSIM_E + 255) / 256;     // halo-region elements per thread (7)
 
-// gaussian(11, 1.5) / sum, the fp32 values the reference's create_window produces (loss_utils.py:20-29)
-__constant__ float kSsimWin[11] = {1.028380124e-03f, 7.598758209e-03f, 3.600077331e-02f, 1.093606874e-01f,
-                                   2.130055279e-01f, 2.660117149e-01f, 2.130055279e-01f, 1.093606874e-01f,
-                                   3.600077331e-02f, 7.598758209e-03f, 1.028380124e-03f};
-
+// (the taps, the separable passes and the per-pixel function: ssim_window.hpp, shared with image_tail.hip)
 // Both kernels: one 32x32 output tile per 256-thread workgroup.  Horizontal pass: a work item = (row of the 42-row
 // halo region, group of 4 adjacent columns): 14 LDS reads per map feed 4 outputs.  Vertical pass: a work item = (column,
 // group of 4 adjacent rows), exactly one per thread.
@@ -124,8 +120,7 @@ __device__ __forceinline__ void ssim_forward_tile(int W, int H, int C, const Ssi
         }
     }
     float w[11];
-#pragma unroll
-    for (int k = 0; k < 11; k++) w[k] = kSsimWin[k];
+    ssim_load_window(w);
     constexpr int ITEMS = SSIM_E * (SSIM_T / SSIM_B), ROUNDS = (ITEMS + 255) / 256;     // horizontal taps
     float hres[ROUNDS][5][SSIM_B];
 #pragma unroll
@@ -137,15 +132,8 @@ __device__ __forceinline__ void ssim_forward_tile(int W, int H, int C, const Ssi
 #pragma unroll
             for (int k = 0; k < SSIM_B + 10; k++) { xv[k] = s_x[r][q0 + k]; yv[k] = s_y[r][q0 + k]; }
 #pragma unroll
-            for (int o = 0; o < SSIM_B; o++) {
-                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
-#pragma unroll
-                for (int k = 0; k < 11; k++) {
-                    const float wx = w[k] * xv[o + k], wy = w[k] * yv[o + k];
-                    a0 += wx; a1 += wy; a2 += wx * xv[o + k]; a3 += wy * yv[o + k]; a4 += wx * yv[o + k];
-                }
-                hres[rd][0][o] = a0; hres[rd][1][o] = a1; hres[rd][2][o] = a2; hres[rd][3][o] = a3; hres[rd][4][o] = a4;
-            }
+            for (int o = 0; o < SSIM_B; o++)
+                ssim_taps_pair(w, xv + o, yv + o, hres[rd][0][o], hres[rd][1][o], hres[rd][2][o], hres[rd][3][o], hres[rd][4][o]);
         }
     }
     __syncthreads();                                   // every read of the staged inputs is done: reuse their storage
@@ -170,12 +158,7 @@ __device__ __forceinline__ void ssim_forward_tile(int W, int H, int C, const Ssi
 #pragma unroll
         for (int k = 0; k < SSIM_B + 10; k++) col[k] = s_h[m][ty0 + k][tx];
 #pragma unroll
-        for (int o = 0; o < SSIM_B; o++) {
-            float a = 0.f;
-#pragma unroll
-            for (int k = 0; k < 11; k++) a += w[k] * col[o + k];
-            acc[m][o] = a;
-        }
+        for (int o = 0; o < SSIM_B; o++) acc[m][o] = ssim_taps(w, col + o);
     }
     float ssim_sum = 0.f;
     float* pc = EVAL ? nullptr : partials + (size_t)c * 3 * HW;
@@ -183,21 +166,13 @@ __device__ __forceinline__ void ssim_forward_tile(int W, int H, int C, const Ssi
     for (int o = 0; o < SSIM_B; o++) {
         const int py = by + ty0 + o;
         if (px < W && py < H) {
-            const float mu1 = acc[0][o], mu2 = acc[1][o], e11 = acc[2][o], e22 = acc[3][o], e12 = acc[4][o];
-            const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-            const float A = 2.f * mu1 * mu2 + C1;
-            const float B = 2.f * (e12 - mu1 * mu2) + C2;
-            const float C = mu1 * mu1 + mu2 * mu2 + C1;
-            const float D = (e11 - mu1 * mu1) + (e22 - mu2 * mu2) + C2;
-            const float inv = 1.f / (C * D);
-            const float ssim = A * B * inv;
-            ssim_sum += ssim;
+            float p0, p1, p2;
+            ssim_sum += ssim_pixel<!EVAL>(acc[0][o], acc[1][o], acc[2][o], acc[3][o], acc[4][o], p0, p1, p2);
             if constexpr (!EVAL) {
-                // partial derivatives of ssim w.r.t. mu1, E[x^2], E[xy] (treated as independent window averages)
                 const size_t off = (size_t)py * W + px;
-                pc[off] = 2.f * mu2 * (B - A) * inv - ssim * 2.f * mu1 * (D - C) * inv;
-                pc[HW + off] = -ssim / D;
-                pc[2 * HW + off] = 2.f * A * inv;
+                pc[off] = p0;
+                pc[HW + off] = p1;
+                pc[2 * HW + off] = p2;
             }
         }
     }
@@ -289,8 +264,7 @@ ssim_backward_kernel(int W, int H, int C, SsimBatch batch)
     }
     __syncthreads();
     float w[11];
-#pragma unroll
-    for (int k = 0; k < 11; k++) w[k] = kSsimWin[k];
+    ssim_load_window(w);
     constexpr int ITEMS = SSIM_E * (SSIM_T / SSIM_B), ROUNDS = (ITEMS + 255) / 256;
     float hres[ROUNDS][3][SSIM_B];
 #pragma unroll
@@ -304,12 +278,7 @@ ssim_backward_kernel(int W, int H, int C, SsimBatch batch)
 #pragma unroll
                 for (int k = 0; k < SSIM_B + 10; k++) v[k] = s_p[m][r][q0 + k];
 #pragma unroll
-                for (int o = 0; o < SSIM_B; o++) {
-                    float a = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 11; k++) a += w[k] * v[o + k];
-                    hres[rd][m][o] = a;
-                }
+                for (int o = 0; o < SSIM_B; o++) hres[rd][m][o] = ssim_taps(w, v + o);
             }
         }
     }
@@ -333,19 +302,14 @@ ssim_backward_kernel(int W, int H, int C, SsimBatch batch)
 #pragma unroll
         for (int k = 0; k < SSIM_B + 10; k++) col[k] = s_h[m][ty0 + k][tx];
 #pragma unroll
-        for (int o = 0; o < SSIM_B; o++) {
-            float a = 0.f;
-#pragma unroll
-            for (int k = 0; k < 11; k++) a += w[k] * col[o + k];
-            acc[m][o] = a;
-        }
+        for (int o = 0; o < SSIM_B; o++) acc[m][o] = ssim_taps(w, col + o);
     }
 #pragma unroll
     for (int o = 0; o < SSIM_B; o++) {
         const int py = by + ty0 + o;
         if (px < W && py < H) {
             const size_t off = (size_t)py * W + px;
-            grad_x[c * HW + off] = scale * (acc[0][o] + 2.f * xo[o] * acc[1][o] + yo[o] * acc[2][o]);
+            grad_x[c * HW + off] = ssim_grad_pixel(scale, acc[0][o], acc[1][o], acc[2][o], xo[o], yo[o]);
         }
     }
 }

@@ -13,6 +13,7 @@
 // Parity target: the plain-PyTorch restatement in relightable3dgaussian_amd/train_step.py (Stage2Step), fp32 tolerance.
 #include "launchers.hpp"
 #include "glue_math.hpp"
+#include "stage2_loss_math.hpp"
 #include "pseudo_normal.hpp"
 #include "r3dg_hip.h"
 
@@ -315,13 +316,10 @@ s2_pbr_srgb_kernel(int HW, const float* __restrict__ opacity, const float* __res
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= HW) return;
     const float op = opacity[i];
-    const float scale = n_contrib[i] > 0 ? 1.f / fmaxf(op, 1e-5f) : 0.f;
+    const float scale = s2_divide_scale(op, n_contrib[i]);
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float x = feature[(size_t)(2 + c) * HW + i] * scale * op + (1.f - op) * bg[c];
-        const float v = x <= 0.0031308f ? 12.92f * x : 1.055f * srgb_pow(fmaxf(x, 0.0031308f), 1.f / 2.4f) - 0.055f;
-        srgb[(size_t)c * HW + i] = fminf(fmaxf(v, 0.f), 1.f);      // rgb_to_srgb clips (utils/graphics_utils.py:211-212)
-    }
+    for (int c = 0; c < 3; c++)
+        srgb[(size_t)c * HW + i] = s2_pbr_srgb_pixel(feature[(size_t)(2 + c) * HW + i], scale, op, bg[c]);
 }
 
 // pseudo_normal_kernel (the rasterizer forward's K9 + K10, pseudo_normal.hpp) and s2_pbr_srgb_kernel as ONE launch, pixel by pixel:
@@ -338,13 +336,10 @@ s2_normals_srgb_kernel(int W, int H, float focal_x, float focal_y, float cx, flo
     const int HW = W * H, i = y * W + x;
     {
         const float op = opacity[i];
-        const float scale = n_contrib[i] > 0 ? 1.f / fmaxf(op, 1e-5f) : 0.f;
+        const float scale = s2_divide_scale(op, n_contrib[i]);
 #pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const float v0 = feature[(size_t)(2 + c) * HW + i] * scale * op + (1.f - op) * bg[c];
-            const float v = v0 <= 0.0031308f ? 12.92f * v0 : 1.055f * srgb_pow(fmaxf(v0, 0.0031308f), 1.f / 2.4f) - 0.055f;
-            srgb[(size_t)c * HW + i] = fminf(fmaxf(v, 0.f), 1.f);
-        }
+        for (int c = 0; c < 3; c++)
+            srgb[(size_t)c * HW + i] = s2_pbr_srgb_pixel(feature[(size_t)(2 + c) * HW + i], scale, op, bg[c]);
     }
     pseudo_normal_pixel(x, y, W, H, focal_x, focal_y, cx, cy, vm, opacity, depths, normals, surface_xyz);
 }
@@ -393,46 +388,15 @@ s2_loss_kernel(int HW, const float* __restrict__ image, const float* __restrict_
                 v_pn[c] = pseudo_normal[(size_t)c * HW + i];
             }
         }
-        const bool mask = nc > 0;
-        const float opc = fmaxf(op, 1e-5f);
-        const float scale = mask ? 1.f / opc : 0.f;                 // feat = feature * scale
-        const float dscale_dop = (mask && op >= 1e-5f) ? -1.f / (opc * opc) : 0.f;
+        const S2Divide dv = s2_divide(op, nc);
         float g_op = 0.f;
 #pragma unroll
         for (int c = 0; c < 3; c++) {
-            const float g = v_gt[c];
-            // L1 on the SH image
-            const float d0 = v_im[c] - g;
-            s_l1 += fabsf(d0);
             // extra_*: gradients of further terms on the same two images (the SSIM terms, r3dg_ssim_backward)
-            dL_dimage[(size_t)c * HW + i] = w_l1 * signf_(d0) + v_ei[c];
-            // L1 on the sRGB-mapped PBR image: pbr_img = r_pbr * op + (1 - op) * bg
-            const float F = v_F[c];
-            const float r = F * scale;
-            const float x = r * op + (1.f - op) * bg[c];
-            const bool lin = x <= 0.0031308f;
-            const float xs = fmaxf(x, 0.0031308f);
-            // rgb_to_srgb with clip=True (utils/graphics_utils.py:207-213): the curve, then clamp to [0,1]; the clamp passes
-            // the gradient only where 0 <= curve <= 1 (torch.clamp), so saturated HDR highlights stop pulling
-            const float curve = lin ? 12.92f * x : 1.055f * srgb_pow(xs, 1.f / 2.4f) - 0.055f;
-            const bool unclipped = curve >= 0.f && curve <= 1.f;
-            const float srgb = fminf(fmaxf(curve, 0.f), 1.f);
-            const float d1 = srgb - g;
-            s_pbr += fabsf(d1);
-            const float dsrgb = !unclipped ? 0.f : (lin ? 12.92f : 1.055f / 2.4f * srgb_pow(xs, 1.f / 2.4f - 1.f));
-            const float gx = (w_pbr * signf_(d1) + v_es[c]) * dsrgb;   // dL/dx
-            dL_dfeature[(size_t)(2 + c) * HW + i] = gx * op * scale;
-            g_op += gx * (r - bg[c] + op * F * dscale_dop);
-            // normal consistency: mse(r_normal, pseudo_normal)
-            if (normal_on) {
-                // mse(normal * m, pseudo_normal * m), m = the view's object mask (neilf.py:258-264; NULL = all ones)
-                const float Fn = v_Fn[c];
-                const float dn = (Fn * scale - v_pn[c]) * mk;
-                s_n += dn * dn;
-                const float gn = 2.f * w_normal * dn * mk;
-                dL_dfeature[(size_t)(5 + c) * HW + i] = gn * scale;
-                g_op += gn * Fn * dscale_dop;
-            }
+            dL_dimage[(size_t)c * HW + i] = s2_loss_image(v_im[c], v_gt[c], w_l1, v_ei[c], s_l1);
+            dL_dfeature[(size_t)(2 + c) * HW + i] = s2_loss_pbr(v_F[c], v_gt[c], op, bg[c], dv, w_pbr, v_es[c], s_pbr, g_op);
+            if (normal_on)       // (image_mask NULL = all ones)
+                dL_dfeature[(size_t)(5 + c) * HW + i] = s2_loss_normal(v_Fn[c], v_pn[c], mk, dv, w_normal, s_n, g_op);
         }
         dL_dopacity[i] = g_op;
         if (!SPARSE) {

@@ -8,6 +8,8 @@ csrc/stage2_glue.hip, smooth.hip and adam.hip and without an autograd graph: for
     S=16 feature row + light-smoothness sum   written by the two launches above; r3dg_stage2_pack_features behind the general
                                               shading kernel                   (neilf.py:115-122, 286-292)
     rasterize                                 r3dg_rasterize_forward_*         (r3dg_rasterization.py:75-113)
+    the image tail, one launch                r3dg_stage2_image_tail (where the library has it; otherwise, and with
+                                              R3DG_IMAGE_TAIL=0, the three rows below)
     pseudo normals + sRGB-mapped PBR image    r3dg_stage2_normals_srgb
     SSIM of the image and the PBR image       r3dg_ssim_forward_pair / r3dg_ssim_backward_pair
     image-space loss terms + their gradients  r3dg_stage2_loss (+ r3dg_stage2_smooth_fused, + r3dg_stage2_supervision when the
@@ -439,32 +441,42 @@ class FusedStage2Step(FusedStepBase):
         return taps, packed
 
     def _image_loss(self, v, fw):
-        """Image-space loss terms and their gradients.  -> (the gradient slab `g`: dL_dimage 3 | dL_dopacity 1 | dL_dfeature 16 |
-        sRGB PBR image 3 | SSIM partials 2x9 | SSIM gradients 2x3 (the depth image carries no loss), the feature maps that
-        carry a gradient)."""
+        """Image-space loss terms and their gradients.  -> (the gradient slab `g`: dL_dimage 3 | dL_dopacity 1 | dL_dfeature 16
+        (the depth image carries no loss) -- and behind them, on the four-launch path only, its scratch: sRGB PBR image 3 | SSIM
+        partials 2x9 | SSIM gradients 2x3 --, the feature maps that carry a gradient)."""
         L = _lib.lib()
         cam, W, H, N = v.cam, v.W, v.H, v.N
         _R, n_contrib, image, opacity, depth, feature, pseudo_normal, sxyz = fw[:8]
-        g = torch.empty((47, H, W), dtype=torch.float32, device=self.dev)
         gt_c, bg_c = v.gt.contiguous(), v.bg.contiguous()
-        srgb, part_i, part_p, gs_i, gs_p = g[20:23], g[23:32], g[32:41], g[41:44], g[44:47]
-        lam = LAMBDA_DSSIM
-        # the rasterizer forward's pseudo-normal pass (deferred in _front_end) and the sRGB-mapped PBR image: one per-pixel launch
-        _lib.check(L.r3dg_stage2_normals_srgb(v.raw, W, H, v.vm.data_ptr(), float(cam.tanfovx), float(cam.tanfovy), float(cam.cx),
-            float(cam.cy), opacity.data_ptr(), depth.data_ptr(), pseudo_normal.data_ptr(), sxyz.data_ptr(), feature.data_ptr(),
-            n_contrib.data_ptr(), bg_c.data_ptr(), srgb.data_ptr()), "stage2_normals_srgb")
-        _lib.check(L.r3dg_ssim_forward_pair(v.raw, W, H, 3, image.data_ptr(), srgb.data_ptr(), gt_c.data_ptr(), part_i.data_ptr(),
-                                            part_p.data_ptr(), self.sums[5].data_ptr(), self.sums[6].data_ptr()), "ssim_forward")
-        _lib.check(L.r3dg_ssim_backward_pair(v.raw, W, H, 3, image.data_ptr(), srgb.data_ptr(), gt_c.data_ptr(),
-                                             part_i.data_ptr(), part_p.data_ptr(), -self.w["l1"] * lam / (3.0 * N),
-                                             -self.w["pbr"] * lam / (3.0 * N), gs_i.data_ptr(), gs_p.data_ptr()),
-                   "ssim_backward")
         mask_c = None if v.mask is None else v.mask.contiguous()
-        _lib.check(L.r3dg_stage2_loss(v.raw, W, H, image.data_ptr(), opacity.data_ptr(), feature.data_ptr(),
-            pseudo_normal.data_ptr(), n_contrib.data_ptr(), gt_c.data_ptr(), bg_c.data_ptr(), _lib.ptr(mask_c),
-            self.w["l1"] * (1.0 - lam) / (3.0 * N), self.w["pbr"] * (1.0 - lam) / (3.0 * N), self.w["normal"] / (3.0 * N),
-            gs_i.data_ptr(), gs_p.data_ptr(), g[0:3].data_ptr(), g[3:4].data_ptr(), g[4:20].data_ptr(), self.sums.data_ptr(), 1),
-            "stage2_loss")
+        lam = LAMBDA_DSSIM
+        w_l1, w_pbr, w_n = (self.w["l1"] * (1.0 - lam) / (3.0 * N), self.w["pbr"] * (1.0 - lam) / (3.0 * N),
+                            self.w["normal"] / (3.0 * N))
+        ssim_i, ssim_p = -self.w["l1"] * lam / (3.0 * N), -self.w["pbr"] * lam / (3.0 * N)
+        if self._fuses_image_tail(W, H):
+            # the four launches below as one (r3dg_stage2_image_tail): the sRGB image, the SSIM partials and the SSIM gradients
+            # stay on chip, so the slab ends behind the feature gradients
+            g = torch.empty((20, H, W), dtype=torch.float32, device=self.dev)
+            _lib.check(L.r3dg_stage2_image_tail(v.raw, W, H, v.vm.data_ptr(), float(cam.tanfovx), float(cam.tanfovy), float(cam.cx),
+                float(cam.cy), image.data_ptr(), opacity.data_ptr(), depth.data_ptr(), feature.data_ptr(), n_contrib.data_ptr(),
+                gt_c.data_ptr(), bg_c.data_ptr(), _lib.ptr(mask_c), w_l1, w_pbr, w_n, ssim_i, ssim_p, pseudo_normal.data_ptr(),
+                sxyz.data_ptr(), g[0:3].data_ptr(), g[3:4].data_ptr(), g[4:20].data_ptr(), self.sums.data_ptr(),
+                self.sums[5].data_ptr(), self.sums[6].data_ptr()), "stage2_image_tail")
+        else:
+            g = torch.empty((47, H, W), dtype=torch.float32, device=self.dev)
+            srgb, part_i, part_p, gs_i, gs_p = g[20:23], g[23:32], g[32:41], g[41:44], g[44:47]
+            # the rasterizer forward's pseudo-normal pass (deferred in _front_end) and the sRGB-mapped PBR image: one per-pixel launch
+            _lib.check(L.r3dg_stage2_normals_srgb(v.raw, W, H, v.vm.data_ptr(), float(cam.tanfovx), float(cam.tanfovy),
+                float(cam.cx), float(cam.cy), opacity.data_ptr(), depth.data_ptr(), pseudo_normal.data_ptr(), sxyz.data_ptr(),
+                feature.data_ptr(), n_contrib.data_ptr(), bg_c.data_ptr(), srgb.data_ptr()), "stage2_normals_srgb")
+            _lib.check(L.r3dg_ssim_forward_pair(v.raw, W, H, 3, image.data_ptr(), srgb.data_ptr(), gt_c.data_ptr(),
+                part_i.data_ptr(), part_p.data_ptr(), self.sums[5].data_ptr(), self.sums[6].data_ptr()), "ssim_forward")
+            _lib.check(L.r3dg_ssim_backward_pair(v.raw, W, H, 3, image.data_ptr(), srgb.data_ptr(), gt_c.data_ptr(),
+                part_i.data_ptr(), part_p.data_ptr(), ssim_i, ssim_p, gs_i.data_ptr(), gs_p.data_ptr()), "ssim_backward")
+            _lib.check(L.r3dg_stage2_loss(v.raw, W, H, image.data_ptr(), opacity.data_ptr(), feature.data_ptr(),
+                pseudo_normal.data_ptr(), n_contrib.data_ptr(), gt_c.data_ptr(), bg_c.data_ptr(), _lib.ptr(mask_c), w_l1, w_pbr, w_n,
+                gs_i.data_ptr(), gs_p.data_ptr(), g[0:3].data_ptr(), g[3:4].data_ptr(), g[4:20].data_ptr(), self.sums.data_ptr(), 1),
+                "stage2_loss")
         # r3dg_stage2_loss only writes the pbr maps and -- when that term is on -- the normal maps; the smoothness terms
         # add base colour / roughness / diffuse light (and, through the light term's guide, the normal maps)
         active = [2, 3, 4] + ([5, 6, 7] if self.w["normal"] != 0.0 else [])
@@ -490,6 +502,15 @@ class FusedStage2Step(FusedStepBase):
             active += ([0] if w_d != 0.0 else []) + ([5, 6, 7] if w_nm != 0.0 and 5 not in active else [])
         self.last_active_features = sorted(set(active))
         return g, active
+
+    @staticmethod
+    def _fuses_image_tail(W, H):
+        """The image tail runs as one launch (r3dg_stage2_image_tail)?  The forward in use says that the library has the kernel for
+        this image size (rasterize_gaussians_begin.image_tail_supported: a stand-in without the attribute, or a library that
+        answers 0, keeps the four launches), and R3DG_IMAGE_TAIL is not 0 (the A/B switch: 0 restores r3dg_stage2_normals_srgb,
+        r3dg_ssim_forward_pair, r3dg_ssim_backward_pair, r3dg_stage2_loss)."""
+        can = getattr(rasterizer_ops.rasterize_gaussians_begin, "image_tail_supported", None)
+        return can is not None and os.environ.get("R3DG_IMAGE_TAIL", "1") != "0" and bool(can(W, H))
 
     def _supervision_count(self, v, depth_c, mask_c):
         """The number of pixels the depth term averages over (r3dg_supervision_count), on the device.  It depends on the view's

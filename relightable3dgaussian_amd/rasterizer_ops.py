@@ -293,6 +293,16 @@ def _sh_adam_supported(M):
 rasterize_gaussians_backward.sh_adam_supported = _sh_adam_supported
 
 
+def _image_tail_supported(W, H):
+    """The pseudo-normal pass that rasterize_gaussians_begin(defer_pseudo_normal=True) leaves to its caller can run inside the fused
+    stage-2 image tail (r3dg_stage2_image_tail_supported: the library has the kernel for a W x H image)?"""
+    return _lib.lib().r3dg_stage2_image_tail_supported(int(W), int(H)) == 1
+
+
+# (asked of the FUNCTION that defers the pass, as sh_adam_supported above: a stand-in without the attribute keeps the four launches)
+rasterize_gaussians_begin.image_tail_supported = _image_tail_supported
+
+
 def rasterize_gaussians_backward_features(P, S, image_height, image_width, dL_dout_feature, geomBuffer, R, binningBuffer,
                                           imageBuffer, debug=False, active_features=None):
     """The backward for FROZEN geometry (not in the reference; r3dg_rasterize_backward_features): only dL_dfeatures [P,S]
