@@ -849,6 +849,32 @@ int r3dg_scene_pack_records(void* stream, int P, int columns, void** src_groups,
  *   NaN quantises to 0.  The driver copies d_bytes asynchronously into its ring of pinned host buffers. */
 int r3dg_relight_quantize(void* stream, int width, int height, int channels, const float* d_image, uint8_t* d_bytes);
 
+/* r3dg_training_sheet: the contact sheet train.py:276-317 (save_training_vis) writes while a run trains, d_bytes
+ *   [out_height,out_width,3] uint8, from the RAW outputs of one eval frame in one launch: d_render, d_gt, d_pseudo_normal [3,H,W],
+ *   d_opacity [H,W], d_n_contrib [H,W], the rasterizer's un-normalised feature image d_feature [S,H,W].  layout 0: S = 5, channels
+ *   normal3, depth, depth2 (render.py:91,111), 7 panels; layout 1: the S = 28 eval row of r3dg_relight_pack_features, 16 panels,
+ *   with d_background [3] and the ACTIVATED environment texture d_env [env_rows,2 env_rows,3] (both read by layout 1 only and may
+ *   be NULL for layout 0; every other pointer is required).  Per output byte, in this order: (1) the source of the nearest-
+ *   neighbour resample of the grid to out_height x out_width, torch's rule src = min((int)floorf(dst * scale), in - 1), scale =
+ *   (float)in / out; (2) the cell of torchvision's make_grid(nrow=4, padding=2, pad_value=0): panel k at y = (k / 4) * (H + 2)
+ *   + 2, x = (k % 4) * (W + 2) + 2 of a grid of rows * (H + 2) + 2 by 4 * (W + 2) + 2, padding and cell 7 of the stage-1 grid 0;
+ *   (3) that panel at that pixel, with x = feature / max(opacity, 1e-5) * (n_contrib > 0) as in r3dg_relight_capture:
+ *     0 render, 1 gt, 2 visualize_depth(depth) (utils/image_utils.py:6-21 with its defaults: t = clip((-log(depth + eps) -
+ *     c_far) / (c_near - c_far), 0, 1) in float32, NaN -> 0, bin min((int)(t * 256), 255) of matplotlib's `turbo` table),
+ *     3 min((depth2 - depth^2) / 0.001, 1), 4 opacity, 5 normal * 0.5 + 0.5, 6 pseudo_normal * 0.5 + 0.5, 7 srgb(base_color),
+ *     8 roughness, 9 visibility, 10 srgb(diffuse), 11 srgb(specular), 12 srgb(global_lights), 13 srgb(pbr * opacity + (1 -
+ *     opacity) * background), 14 / 15 the left / right half of srgb(F.interpolate(env, (H, 2W))), nearest by the same rule;
+ *   one-channel panels fill all three channels; srgb is rgb_to_srgb with its clip; (4) r3dg_relight_quantize's quantisation.
+ *   The caller picks the size (training_vis.sheet_size: the reference's `scale = grid_h / 800`); any size of at least 1 x 1 is
+ *   served.  d_bytes must be 4-byte aligned: a lane stores four consecutive bytes as one word (the last lane its own bytes
+ *   only), the floats are read with 4-byte accesses at any 4-byte alignment, nothing outside the arrays is touched.  Nothing
+ *   synchronises; no atomics.  layout outside {0, 1}, a NULL required pointer, and frames, sheets or grid sides of 2^31
+ *   pixels and more are rejected. */
+int r3dg_training_sheet(void* stream, int width, int height, int layout, const float* d_render, const float* d_gt,
+                        const float* d_opacity, const int32_t* d_n_contrib, const float* d_feature,
+                        const float* d_pseudo_normal, const float* d_background, const float* d_env, int env_rows,
+                        int out_width, int out_height, uint8_t* d_bytes);
+
 /* r3dg_view_unpack: one ground-truth view of the device view store, d_pixels [H,W,C] uint8 as the image file holds them (C = 4:
  *   RGBA, C = 3: RGB) -> d_image [3,H,W] float composited onto d_background (3 floats on the device) and d_mask [1,H,W] float (the
  *   alpha channel; ones for C = 3; NULL: not wanted), bit for bit what the reference's reader makes of the file

@@ -91,6 +91,27 @@ int r3dg_relight_quantize(void* stream_, int width, int height, int channels, co
     });
 }
 
+int r3dg_training_sheet(void* stream_, int width, int height, int layout, const float* render, const float* gt,
+                        const float* opacity, const int32_t* n_contrib, const float* feature, const float* pseudo_normal,
+                        const float* background, const float* env, int env_rows, int out_width, int out_height, uint8_t* bytes)
+{
+    if (layout != 0 && layout != 1) return invalid("training_sheet: layout is 0 (stage 1, S = 5) or 1 (stage 2, S = 28)");
+    if (width < 1 || height < 1 || out_width < 1 || out_height < 1) return invalid("training_sheet: bad shape");
+    if ((long long)width * height >= (1ll << 31) || (long long)out_width * out_height >= (1ll << 31) ||
+        4ll * ((long long)width + 2) + 2 >= (1ll << 31) || 4ll * ((long long)height + 2) + 2 >= (1ll << 31))
+        return invalid("training_sheet: image too large");
+    if (!render || !gt || !opacity || !n_contrib || !feature || !pseudo_normal || !bytes)
+        return invalid("training_sheet: null buffer");
+    if (layout == 1 && (!background || !env || env_rows < 1 || env_rows >= (1 << 14)))
+        return invalid("training_sheet: layout 1 needs the background and the environment texture [R,2R,3], 1 <= R < 16384");
+    if ((size_t)bytes & 3) return invalid("training_sheet: the sheet must be 4-byte aligned");
+    return guarded([&]() -> int {
+        launch_training_sheet((hipStream_t)stream_, width, height, layout, render, gt, opacity, n_contrib, feature, pseudo_normal,
+                              background, env, env_rows, out_width, out_height, bytes);
+        return R3DG_OK;
+    });
+}
+
 int r3dg_view_unpack(void* stream_, int width, int height, int channels, const uint8_t* pixels, const float* background,
                      float* image, float* mask)
 {

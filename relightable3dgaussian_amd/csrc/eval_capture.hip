@@ -10,7 +10,7 @@
 // Lane = pixel, every channel a coalesced row read of the [28,HW] image (channel layout: relight_pack_features_kernel); each
 // channel is read once and nothing is kept across channels but the pixel's divisor, so there is nothing to spill.
 // Parity target: evaluate.capture_reference (PyTorch).
-#include "glue_math.hpp"
+#include "capture_math.hpp"
 #include "launchers.hpp"
 
 namespace r3dg {
@@ -22,17 +22,7 @@ __device__ __forceinline__ float over_background(float x, float m, float bg)
     const float a = x * m, b = (1.f - m) * bg;
     return a + b;
 }
-// depth2 - depth^2 likewise: a difference of two nearly equal terms, where a fused multiply-add is a visibly different value
-__device__ __forceinline__ float variance_of(float d, float d2)
-{
-#pragma clang fp contract(off)
-    const float sq = d * d;
-    return d2 - sq;
-}
-
-// feature / max(opacity, 1e-5) * (num_contrib > 0) with the reference's own rounding (a true division: depth_var below is a
-// difference of two nearly equal terms, a reciprocal's extra half ulp would show there); den == 0 stands for num_contrib == 0
-__device__ __forceinline__ float normalised(float f, float den) { return den > 0.f ? __fdiv_rn(f, den) : 0.f; }
+// (variance_of, normalised, capture_divisor, pbr_over_background: capture_math.hpp, shared with training_sheet.hip)
 
 template <int N, bool SRGB>
 __device__ __forceinline__ void capture_group(const float* __restrict__ feature, int c0, size_t HW, size_t i, float den,
@@ -56,7 +46,7 @@ relight_capture_kernel(int HW_, const float* __restrict__ feature, const float* 
     const size_t HW = (size_t)HW_, i = (size_t)blockIdx.x * 256 + threadIdx.x;     // (HW may lie within 256 of 2^31)
     if (i >= HW) return;
     const float op = opacity[i];
-    const float den = n_contrib[i] > 0 ? fmaxf(op, 1e-5f) : 0.f;     // rendered_feature / opacity * mask (neilf.py:146-147)
+    const float den = capture_divisor(op, n_contrib[i]);             // rendered_feature / opacity * mask (neilf.py:146-147)
     const bool masked = mask != nullptr;
     const float m = masked ? mask[i] : 1.f;
     float bg[3] = {0.f, 0.f, 0.f};
@@ -69,7 +59,7 @@ relight_capture_kernel(int HW_, const float* __restrict__ feature, const float* 
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             const float pbr = normalised(feature[(size_t)(2 + c) * HW + i], den);
-            float v = srgb_of(pbr * op + (1.f - op) * bg[c]);
+            float v = pbr_over_background(pbr, op, bg[c]);
             if (masked) v = over_background(v, m, bg[c]);
             maps.pbr[(size_t)c * HW + i] = v;
         }

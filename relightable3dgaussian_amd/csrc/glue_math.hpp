@@ -1,5 +1,5 @@
-// Scalar helpers of the glue kernels (stage2_glue.hip, stage1_glue.hip, smooth.hip, relight.hip, eval_capture.hip): the sRGB
-// curve, sigmoid, sign,
+// Scalar helpers of the glue kernels (stage2_glue.hip, stage1_glue.hip, smooth.hip, relight.hip, eval_capture.hip,
+// scene_assembly.hip, training_sheet.hip): the sRGB curve, the 8-bit quantisation, sigmoid, sign,
 // F.normalize and its backward, the adjoint weight of the replicate-padded Sobel stencil.
 #pragma once
 #include "common.hpp"
@@ -63,6 +63,14 @@ __device__ __forceinline__ float srgb_of(float x)
     const float p = __builtin_amdgcn_exp2f((1.0f / 2.4f) * __builtin_amdgcn_logf(fmaxf(x, 0.0031308f)));
     const float y = x > 0.0031308f ? p * 1.055f - 0.055f : 12.92f * x;
     return fminf(fmaxf(y, 0.f), 1.f);
+}
+
+// a value for an 8-bit image file as torchvision's save_image quantises it: clamp(x * 255 + 0.5, 0, 255) truncated, the product
+// and the sum rounded separately; NaN -> 0 (r3dg_relight_quantize, r3dg_training_sheet)
+__device__ __forceinline__ uint8_t quantize_byte(float x)
+{
+    const float v = __fadd_rn(__fmul_rn(x, 255.f), 0.5f);
+    return (uint8_t)(int)fminf(fmaxf(v, 0.f), 255.f);
 }
 
 // sum_d [clamp(q + d, 0, n-1) == p] * k[d+1]: weight with which position q's replicate-padded 1-D stencil reads position p

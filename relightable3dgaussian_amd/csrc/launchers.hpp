@@ -246,6 +246,11 @@ void launch_scene_place_groups(hipStream_t s, int P, const SceneGroups& src, con
                                long long row_offset, const SceneGroups& dst);
 void launch_scene_pack_records(hipStream_t s, int P, int columns, const SceneGroups& src, float* records);
 void launch_relight_quantize(hipStream_t s, int W, int H, int C, const float* image, uint8_t* bytes);
+// training_sheet.hip: the 8-bit training contact sheet [out_h,out_w,3] from an eval frame's raw outputs (layout 0: S = 5, 7 panels;
+// 1: S = 28, 16 panels, with the activated environment texture env [env_rows,2 env_rows,3]); bytes 4-byte aligned
+void launch_training_sheet(hipStream_t s, int W, int H, int layout, const float* render, const float* gt, const float* opacity,
+                           const int* n_contrib, const float* feature, const float* pseudo_normal, const float* background,
+                           const float* env, int env_rows, int out_w, int out_h, uint8_t* bytes);
 // view_store.hip: 8-bit pixels [H,W,C] of a stored ground-truth view -> image [3,H,W] over the background + mask [1,H,W] (or NULL)
 void launch_view_unpack(hipStream_t s, int W, int H, int C, const uint8_t* pixels, const float* background, float* image,
                         float* mask);

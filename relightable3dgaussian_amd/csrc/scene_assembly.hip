@@ -15,6 +15,7 @@
 //   No atomics; the only per-thread arrays (15 coefficients in, 15 out) are indexed by unrolled constants: no scratch memory.
 //
 //   relight_quantize_kernel   [C,H,W] float -> [H,W,C] uint8 as torchvision's save_image rounds (thread = output byte).
+#include "glue_math.hpp"
 #include "launchers.hpp"
 
 namespace r3dg {
@@ -253,8 +254,7 @@ relight_quantize_kernel(size_t HW, int C, const float* __restrict__ image, uint8
     if (i >= HW * (size_t)C) return;
     const size_t pix = i / (size_t)C;
     const int c = (int)(i - pix * (size_t)C);
-    const float v = __fadd_rn(__fmul_rn(image[(size_t)c * HW + pix], 255.f), 0.5f);
-    bytes[i] = (uint8_t)(int)fminf(fmaxf(v, 0.f), 255.f);
+    bytes[i] = quantize_byte(image[(size_t)c * HW + pix]);
 }
 
 template <bool FROM_RECORDS, bool TO_RECORDS>

@@ -139,7 +139,8 @@ class FrameWriter:
     """PNG output beside the renderer: `submit(image [C,H,W], path)` quantises on the device into one slot of a small ring,
     starts the asynchronous copy into the slot's pinned host buffer and hands the encoding (PIL) to a pool of at most 8 worker
     threads.  submit blocks only when every slot is still being encoded; `close` waits for the files and raises what a worker
-    raised."""
+    raised.  `submit_bytes(bytes [H,W,C] uint8, path)` takes a picture that is 8-bit already (training_vis) through the same ring,
+    copy, event and workers without the quantise launch."""
 
     def __init__(self, workers=None, slots=None):
         self.workers = max(1, min(8, workers or (os.cpu_count() or 1)))
@@ -157,6 +158,22 @@ class FrameWriter:
             slot.host = torch.empty(H, W, C, dtype=torch.uint8, pin_memory=True)
         quantize(image, slot.dev)
         slot.host.copy_(slot.dev, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self.jobs.append(self.pool.submit(self._encode, slot, done, path))
+
+    def submit_bytes(self, bytes_dev, path):
+        """The same for a picture that is 8-bit already ([H,W,C] uint8 on the device, contiguous: r3dg_training_sheet's output): no
+        quantise launch, the asynchronous copy goes from the caller's tensor straight into the slot's pinned host buffer.  The copy
+        is queued on the current stream, so the caller may overwrite `bytes_dev` with later work of that stream."""
+        if not isinstance(bytes_dev, torch.Tensor) or not bytes_dev.is_cuda or bytes_dev.dtype != torch.uint8 or \
+                bytes_dev.dim() != 3 or not 1 <= bytes_dev.shape[2] <= 4 or not bytes_dev.is_contiguous():
+            raise RuntimeError("submit_bytes: the picture must be a contiguous uint8 [H,W,C] with 1 <= C <= 4 on the device")
+        slot = self.free.get()
+        if slot.host is None or tuple(slot.host.shape) != tuple(bytes_dev.shape):
+            slot.dev = None                  # (a slot that changes size drops the device half `submit` would have to match)
+            slot.host = torch.empty(tuple(bytes_dev.shape), dtype=torch.uint8, pin_memory=True)
+        slot.host.copy_(bytes_dev, non_blocking=True)
         done = torch.cuda.Event()
         done.record()
         self.jobs.append(self.pool.submit(self._encode, slot, done, path))

@@ -26,11 +26,19 @@ of DirectLightMap.capture() inside train.py:197), and with --eval OUT/metrics.js
 (evaluate.evaluate_nvs) and, after stage 2, of `pbr` from a relight.RelightRenderer on the learned texture softplus(env).
 One progress line every --log_interval iterations (step.loss(): the only host read of the loop besides the overflow poll).
 
+`--save_training_vis` [`--save_training_vis_iteration N`, default 1000] (every script the reference ships passes it): the contact
+sheet of train.py:276-317, OUT/visualize/%06d.png, of the iteration's own view whenever the iteration count is a multiple of N
+and at the run's first iteration -- one eval frame of the live step and one r3dg_training_sheet launch (training_vis), encoded
+off the training thread; the writer is closed, and its errors raised, before --eval and before train() returns.  Without the flag
+nothing of it exists: no directory, no launch, no import.  ONE DIFFERENCE: the fused step has applied Adam when the loop's hook
+runs, so sheet g shows the state AFTER iteration g; the reference's shows the state before its optimizer step.
+
 Arguments carry the names and defaults of the reference's arguments/__init__.py.  The lambdas the fused steps implement become
 their loss weights; every other non-zero lambda RAISES before anything is loaded (`loss_weights_of`).
 
 Out of scope: the COLMAP / Stanford-ORB readers; OpenEXR files other than NONE / ZIPS / ZIP scanline files (PIZ above all); `resolution_scale` other than 1 and upscaling; MVS depth /
-normal maps (hence no lambda_depth / lambda_normal_mvs_depth); cfg_args, cameras.json, TensorBoard, LPIPS; data parallelism in this
+normal maps (hence no lambda_depth / lambda_normal_mvs_depth); cfg_args, cameras.json, TensorBoard (training_report's grids too),
+LPIPS; --video and the eval/ image folders of eval_render; data parallelism in this
 driver (train_loop's loops take a process group; this command does not start one).  THE ONE KNOWN DIFFERENCE FROM THE REFERENCE
 SCHEDULE: train.py:107-108 raises the active SH degree by one every 1000 iterations, the fused steps train degree 3 from the
 first iteration.
@@ -104,6 +112,9 @@ def build_parser():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--log_interval", type=int, default=100, help="0: no progress lines")
     p.add_argument("--visibility_interval", type=int, default=0, help="re-trace the visibility every N stage-2 iterations")
+    p.add_argument("--save_training_vis", action="store_true",
+                   help="write the contact sheet OUT/visualize/<iteration>.png of the iteration's view (training_vis)")
+    p.add_argument("--save_training_vis_iteration", type=int, default=1000, help="... every N iterations, and at the first")
     p.add_argument("--device", default="cuda")
     for name, value in sorted(vars(train_loop.Schedule()).items()):              # learning rates, light_init, densification
         if name not in _NOT_SCHEDULE and not name.startswith("lambda_"):
@@ -248,9 +259,33 @@ def train(args):
     result = types.SimpleNamespace(views=seen, files=files, metrics=None, env_init=None, store=store, extent=extent, cameras=cameras,
                                    test_cameras=test[2] if test else None)
     first = 0
+    vis = types.SimpleNamespace(sheet=None)                           # the training_vis.TrainingSheet, made at the first sheet
+    if args.save_training_vis:
+        if args.save_training_vis_iteration < 1:
+            raise RuntimeError("--save_training_vis_iteration %d: an interval of at least 1" % args.save_training_vis_iteration)
+        os.makedirs(os.path.join(args.model_path, "visualize"), exist_ok=True)
+
+    def save_sheet(it, g, step):
+        # train.py:279: every N iterations and at the run's first; the view of THIS iteration, its pair out of the store's ring
+        # while the ring still holds it (no second unpack launch)
+        if not (g % args.save_training_vis_iteration == 0 or it == 1):
+            return
+        if vis.sheet is None:
+            from . import training_vis
+            vis.sheet = training_vis.TrainingSheet(step, args.sample_num if stage2 else None)
+        v = seen[-1]
+        path = os.path.join(args.model_path, "visualize", "%06d.png" % g)
+        vis.sheet.save(cameras[v], store._pair(v, background, fresh=False)[0], background, path)
+        files.append(path)
+
+    def close_sheets():
+        if vis.sheet is not None:
+            vis.sheet.close()                                         # (waits for the files; raises what an encoder raised)
 
     def on_iteration(it, step):
         g = first + it
+        if args.save_training_vis:
+            save_sheet(it, g, step)
         if args.log_interval and it % args.log_interval == 0:
             if getattr(step, "last_outs", None) is None:
                 # (a densification replaced the step's buffers, the loss sums among them, after this iteration's backward)
@@ -302,6 +337,7 @@ def train(args):
                                                 visibility_interval=args.visibility_interval, masks=masks, loss_weights=weights,
                                                 on_iteration=on_iteration, view_order=view_order, first_iteration=first)
     result.step, result.history, result.first_iteration = step, history, first
+    close_sheets()                                                    # (before --eval, and before train() returns)
     if args.eval:
         _, test_store, test_cameras = test
         metrics = evaluate_step(step, args, test_cameras, test_store, background)
