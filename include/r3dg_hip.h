@@ -748,6 +748,66 @@ int r3dg_rasterize_backward_split_sh_adam(void* stream, void* geometry_stream, i
                                           const r3dg_adam_group* sh_adam, float beta1, float beta2, float eps, int step,
                                           float grad_scale, const float* d_skip_flag);
 
+/* ---- the tile backward's gradient records, read in place ------------------------------------------------------------------
+ * r3dg_rasterize_backward_split runs three launches: the tile kernel adds into one record per Gaussian, a scatter pass copies the
+ * records into five arrays (and zeroes them), the per-Gaussian geometry kernel reads three of the arrays.  In a whole stage-2
+ * iteration the other readers of the arrays -- r3dg_stage2_unpack_gradients and r3dg_stage2_activate_backward_with -- run one
+ * thread per Gaussian too, so each of the three can read its Gaussian's record row itself and the scatter pass (at 300k
+ * Gaussians 71 MB through device memory, alone on the critical path) is not needed.
+ *
+ * A LAYOUT is R3DG_GRAD_RECORD_LAYOUT_INTS host ints that say which channel of a record holds what: the record width in floats |
+ * colour r g b | S_x, S_y, depth side channel | S_xx, S_xy, S_yy, opacity | the channel of each of the 36 possible feature columns.
+ * A channel of -1 means "not carried": the value is +0.f (the depth side channel of an instance without a depth gradient, a
+ * feature column outside active_features).
+ *
+ * r3dg_rasterize_backward_split_records: r3dg_rasterize_backward_split_sh_adam without the scatter pass and without the four
+ *   arrays only that pass writes.  *supported_out = 1: the tile kernel has filled the records of `stream`, the geometry kernel
+ *   has read them in place on geometry_stream (sh_adam may be NULL: then it writes d_dL_dsh as r3dg_rasterize_backward_split
+ *   does), *d_records_out is the first of P rows and layout_out describes them.  d_dL_dmean2D [P,3], an output of the op, is
+ *   written in full by the geometry kernel (valid after joining geometry_stream); every other output is bit for bit what
+ *   r3dg_rasterize_backward_split writes.  The caller then OWES the rows their zeroing: r3dg_stage2_activate_backward_with_records
+ *   on `stream` (behind the join with geometry_stream) or r3dg_gradient_records_scatter.  A backward on the same stream that
+ *   finds the debt unpaid clears the whole buffer first, so an abandoned fill costs time, not correctness.
+ *   *supported_out = 0: nothing was enqueued -- the instance this call selects has no 16-float records (more than 7 active
+ *   feature channels, or a depth gradient with more than 6); call r3dg_rasterize_backward_split.
+ * r3dg_gradient_records_scatter: the scatter pass alone -- P rows of `layout` -> the five arrays of r3dg_rasterize_backward_split
+ *   (every element written, as there), zeros -> the rows.  d_records may be a copy of the rows in the caller's memory.
+ * r3dg_stage2_unpack_gradients_records, r3dg_stage2_activate_backward_with_records: those two calls with the rows (16-float
+ *   records over S = 16 feature columns) in place of d_dL_dfeatures, and of d_dL_dopacity; same arithmetic, same results.  The
+ *   second is the LAST reader: each thread writes its row back as zeros behind its loads.  Frozen geometry (d_g_xyz == NULL) has
+ *   no records: R3DG_EINVAL. */
+#define R3DG_GRAD_RECORD_LAYOUT_INTS 47
+int r3dg_rasterize_backward_split_records(void* stream, void* geometry_stream, int P, int S, int D, int M, int R,
+                                          const float* d_background, int width, int height, const float* d_means3D,
+                                          const float* d_shs, const float* d_features, const float* d_colors_precomp,
+                                          const float* d_scales, float scale_modifier, const float* d_rotations,
+                                          const float* d_cov3D_precomp, const float* d_viewmatrix,
+                                          const float* d_projmatrix, const float* d_campos, float tan_fovx, float tan_fovy,
+                                          const int32_t* d_radii, const void* d_geom_buffer, const void* d_binning_buffer,
+                                          const void* d_img_buffer, const float* d_dL_dpix, const float* d_dL_dpix_o,
+                                          const float* d_dL_dpix_d, const float* d_dL_dpix_f, float* d_dL_dmean2D,
+                                          float* d_dL_dmean3D, float* d_dL_dcov3D, float* d_dL_dsh, float* d_dL_dscale,
+                                          float* d_dL_drot, int backward_geometry, int debug, int n_active_features,
+                                          const int* active_features, const r3dg_adam_group* sh_adam, float beta1, float beta2,
+                                          float eps, int step, float grad_scale, const float* d_skip_flag,
+                                          void** d_records_out, int* layout_out, int* supported_out);
+int r3dg_gradient_records_scatter(void* stream, int P, int S, float* d_records, const int* layout, float* d_dL_dmean2D,
+                                  float* d_dL_dconic, float* d_dL_dopacity, float* d_dL_dcolor, float* d_dL_dfeature);
+int r3dg_stage2_unpack_gradients_records(void* stream, int P, const float* d_records, const int* layout,
+                                         const float* d_shade_out, float light_weight, float* d_dL_dpbr,
+                                         float* d_dL_ddiffuse_light, float* d_block_absmax, float* d_light_l1_sum);
+int r3dg_stage2_activate_backward_with_records(void* stream, int P, const float* d_xyz, const float* d_scaling_raw,
+                                               const float* d_rotation_raw, const float* d_opacity_raw,
+                                               const float* d_normal_raw, const float* d_base_raw, const float* d_rough_raw,
+                                               const float* d_viewmatrix, const float* d_campos, float* d_records,
+                                               const int* layout, const float* d_dL_dbase_color,
+                                               const float* d_dL_droughness, const float* d_dL_dviewdirs,
+                                               const float* d_dL_dscales, const float* d_dL_drot, const float* d_dL_dmeans3D,
+                                               float* d_g_xyz, float* d_g_scaling, float* d_g_rotation, float* d_g_opacity,
+                                               float* d_g_normal, float* d_g_base, float* d_g_rough, int He, int We,
+                                               const float* d_env_raw, const float* d_env, float* d_dL_denv, float w_tv,
+                                               float* d_g_env_raw, float* d_tv_sum, int consume);
+
 /* ---- relight / eval frame glue (relighting.py:114-170 -> gaussian_renderer/neilf.py:74-209 with is_training=False) -----
  * r3dg_relight_pack_features: the S=28 eval feature row (neilf.py:124-130) from the activated parameters and the 19
  *   outputs of r3dg_shade_forward: depth, depth^2, pbr3, normal3, base_color3, roughness, diffuse3, specular3, incident /

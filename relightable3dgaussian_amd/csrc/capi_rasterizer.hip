@@ -4,6 +4,7 @@
 #include "adam_update.hpp"
 #include "capi_internal.hpp"
 
+#include <cstring>
 #include <mutex>
 #include <vector>
 
@@ -535,8 +536,10 @@ static int check_active_features(const char* name, int n, const int* list, int S
     return R3DG_OK;
 }
 
-// the backward behind r3dg_rasterize_backward_split and _split_sh_adam (`adam` != nullptr: the geometry kernel applies the SH
-// colour group's Adam and does not write dL_dsh)
+// the backward behind r3dg_rasterize_backward_split, _split_sh_adam (`adam` != nullptr: the geometry kernel applies the SH
+// colour group's Adam and does not write dL_dsh) and _split_records (`records_out` != nullptr: no scatter pass -- the geometry
+// kernel reads the gradient record rows in place, the rows and their layout are handed to the caller, whose kernels read the rest;
+// *supported_out = 0 and nothing enqueued where the instance has no 16-float rows)
 static int backward_split_impl(void* stream_, void* geometry_stream_, int P, int S, int D, int M, int R,
                                   const float* background, int width, int height, const float* means3D,
                                   const float* shs, const float* features, const float* colors_precomp,
@@ -549,14 +552,25 @@ static int backward_split_impl(void* stream_, void* geometry_stream_, int P, int
                                   float* dL_dcolor, float* dL_dfeature, float* dL_dmean3D, float* dL_dcov3D,
                                   float* dL_dsh, float* dL_dscale, float* dL_drot, int backward_geometry, int debug_,
                                   int n_active_features, const int* active_features,
-                                  const ShAdamArgs* adam)
+                                  const ShAdamArgs* adam, void** records_out = nullptr, int* layout_out = nullptr,
+                                  int* supported_out = nullptr)
 {
+    if (records_out) *records_out = nullptr;
+    if (supported_out) *supported_out = 0;
     if (P < 0 || width <= 0 || height <= 0 || R < 0) return invalid("rasterize_backward: bad P/R/width/height");
     if (S < 0 || S > R3DG_MAX_S_BWD) return invalid("rasterize_backward: feature channels S must be in [0,36]");
     if (P == 0) return R3DG_OK;
     if (!geom_buffer || !img_buffer || (R > 0 && !binning_buffer)) return invalid("rasterize_backward: null state buffer");
     if (!dL_dpix || !dL_dpix_o || (S > 0 && !dL_dpix_f)) return invalid("rasterize_backward: null upstream gradient");
     if (int e = check_active_features("rasterize_backward", n_active_features, active_features, S)) return e;
+    const bool in_place = records_out != nullptr;
+    if (in_place) {
+        if (!layout_out || !supported_out) return invalid("rasterize_backward_split_records: null output");
+        const GradRecordLayout L = render_backward_layout(S, n_active_features, active_features, dL_dpix_d != nullptr,
+                                                          backward_geometry);
+        if (L.nvp != 16) return R3DG_OK;                 // (not an error: the caller takes r3dg_rasterize_backward_split)
+        *supported_out = 1;
+    }
 
     return guarded([&]() -> int {
         hipStream_t stream = (hipStream_t)stream_;
@@ -572,7 +586,21 @@ static int backward_split_impl(void* stream_, void* geometry_stream_, int P, int
         const char* bbuf = (const char*)binning_buffer;
         const int* radii_p = radii ? radii : (const int*)(gbuf + G.radii);
 
-        if (R > 0) {
+        float* rec = nullptr;
+        GradRecordLayout layout;
+        if (in_place) {
+            StageTimer t_rb(stream, ST_RENDER_BWD);
+            rec = launch_render_backward_fill(stream, P, width, height, S, n_active_features, active_features,
+                                              opt(R3DG_OPT_TILE_ORDER) ? (const uint32_t*)(ibuf + I.tile_order) : nullptr,
+                                              (const uint32_t*)(ibuf + I.ranges), (const uint32_t*)(bbuf + B.vals), background,
+                                              (const float*)(gbuf + G.splat), features, (const float*)(ibuf + I.final_T),
+                                              (const uint32_t*)(ibuf + I.n_contrib), dL_dpix, dL_dpix_o, dL_dpix_d, dL_dpix_f,
+                                              backward_geometry, R > 0, &layout);
+            check_launch(stream, debug, "render_backward");
+            t_rb.stop();
+            *records_out = rec;
+            std::memcpy(layout_out, &layout, sizeof(layout));
+        } else if (R > 0) {
             StageTimer t_rb(stream, ST_RENDER_BWD);
             launch_render_backward(stream, P, width, height, S, n_active_features, active_features,
                                    opt(R3DG_OPT_TILE_ORDER) ? (const uint32_t*)(ibuf + I.tile_order) : nullptr,
@@ -601,7 +629,8 @@ static int backward_split_impl(void* stream_, void* geometry_stream_, int P, int
                                    (const uint8_t*)(gbuf + G.clamped), cov3D_precomp == nullptr ? scales : nullptr,
                                    rotations, scale_modifier, cov3D_ptr, viewmatrix, projmatrix, focal_x, focal_y,
                                    tan_fovx, tan_fovy, campos, dL_dmean2D, dL_dconic, (const float*)(gbuf + G.conic_opacity),
-                                   width, height, dL_dmean3D, dL_dcolor, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, adam);
+                                   width, height, dL_dmean3D, dL_dcolor, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, adam, rec,
+                                   in_place ? &layout : nullptr);
         check_launch(stream, debug, "preprocess_backward");
         t_pb.stop();
         return R3DG_OK;
@@ -664,6 +693,66 @@ int r3dg_rasterize_backward_split_sh_adam(void* stream_, void* geometry_stream_,
     return backward_split_impl(R3DG_BACKWARD_SPLIT_ARGS, &adam);
 }
 #undef R3DG_BACKWARD_SPLIT_ARGS
+
+int r3dg_rasterize_backward_split_records(void* stream_, void* geometry_stream_, int P, int S, int D, int M, int R,
+                                  const float* background, int width, int height, const float* means3D,
+                                  const float* shs, const float* features, const float* colors_precomp,
+                                  const float* scales, float scale_modifier, const float* rotations,
+                                  const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                  const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
+                                  const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
+                                  const float* dL_dpix, const float* dL_dpix_o, const float* dL_dpix_d,
+                                  const float* dL_dpix_f, float* dL_dmean2D, float* dL_dmean3D, float* dL_dcov3D,
+                                  float* dL_dsh, float* dL_dscale, float* dL_drot, int backward_geometry, int debug_,
+                                  int n_active_features, const int* active_features,
+                                  const r3dg_adam_group* sh_adam, float beta1, float beta2, float eps, int step,
+                                  float grad_scale, const float* skip_flag, void** records_out, int* layout_out,
+                                  int* supported_out)
+{
+    const char* me = "rasterize_backward_split_records: ";
+    if (!records_out || !layout_out || !supported_out) return invalid(std::string(me) + "null output");
+    *records_out = nullptr;
+    *supported_out = 0;
+    if (P > 0 && !dL_dmean2D) return invalid(std::string(me) + "null dL_dmean2D");
+    ShAdamArgs adam = {};
+    if (sh_adam) {
+        if (P < 0 || M < 0) return invalid(std::string(me) + "bad P/M");
+        if (step < 1) return invalid(std::string(me) + "step counts from 1");
+        if (!preprocess_backward_applies_adam(M)) return invalid(std::string(me) + "no such kernel for this M / with STAGE_SH_ROWS off");
+        if (!shs || colors_precomp) return invalid(std::string(me) + "needs SH input");
+        const r3dg_adam_group& g = *sh_adam;
+        if (g.param != shs || g.n != (uint64_t)P * 3 * (uint64_t)M || g.n >= (1ull << 32))
+            return invalid(std::string(me) + "the group must be the [P,M,3] SH tensor itself (below 2^32 elements)");
+        if (P > 0 && (!g.exp_avg || !g.exp_avg_sq || (((uintptr_t)g.param | (uintptr_t)g.exp_avg | (uintptr_t)g.exp_avg_sq) & 15)))
+            return invalid(std::string(me) + "null or unaligned buffer in group");
+        const AdamBias b = adam_bias(beta1, beta2, step);
+        adam = ShAdamArgs{g, beta1, beta2, eps, b.bias1, b.inv_sqrt_bias2, grad_scale, skip_flag};
+    }
+    return backward_split_impl(stream_, geometry_stream_, P, S, D, M, R, background, width, height, means3D, shs, features,
+                               colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                               tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dpix_o, dL_dpix_d,
+                               dL_dpix_f, dL_dmean2D, nullptr, nullptr, nullptr, nullptr, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
+                               dL_drot, backward_geometry, debug_, n_active_features, active_features,
+                               sh_adam ? &adam : nullptr, records_out, layout_out, supported_out);
+}
+
+int r3dg_gradient_records_scatter(void* stream_, int P, int S, float* records, const int* layout_, float* dL_dmean2D,
+                                  float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dfeature)
+{
+    if (P < 0 || S < 0 || S > R3DG_MAX_S_BWD) return invalid("gradient_records_scatter: bad P/S");
+    if (P == 0) return R3DG_OK;
+    if (!records || !layout_ || !dL_dmean2D || !dL_dconic || !dL_dopacity || !dL_dcolor || (S > 0 && !dL_dfeature))
+        return invalid("gradient_records_scatter: null buffer");
+    GradRecordLayout L;
+    std::memcpy(&L, layout_, sizeof(L));
+    if (!gradient_record_layout_valid(L, S)) return invalid("gradient_records_scatter: not a gradient record layout");
+    return guarded([&]() -> int {
+        launch_gradient_records_scatter((hipStream_t)stream_, P, S, records, L, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
+                                        dL_dfeature);
+        check_launch((hipStream_t)stream_, false, "gradient_records_scatter");
+        return R3DG_OK;
+    });
+}
 
 int r3dg_rasterize_backward_features(void* stream_, int P, int S, int R, int width, int height, const void* geom_buffer,
                                      const void* binning_buffer, const void* img_buffer, const float* dL_dpix_f,

@@ -1,6 +1,7 @@
 // C ABI of the training-iteration glue (include/r3dg_hip.h): stage-1 / stage-2 activations, feature packing and losses,
 // SSIM, Adam, relighting, evaluation, densification.  Thin wrappers: argument checks, stage timing, one launcher each.
 #include "capi_internal.hpp"
+#include <cstring>
 
 using namespace r3dg;
 
@@ -66,19 +67,50 @@ int r3dg_stage2_pack_features(void* stream_, int P, const float* xyz, const floa
     });
 }
 
+// the host copy of a gradient record layout (R3DG_GRAD_RECORD_LAYOUT_INTS ints) for the kernels that read 16-float rows in place
+static int record_layout_16(const char* name, const int* layout, GradRecordLayout* out)
+{
+    if (!layout) return invalid(std::string(name) + ": null record layout");
+    std::memcpy(out, layout, sizeof(GradRecordLayout));
+    if (!gradient_record_layout_valid(*out, 16) || out->nvp != 16)
+        return invalid(std::string(name) + ": not a layout of 16-float gradient records over 16 feature columns");
+    return R3DG_OK;
+}
+
+static int unpack_impl(void* stream_, int P, const float* dL_dfeatures, const float* records, const int* layout,
+                       const float* shade_out, float light_weight, float* dL_dpbr, float* dL_ddiffuse, float* block_absmax,
+                       float* light_l1_sum)
+{
+    if (P < 0) return invalid("stage2_unpack_gradients: bad P");
+    if (P == 0) return R3DG_OK;
+    if (!(dL_dfeatures || records) || !shade_out || !dL_dpbr || !dL_ddiffuse) return invalid("stage2_unpack_gradients: null buffer");
+    GradRecordLayout L;
+    if (records != nullptr)
+        if (int e = record_layout_16("stage2_unpack_gradients_records", layout, &L)) return e;
+    return guarded([&]() -> int {
+        StageTimer t((hipStream_t)stream_, ST_S2_UNPACK);
+        launch_s2_unpack((hipStream_t)stream_, P, dL_dfeatures, shade_out, light_weight, dL_dpbr, dL_ddiffuse, block_absmax,
+                         light_l1_sum, records, records != nullptr ? &L : nullptr);
+        return R3DG_OK;
+    });
+}
+
 int r3dg_stage2_unpack_gradients(void* stream_, int P, const float* dL_dfeatures, const float* shade_out,
                                  float light_weight, float* dL_dpbr, float* dL_ddiffuse, float* block_absmax,
                                  float* light_l1_sum)
 {
-    if (P < 0) return invalid("stage2_unpack_gradients: bad P");
-    if (P == 0) return R3DG_OK;
-    if (!dL_dfeatures || !shade_out || !dL_dpbr || !dL_ddiffuse) return invalid("stage2_unpack_gradients: null buffer");
-    return guarded([&]() -> int {
-        StageTimer t((hipStream_t)stream_, ST_S2_UNPACK);
-        launch_s2_unpack((hipStream_t)stream_, P, dL_dfeatures, shade_out, light_weight, dL_dpbr, dL_ddiffuse, block_absmax,
-                         light_l1_sum);
-        return R3DG_OK;
-    });
+    if (P > 0 && !dL_dfeatures) return invalid("stage2_unpack_gradients: null buffer");
+    return unpack_impl(stream_, P, dL_dfeatures, nullptr, nullptr, shade_out, light_weight, dL_dpbr, dL_ddiffuse, block_absmax,
+                       light_l1_sum);
+}
+
+int r3dg_stage2_unpack_gradients_records(void* stream_, int P, const float* records, const int* layout, const float* shade_out,
+                                         float light_weight, float* dL_dpbr, float* dL_ddiffuse, float* block_absmax,
+                                         float* light_l1_sum)
+{
+    if (P > 0 && !records) return invalid("stage2_unpack_gradients_records: null buffer");
+    return unpack_impl(stream_, P, nullptr, records, layout, shade_out, light_weight, dL_dpbr, dL_ddiffuse, block_absmax,
+                       light_l1_sum);
 }
 
 int r3dg_stage2_activate_backward(void* stream_, int P, const float* xyz, const float* scaling_raw,
@@ -97,6 +129,46 @@ int r3dg_stage2_activate_backward(void* stream_, int P, const float* xyz, const 
                                               0.f, nullptr, nullptr, 0);
 }
 
+static int activate_backward_impl(void* stream_, int P, const float* xyz, const float* scaling_raw,
+                                  const float* rotation_raw, const float* opacity_raw, const float* normal_raw,
+                                  const float* base_raw, const float* rough_raw, const float* viewmatrix,
+                                  const float* campos, const float* dL_dfeatures, const float* dL_dbase_shade,
+                                  const float* dL_drough_shade, const float* dL_dviewdirs, const float* dL_dscales,
+                                  const float* dL_drot, const float* dL_dopacity, const float* dL_dmeans3D, float* g_xyz,
+                                  float* g_scaling, float* g_rotation, float* g_opacity, float* g_normal, float* g_base,
+                                  float* g_rough, int He, int We,
+                                       const float* env_raw, const float* env, float* dL_denv, float w_tv,
+                                       float* g_env_raw, float* tv_sum, int consume, float* records, const int* layout)
+{
+    if (P < 0) return invalid("stage2_activate_backward: bad P");
+    if (He < 0 || We < 0) return invalid("stage2_activate_backward: bad texture size");
+    const bool env_job = He * We != 0;
+    if (env_job && (!env_raw || !env || !dL_denv || !g_env_raw)) return invalid("stage2_activate_backward: null texture buffer");
+    if (P == 0) return env_job ? r3dg_stage2_env_backward(stream_, He, We, env_raw, env, dL_denv, w_tv, g_env_raw, tv_sum, consume) : R3DG_OK;
+    if (!base_raw || !rough_raw || !(dL_dfeatures || records) || !dL_dbase_shade || !dL_drough_shade || !g_base || !g_rough)
+        return invalid("stage2_activate_backward: null buffer");
+    GradRecordLayout L;
+    if (records != nullptr) {
+        if (int e = record_layout_16("stage2_activate_backward_with_records", layout, &L)) return e;
+        if (g_xyz == nullptr) return invalid("stage2_activate_backward_with_records: frozen geometry reads no gradient records");
+    }
+    // g_xyz == NULL: frozen geometry -- only g_base / g_rough are produced and the geometry inputs are not read
+    if (g_xyz != nullptr &&
+        (!xyz || !scaling_raw || !rotation_raw || !opacity_raw || !normal_raw || !viewmatrix || !campos || !dL_dviewdirs ||
+         !dL_dscales || !dL_drot || !(dL_dopacity || records) || !dL_dmeans3D || !g_scaling || !g_rotation || !g_opacity || !g_normal))
+        return invalid("stage2_activate_backward: null buffer");
+    return guarded([&]() -> int {
+        StageTimer t((hipStream_t)stream_, ST_S2_ACTIVATE_BWD);
+        launch_s2_activate_backward((hipStream_t)stream_, P, xyz, scaling_raw, rotation_raw, opacity_raw, normal_raw,
+                                    base_raw, rough_raw, viewmatrix, campos, dL_dfeatures, dL_dbase_shade,
+                                    dL_drough_shade, dL_dviewdirs, dL_dscales, dL_drot, dL_dopacity, dL_dmeans3D, g_xyz,
+                                    g_scaling, g_rotation, g_opacity, g_normal, g_base, g_rough, env_job ? He : 0, env_job ? We : 0,
+                                    env_job ? env_raw : nullptr, env, dL_denv, w_tv, g_env_raw, tv_sum, consume, records,
+                                    records != nullptr ? &L : nullptr);
+        return R3DG_OK;
+    });
+}
+
 int r3dg_stage2_activate_backward_with(void* stream_, int P, const float* xyz, const float* scaling_raw,
                                   const float* rotation_raw, const float* opacity_raw, const float* normal_raw,
                                   const float* base_raw, const float* rough_raw, const float* viewmatrix,
@@ -108,27 +180,29 @@ int r3dg_stage2_activate_backward_with(void* stream_, int P, const float* xyz, c
                                        const float* env_raw, const float* env, float* dL_denv, float w_tv,
                                        float* g_env_raw, float* tv_sum, int consume)
 {
-    if (P < 0) return invalid("stage2_activate_backward: bad P");
-    if (He < 0 || We < 0) return invalid("stage2_activate_backward: bad texture size");
-    const bool env_job = He * We != 0;
-    if (env_job && (!env_raw || !env || !dL_denv || !g_env_raw)) return invalid("stage2_activate_backward: null texture buffer");
-    if (P == 0) return env_job ? r3dg_stage2_env_backward(stream_, He, We, env_raw, env, dL_denv, w_tv, g_env_raw, tv_sum, consume) : R3DG_OK;
-    if (!base_raw || !rough_raw || !dL_dfeatures || !dL_dbase_shade || !dL_drough_shade || !g_base || !g_rough)
-        return invalid("stage2_activate_backward: null buffer");
-    // g_xyz == NULL: frozen geometry -- only g_base / g_rough are produced and the geometry inputs are not read
-    if (g_xyz != nullptr &&
-        (!xyz || !scaling_raw || !rotation_raw || !opacity_raw || !normal_raw || !viewmatrix || !campos || !dL_dviewdirs ||
-         !dL_dscales || !dL_drot || !dL_dopacity || !dL_dmeans3D || !g_scaling || !g_rotation || !g_opacity || !g_normal))
-        return invalid("stage2_activate_backward: null buffer");
-    return guarded([&]() -> int {
-        StageTimer t((hipStream_t)stream_, ST_S2_ACTIVATE_BWD);
-        launch_s2_activate_backward((hipStream_t)stream_, P, xyz, scaling_raw, rotation_raw, opacity_raw, normal_raw,
-                                    base_raw, rough_raw, viewmatrix, campos, dL_dfeatures, dL_dbase_shade,
-                                    dL_drough_shade, dL_dviewdirs, dL_dscales, dL_drot, dL_dopacity, dL_dmeans3D, g_xyz,
-                                    g_scaling, g_rotation, g_opacity, g_normal, g_base, g_rough, env_job ? He : 0, env_job ? We : 0,
-                                    env_job ? env_raw : nullptr, env, dL_denv, w_tv, g_env_raw, tv_sum, consume);
-        return R3DG_OK;
-    });
+    if (P > 0 && (!dL_dfeatures || (g_xyz != nullptr && !dL_dopacity))) return invalid("stage2_activate_backward: null buffer");
+    return activate_backward_impl(stream_, P, xyz, scaling_raw, rotation_raw, opacity_raw, normal_raw, base_raw, rough_raw,
+                                  viewmatrix, campos, dL_dfeatures, dL_dbase_shade, dL_drough_shade, dL_dviewdirs, dL_dscales,
+                                  dL_drot, dL_dopacity, dL_dmeans3D, g_xyz, g_scaling, g_rotation, g_opacity, g_normal, g_base,
+                                  g_rough, He, We, env_raw, env, dL_denv, w_tv, g_env_raw, tv_sum, consume, nullptr, nullptr);
+}
+
+int r3dg_stage2_activate_backward_with_records(void* stream_, int P, const float* xyz, const float* scaling_raw,
+                                  const float* rotation_raw, const float* opacity_raw, const float* normal_raw,
+                                  const float* base_raw, const float* rough_raw, const float* viewmatrix,
+                                  const float* campos, float* records, const int* layout, const float* dL_dbase_shade,
+                                  const float* dL_drough_shade, const float* dL_dviewdirs, const float* dL_dscales,
+                                  const float* dL_drot, const float* dL_dmeans3D, float* g_xyz,
+                                  float* g_scaling, float* g_rotation, float* g_opacity, float* g_normal, float* g_base,
+                                  float* g_rough, int He, int We,
+                                       const float* env_raw, const float* env, float* dL_denv, float w_tv,
+                                       float* g_env_raw, float* tv_sum, int consume)
+{
+    if (P > 0 && !records) return invalid("stage2_activate_backward_with_records: null buffer");
+    return activate_backward_impl(stream_, P, xyz, scaling_raw, rotation_raw, opacity_raw, normal_raw, base_raw, rough_raw,
+                                  viewmatrix, campos, nullptr, dL_dbase_shade, dL_drough_shade, dL_dviewdirs, dL_dscales,
+                                  dL_drot, nullptr, dL_dmeans3D, g_xyz, g_scaling, g_rotation, g_opacity, g_normal, g_base,
+                                  g_rough, He, We, env_raw, env, dL_denv, w_tv, g_env_raw, tv_sum, consume, records, layout);
 }
 
 int r3dg_stage2_loss(void* stream_, int width, int height, const float* image, const float* opacity,

@@ -37,6 +37,32 @@ void launch_render_backward(hipStream_t s, int P, int W, int H, int S, int n_act
                             const float* dL_dpix, const float* dL_dpix_o, const float* dL_dpix_d, const float* dL_dpix_f,
                             float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dfeature,
                             int bg_geom);
+// launch_render_backward is (a) + (c) of three parts (rasterizer_render_bwd.hip):
+//   (a) launch_render_backward_fill: the tile kernel adds into the per-Gaussian gradient records of stream `s` (library scratch,
+//       zero between calls) -> the records; `tiles` false (nothing was rendered): no launch, the rows are zeros;
+//   (b) GradRecordLayout: the record channel of every value the tile kernel left (-1: not carried, the value is +0.f) -- what a
+//       kernel that reads the rows in place needs (r3dg_hip.h: the same R3DG_GRAD_RECORD_LAYOUT_INTS ints, in this order);
+//   (c) launch_gradient_records_scatter: rows -> the op's five arrays, zeros -> the rows.
+// Between (a) and the launch that zeroes the rows the buffer counts as dirty; (c) and gradient_records_zeroed end that.
+struct GradRecordLayout {
+    int nvp;                         // floats per record
+    int color[3];
+    int sx, sy, depth;               // first moments; the depth side channel (-1 in the instances without one)
+    int sxx, sxy, syy, opacity;
+    int feature[R3DG_MAX_S_BWD];     // by feature column
+};
+static_assert(sizeof(GradRecordLayout) == R3DG_GRAD_RECORD_LAYOUT_INTS * sizeof(int), "GradRecordLayout is the C ABI's int array");
+GradRecordLayout render_backward_layout(int S, int n_active, const int* active, bool depth_gradient, int bg_geom);
+float* launch_render_backward_fill(hipStream_t s, int P, int W, int H, int S, int n_active, const int* active,
+                                   const uint32_t* tile_order, const uint32_t* ranges, const uint32_t* point_list,
+                                   const float* bg, const float* splat, const float* features, const float* final_Ts,
+                                   const uint32_t* n_contrib, const float* dL_dpix, const float* dL_dpix_o,
+                                   const float* dL_dpix_d, const float* dL_dpix_f, int bg_geom, bool tiles,
+                                   GradRecordLayout* layout);
+void launch_gradient_records_scatter(hipStream_t s, int P, int S, float* rec, const GradRecordLayout& layout, float* dL_dmean2D,
+                                     float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dfeature);
+bool gradient_record_layout_valid(const GradRecordLayout& layout, int S);
+void gradient_records_zeroed(const float* rec);
 void launch_render_backward_features(hipStream_t s, int W, int H, int S, int n_active, const int* active,
                                      const uint32_t* tile_order, const uint32_t* ranges, const uint32_t* point_list,
                                      const float* splat, const float* final_Ts, const uint32_t* n_contrib,
@@ -49,14 +75,40 @@ struct ShAdamArgs {
     const float* skip_flag;
 };
 bool preprocess_backward_applies_adam(int M);
-// `adam` != nullptr: dL_dsh is NOT written; parameters and moments of the group are updated in place instead
+// Where the per-Gaussian kernel finds the sums the tile backward left for Gaussian g: value k of a group at
+// base[g * stride + off[k]].  Either the op's arrays (dL_dmean2D [P,3], dL_dconic [P,4], dL_dcolor [P,3]: tile_grad_arrays) or the
+// gradient record rows, read in place (tile_grad_records).  `records` != 0 also means that nothing has written dL_dmean2D yet:
+// the kernel then writes all three of its columns, for Gaussians outside the view too.
+struct TileGradSource {
+    const float* mean2D;
+    const float* conic;
+    const float* color;
+    int mean2D_stride, conic_stride, color_stride;
+    int sx, sy, depth;               // depth < 0: the side channel is +0.f
+    int sxx, sxy, syy;
+    int c[3];
+    int records;
+};
+inline TileGradSource tile_grad_arrays(const float* dL_dmean2D, const float* dL_dconic, const float* dL_dcolor)
+{
+    return TileGradSource{dL_dmean2D, dL_dconic, dL_dcolor, 3, 4, 3, 0, 1, 2, 0, 1, 3, {0, 1, 2}, 0};
+}
+inline TileGradSource tile_grad_records(const float* rec, const GradRecordLayout& L)
+{
+    return TileGradSource{rec, rec, rec, L.nvp, L.nvp, L.nvp, L.sx, L.sy, L.depth, L.sxx, L.sxy, L.syy,
+                          {L.color[0], L.color[1], L.color[2]}, 1};
+}
+// `adam` != nullptr: dL_dsh is NOT written; parameters and moments of the group are updated in place instead.
+// `records` != nullptr: the tile backward's sums are read from the record rows (`layout`), not from dL_dmean2D / dL_dconic /
+// dL_dcolor (the latter two may then be NULL); dL_dmean2D is written in full.
 void launch_preprocess_backward(hipStream_t s, int P, int D, int M, const float* means, const int* radii, const float* shs,
                                 const uint8_t* clamped, const float* scales, const float* rotations, float scale_modifier,
                                 const float* cov3Ds, const float* vm, const float* proj, float h_x, float h_y,
                                 float tan_fovx, float tan_fovy, const float* campos, float* dL_dmean2D,
                                 const float* dL_dconic, const float* conic_opacity, int W, int H, float* dL_dmeans,
                                 const float* dL_dcolor, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                                const ShAdamArgs* adam);
+                                const ShAdamArgs* adam, const float* records = nullptr,
+                                const GradRecordLayout* layout = nullptr);
 void launch_shade_forward(hipStream_t s, int P, int K, int M, const float* base_color, const float* roughness,
                           const float* normals, const float* viewdirs, const float* incidents, const float* env, int He,
                           int We, const float* tr, const float* visibility, const float* dirs, const float* areas,
@@ -148,7 +200,10 @@ void launch_s2_pack(hipStream_t s, int P, const float* xyz, const float* viewmat
                     const float* base_color, const float* roughness, const float* shade_out, float* features,
                     float* light_l1_sum);
 void launch_s2_unpack(hipStream_t s, int P, const float* dL_dfeatures, const float* shade_out, float light_weight,
-                      float* dL_dpbr, float* dL_ddiffuse, float* block_absmax, float* light_l1_sum);
+                      float* dL_dpbr, float* dL_ddiffuse, float* block_absmax, float* light_l1_sum,
+                      const float* records = nullptr, const GradRecordLayout* layout = nullptr);
+// `records` + `layout` (16-float rows): the feature columns and the opacity gradient are read from the gradient record rows, not
+// from dL_dfeatures / dL_dopacity (which may then be NULL); launch_s2_activate_backward, the last reader, zeroes the rows
 void launch_s2_activate_backward(hipStream_t s, int P, const float* xyz, const float* scaling_raw, const float* rotation_raw,
                                  const float* opacity_raw, const float* normal_raw, const float* base_raw,
                                  const float* rough_raw, const float* viewmatrix, const float* campos,
@@ -157,7 +212,8 @@ void launch_s2_activate_backward(hipStream_t s, int P, const float* xyz, const f
                                  const float* dL_dopacity, const float* dL_dmeans3D, float* g_xyz, float* g_scaling,
                                  float* g_rotation, float* g_opacity, float* g_normal, float* g_base, float* g_rough, int He,
                                  int We, const float* env_raw, const float* env, float* dL_denv, float w_tv,
-                                 float* g_env_raw, float* tv_sum, int consume);
+                                 float* g_env_raw, float* tv_sum, int consume, float* records = nullptr,
+                                 const GradRecordLayout* layout = nullptr);
 void launch_s2_loss(hipStream_t s, int HW, const float* image, const float* opacity, const float* feature,
                     const float* pseudo_normal, const int* n_contrib, const float* gt, const float* bg,
                     const float* image_mask, float w_l1, float w_pbr, float w_normal, const float* extra_dimage,

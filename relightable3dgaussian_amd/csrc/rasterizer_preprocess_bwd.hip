@@ -54,6 +54,9 @@ __device__ const float bSH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0
 // multiply-adds in the per-Gaussian part), so dL_dmeans3D came out a few ulp apart with and without the update; one instruction
 // stream for that part keeps every geometry output bit for bit the same whichever tail runs.
 // `shs` IS the parameter array the tail updates -- through a pointer derived from `shs`, which is what its no-alias promise allows.
+// `src` (TileGradSource, launchers.hpp): the tile backward's sums come from the op's arrays or straight from the gradient record
+// rows -- for the same reason a run-time choice, and one that only enters the ADDRESSES of the nine loads (plus, on the record
+// path, the stores of the dL_dmean2D columns the scatter pass would have written): the arithmetic behind them is one stream.
 template <bool STAGED>
 __global__ void __launch_bounds__(256)
 preprocess_backward_kernel(int P, int D, int M, const float* __restrict__ means, const int* __restrict__ radii,
@@ -61,9 +64,9 @@ preprocess_backward_kernel(int P, int D, int M, const float* __restrict__ means,
                            const float* __restrict__ scales, const float* __restrict__ rotations, float scale_modifier,
                            const float* __restrict__ cov3Ds, const float* __restrict__ vm, const float* __restrict__ proj,
                            float h_x, float h_y, float tan_fovx, float tan_fovy, const float* __restrict__ campos,
-                           float* __restrict__ dL_dmean2D, const float* __restrict__ dL_dconics,
+                           float* __restrict__ dL_dmean2D, TileGradSource src,
                            const float4* __restrict__ conic_opacity, float half_w, float half_h,
-                           float* __restrict__ dL_dmeans, const float* __restrict__ dL_dcolor,
+                           float* __restrict__ dL_dmeans,
                            float* __restrict__ dL_dcov3D, float* __restrict__ dL_dsh, float* __restrict__ dL_dscale,
                            float* __restrict__ dL_drot, ShAdamArgs adam)
 {
@@ -90,6 +93,10 @@ preprocess_backward_kernel(int P, int D, int M, const float* __restrict__ means,
         // caller can hand in uninitialised memory (saves five zero-fill launches per backward)
 #pragma unroll
         for (int i = 0; i < 3; i++) dL_dmeans[3 * idx + i] = 0.f;
+        if (src.records) {           // (the scatter pass wrote the untouched record there: zeros)
+#pragma unroll
+            for (int i = 0; i < 3; i++) dL_dmean2D[3 * idx + i] = 0.f;
+        }
 #pragma unroll
         for (int i = 0; i < 6; i++) dL_dcov3D[6 * idx + i] = 0.f;
         if (shs != nullptr) {
@@ -113,14 +120,17 @@ preprocess_backward_kernel(int P, int D, int M, const float* __restrict__ means,
     // with (A, B, C) the conic the forward stored (GeometryState::conic_opacity, the values the tile kernels blended with).  The
     // final dL_dmean2D goes back to its slot: it is an OUTPUT of the op (the viewspace gradient the densification reads).
     const float4 co = conic_opacity[idx];
-    const float s_x = dL_dmean2D[3 * idx], s_y = dL_dmean2D[3 * idx + 1], g2z = dL_dmean2D[3 * idx + 2];
+    const float* m2 = src.mean2D + (size_t)idx * src.mean2D_stride;
+    const float s_x = m2[src.sx], s_y = m2[src.sy], g2z = src.depth < 0 ? 0.f : m2[src.depth];
     const float g2x = -half_w * (co.x * s_x + co.y * s_y), g2y = -half_h * (co.z * s_y + co.y * s_x);
     dL_dmean2D[3 * idx] = g2x;
     dL_dmean2D[3 * idx + 1] = g2y;
+    if (src.records) dL_dmean2D[3 * idx + 2] = g2z;
 
     // ---------------- K12: conic -> cov2D -> cov3D / mean (backward.cu:144-276) ----------------
     const float* c3 = cov3Ds + 6 * idx;
-    const float dcx = -0.5f * dL_dconics[4 * idx], dcy = -0.5f * dL_dconics[4 * idx + 1], dcw = -0.5f * dL_dconics[4 * idx + 3];
+    const float* cn = src.conic + (size_t)idx * src.conic_stride;
+    const float dcx = -0.5f * cn[src.sxx], dcy = -0.5f * cn[src.sxy], dcw = -0.5f * cn[src.syy];
     float tx = vm[0] * mx + vm[4] * my + vm[8] * mz + vm[12];
     float ty = vm[1] * mx + vm[5] * my + vm[9] * mz + vm[13];
     const float tz = vm[2] * mx + vm[6] * my + vm[10] * mz + vm[14];
@@ -221,7 +231,7 @@ preprocess_backward_kernel(int P, int D, int M, const float* __restrict__ means,
         for (int ch = 0; ch < 3; ch++) {
 #define SH(k) (STAGED ? shv[(k) * 3 + ch] : sh[(k) * 3 + ch])
 #define DSH(k) dsh[(k) * 3 + ch]
-            const float g = dL_dcolor[3 * idx + ch] * (clamped[3 * idx + ch] ? 0.f : 1.f);
+            const float g = src.color[(size_t)idx * src.color_stride + src.c[ch]] * (clamped[3 * idx + ch] ? 0.f : 1.f);
             float dRx = 0, dRy = 0, dRz = 0;
             for (int k = (D + 1) * (D + 1); k < M; k++) DSH(k) = 0.f;      // coefficients above the active degree
             DSH(0) = bSH_C0 * g;
@@ -374,9 +384,11 @@ void launch_preprocess_backward(hipStream_t s, int P, int D, int M, const float*
                                 float h_y, float tan_fovx, float tan_fovy, const float* campos, float* dL_dmean2D,
                                 const float* dL_dconic, const float* conic_opacity, int W, int H, float* dL_dmeans,
                                 const float* dL_dcolor, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                                const ShAdamArgs* adam)
+                                const ShAdamArgs* adam, const float* records, const GradRecordLayout* layout)
 {
     if (P <= 0) return;
+    const TileGradSource src = records != nullptr && layout != nullptr ? tile_grad_records(records, *layout)
+                                                                       : tile_grad_arrays(dL_dmean2D, dL_dconic, dL_dcolor);
     // SH rows through LDS when there are SH coefficients of at most degree 3 (256 x 49 words = 49 KB per block)
     const bool staged = opt(R3DG_OPT_STAGE_SH_ROWS) && shs != nullptr && M >= 1 && M <= 16;
     // (adam != nullptr: the C-ABI wrapper refused the call unless preprocess_backward_applies_adam(M) and shs != NULL, so the
@@ -385,12 +397,12 @@ void launch_preprocess_backward(hipStream_t s, int P, int D, int M, const float*
     if (staged)
         preprocess_backward_kernel<true><<<(P + 255) / 256, 256, 256 * staged_row_stride_host(3 * M) * sizeof(float), s>>>(
             P, D, M, means, radii, shs, clamped, scales, rotations, scale_modifier, cov3Ds, vm, proj, h_x, h_y, tan_fovx,
-            tan_fovy, campos, dL_dmean2D, dL_dconic, (const float4*)conic_opacity, 0.5f * W, 0.5f * H, dL_dmeans, dL_dcolor, dL_dcov3D,
+            tan_fovy, campos, dL_dmean2D, src, (const float4*)conic_opacity, 0.5f * W, 0.5f * H, dL_dmeans, dL_dcov3D,
             dL_dsh, dL_dscale, dL_drot, adam != nullptr ? *adam : none);
     else
         preprocess_backward_kernel<false><<<(P + 255) / 256, 256, 0, s>>>(
             P, D, M, means, radii, shs, clamped, scales, rotations, scale_modifier, cov3Ds, vm, proj, h_x, h_y, tan_fovx,
-            tan_fovy, campos, dL_dmean2D, dL_dconic, (const float4*)conic_opacity, 0.5f * W, 0.5f * H, dL_dmeans, dL_dcolor, dL_dcov3D,
+            tan_fovy, campos, dL_dmean2D, src, (const float4*)conic_opacity, 0.5f * W, 0.5f * H, dL_dmeans, dL_dcov3D,
             dL_dsh, dL_dscale, dL_drot, none);
 }
 

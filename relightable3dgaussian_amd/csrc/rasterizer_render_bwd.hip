@@ -15,6 +15,7 @@
 #include "launchers.hpp"
 #include "wave_reduce.hpp"
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -442,8 +443,10 @@ render_backward_scatter_kernel(int P, int S, int NF, ChannelList chan_list, floa
 }
 
 // The records: library scratch per (device, stream), zero whenever no backward is in flight on that stream -- the scatter kernel
-// zeroes what the tile kernel may have written.  `dirty` guards the invariant on the host: set before the tile kernel is
-// enqueued, cleared once the scatter kernel is; a call that finds it set (an enqueue in between failed) clears the buffer itself.
+// zeroes what the tile kernel may have written, and so does the last of the kernels that read the rows in place where no scatter
+// pass runs (s2_activate_backward_kernel).  `dirty` guards the invariant on the host: set before the tile kernel is enqueued,
+// cleared once the launch that zeroes the rows is (gradient_records_zeroed); a call that finds it set (an enqueue in between
+// failed, or the in-place readers of an earlier fill never ran) clears the buffer itself.
 namespace {
 struct RecordState { float* p = nullptr; size_t cap = 0; bool dirty = false; };
 std::mutex g_records_mu;
@@ -620,16 +623,22 @@ void launch_render_backward_features(hipStream_t s, int W, int H, int S, int n_a
 }
 
 
-void launch_render_backward(hipStream_t s, int P, int W, int H, int S, int n_active, const int* active,
-                            const uint32_t* tile_order, const uint32_t* ranges, const uint32_t* point_list,
-                            const float* bg, const float* splat, const float* features, const float* final_Ts,
-                            const uint32_t* n_contrib, const float* dL_dpix, const float* dL_dpix_o,
-                            const float* dL_dpix_d, const float* dL_dpix_f, float* dL_dmean2D, float* dL_dconic,
-                            float* dL_dopacity, float* dL_dcolor, float* dL_dfeature, int bg_geom)
-{
-    const int tiles_x = (W + R3DG_TILE_X - 1) / R3DG_TILE_X, tiles_y = (H + R3DG_TILE_Y - 1) / R3DG_TILE_Y;
-    const int T = tiles_x * tiles_y;
+// ---- the tile backward in three parts: (a) fill the records, (b) say what lies where in them, (c) scatter them to the arrays -----
+// The instance launch_render_backward runs for a call -- chosen from the arguments alone, so (b) needs no launch.
+namespace {
+struct BackwardInstance {
     ChannelList cl;
+    int spad;          // feature slots the kernel carries (a multiple of 4)
+    bool row4;         // every feature channel carried, float4-aligned rows: the payload is read as float4s
+    bool lean;         // the instance without a depth slot
+    bool smallv;       // 16-wide reduction
+    int nvp;           // record width in floats
+};
+
+BackwardInstance choose_instance(int S, int n_active, const int* active, bool depth_gradient, int bg_geom)
+{
+    BackwardInstance in;
+    ChannelList& cl = in.cl;
     if (n_active < 0 || active == nullptr) {
         cl.n = S;
         cl.identity = 1;
@@ -640,21 +649,71 @@ void launch_render_backward(hipStream_t s, int P, int W, int H, int S, int n_act
         for (int i = 0; i < R3DG_MAX_S_BWD; i++) cl.c[i] = i < n_active ? active[i] : 0;
     }
     const int SP = cl.n;                 // channels the kernel carries
-    const int grid = ((T + 7) / 8) * 8 * 4;       // 4 single-wave workgroups per tile, tile ranks padded to a multiple of 8
     // ROW4: every feature channel is carried and the rows are float4-aligned (S == SPAD): the payload is read as float4s
-    const bool row4 = cl.identity != 0 && (S & 3) == 0;
-    const int spad = (SP + 3) / 4 * 4;
+    in.row4 = cl.identity != 0 && (S & 3) == 0;
+    in.spad = (SP + 3) / 4 * 4;
     // LEAN: no depth gradient (the caller passed no dL_dout_depth), at least one padding slot among the SPAD feature slots, the
     // geometry part of dL_dalpha on (what every caller passes); only instantiated where it pays: up to 8 feature slots
-    const bool lean = dL_dpix_d == nullptr && bg_geom != 0 && SP >= 1 && SP < spad && spad <= 8 && !row4;
+    const bool lean = !depth_gradient && bg_geom != 0 && SP >= 1 && SP < in.spad && in.spad <= 8 && !in.row4;
     // reduction / record width of the instance that runs (the channels past it, if any, are padding feature slots)
-    const bool use_lean = lean && opt(R3DG_OPT_BWD_LEAN) != 0;
-    const int nv = use_lean ? 8 + spad : 10 + spad;
-    const bool smallv = use_lean || spad == 4 || (spad == 8 && cl.n <= 6);
-    const int nvp = smallv ? 16 : next_pow2(nv);
+    in.lean = lean && opt(R3DG_OPT_BWD_LEAN) != 0;
+    const int nv = in.lean ? 8 + in.spad : 10 + in.spad;
+    in.smallv = in.lean || in.spad == 4 || (in.spad == 8 && cl.n <= 6);
+    in.nvp = in.smallv ? 16 : next_pow2(nv);
+    return in;
+}
+
+// (b) of an instance: the record channel of every value (render_backward_wave_kernel's channel table), the feature columns as
+// render_backward_scatter_kernel maps them (slot t of the list -> channel V_FEAT + t while it lies inside the record)
+GradRecordLayout layout_of(const BackwardInstance& in)
+{
+    GradRecordLayout L;
+    const int v_conic = in.lean ? 5 : 6, v_opac = v_conic + 3, v_feat = v_opac + 1;
+    const int nf = in.lean ? in.spad - 1 : in.spad;
+    L.nvp = in.nvp;
+    for (int c = 0; c < 3; c++) L.color[c] = c;
+    L.sx = 3;
+    L.sy = 4;
+    L.depth = in.lean ? -1 : 5;
+    L.sxx = v_conic;
+    L.sxy = v_conic + 1;
+    L.syy = v_conic + 2;
+    L.opacity = v_opac;
+    for (int c = 0; c < R3DG_MAX_S_BWD; c++) L.feature[c] = -1;
+    const int n = in.cl.n < nf ? in.cl.n : nf;
+    for (int t = 0; t < n && t < in.nvp - v_feat; t++) L.feature[in.cl.identity ? t : in.cl.c[t]] = v_feat + t;
+    return L;
+}
+}  // namespace
+
+GradRecordLayout render_backward_layout(int S, int n_active, const int* active, bool depth_gradient, int bg_geom)
+{
+    return layout_of(choose_instance(S, n_active, active, depth_gradient, bg_geom));
+}
+
+// (a) -> the records of stream `s`, P rows of layout.nvp floats, the tile kernel enqueued into them when `tiles` (R > 0; without
+// it the rows are the zeros the buffer holds between calls).  The buffer is marked dirty: whoever enqueues the launch that
+// zeroes the rows again -- (c), or the last of the kernels that read the rows in place -- clears the mark
+// (gradient_records_zeroed); a fill that finds it still set clears the whole buffer first.
+float* launch_render_backward_fill(hipStream_t s, int P, int W, int H, int S, int n_active, const int* active,
+                                   const uint32_t* tile_order, const uint32_t* ranges, const uint32_t* point_list,
+                                   const float* bg, const float* splat, const float* features, const float* final_Ts,
+                                   const uint32_t* n_contrib, const float* dL_dpix, const float* dL_dpix_o,
+                                   const float* dL_dpix_d, const float* dL_dpix_f, int bg_geom, bool tiles,
+                                   GradRecordLayout* layout)
+{
+    const int tiles_x = (W + R3DG_TILE_X - 1) / R3DG_TILE_X, tiles_y = (H + R3DG_TILE_Y - 1) / R3DG_TILE_Y;
+    const int T = tiles_x * tiles_y;
+    const BackwardInstance in = choose_instance(S, n_active, active, dL_dpix_d != nullptr, bg_geom);
+    const ChannelList& cl = in.cl;
+    const bool row4 = in.row4;
+    const int spad = in.spad;
+    const int grid = ((T + 7) / 8) * 8 * 4;       // 4 single-wave workgroups per tile, tile ranks padded to a multiple of 8
+    if (layout != nullptr) *layout = layout_of(in);
     bool* dirty = nullptr;
-    float* rec = gradient_records(s, (size_t)P * nvp, &dirty);
+    float* rec = gradient_records(s, (size_t)P * in.nvp, &dirty);
     *dirty = true;
+    if (!tiles) return rec;
 #define R3DG_BWD_ARGS                                                                                                  \
     (const uint2*)ranges, point_list, S, cl, W, H, tiles_x, T, opt(R3DG_OPT_CULL), tile_order, bg, (const float4*)splat, features,       \
         final_Ts, n_contrib, dL_dpix, dL_dpix_o, dL_dpix_d, dL_dpix_f, rec, bg_geom
@@ -663,7 +722,7 @@ void launch_render_backward(hipStream_t s, int P, int W, int H, int S, int n_act
         if (row4) render_backward_wave_kernel<SP_, SV, true, false><<<grid, 64, 0, s>>>(R3DG_BWD_ARGS);                \
         else render_backward_wave_kernel<SP_, SV, false, false><<<grid, 64, 0, s>>>(R3DG_BWD_ARGS);                    \
     } while (0)
-    if (use_lean) {
+    if (in.lean) {
         // 9 + (SPAD - 1) reduction channels: 12 (SPAD 4) and 16 (SPAD 8) -- both reduce 16-wide
         if (spad == 4) render_backward_wave_kernel<4, true, false, true><<<grid, 64, 0, s>>>(R3DG_BWD_ARGS);
         else render_backward_wave_kernel<8, true, false, true><<<grid, 64, 0, s>>>(R3DG_BWD_ARGS);
@@ -682,20 +741,84 @@ void launch_render_backward(hipStream_t s, int P, int W, int H, int S, int n_act
             default: R3DG_BWD(36, false); break;
         }
     }
-    // records -> the op's output arrays
-    const int nf = use_lean ? spad - 1 : spad;
+#undef R3DG_BWD
+#undef R3DG_BWD_ARGS
+    return rec;
+}
+
+// the launch that zeroes the rows of `rec` again has been enqueued: if `rec` is library scratch of this device, it is clean
+void gradient_records_zeroed(const float* rec)
+{
+    int dev = 0;
+    R3DG_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_records_mu);
+    for (auto& kv : g_records)
+        if (kv.first.first == dev && kv.second.p == rec && rec != nullptr) kv.second.dirty = false;
+}
+
+// (c) records -> the op's output arrays (and zeros into the records).  The kernel's channel list is rebuilt from the layout: slot
+// t = the feature column whose channel is V_FEAT + t, which is how (b) numbered them.
+void launch_gradient_records_scatter(hipStream_t s, int P, int S, float* rec, const GradRecordLayout& L, float* dL_dmean2D,
+                                     float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dfeature)
+{
+    const bool lean = L.depth < 0;
+    const int v_feat = L.opacity + 1;
+    ChannelList cl;
+    cl.n = 0;
+    cl.identity = 0;
+    for (int i = 0; i < R3DG_MAX_S_BWD; i++) cl.c[i] = 0;
+    for (int c = 0; c < S && c < R3DG_MAX_S_BWD; c++)
+        if (L.feature[c] >= v_feat && L.feature[c] < L.nvp) {
+            cl.c[L.feature[c] - v_feat] = c;
+            cl.n = std::max(cl.n, L.feature[c] - v_feat + 1);
+        }
+    const int nf = L.nvp - v_feat;
     const int sgrid = (P + 255) / 256;
 #define R3DG_SCATTER(NVP_, LEAN_)                                                                                      \
     render_backward_scatter_kernel<NVP_, LEAN_><<<sgrid, 256, 0, s>>>(P, S, nf, cl, (float4*)rec, dL_dmean2D, dL_dconic, dL_dopacity, \
                                                                        dL_dcolor, dL_dfeature)
-    if (use_lean) R3DG_SCATTER(16, true);
-    else if (nvp == 16) R3DG_SCATTER(16, false);
-    else if (nvp == 32) R3DG_SCATTER(32, false);
+    if (lean) R3DG_SCATTER(16, true);
+    else if (L.nvp == 16) R3DG_SCATTER(16, false);
+    else if (L.nvp == 32) R3DG_SCATTER(32, false);
     else R3DG_SCATTER(64, false);
 #undef R3DG_SCATTER
-    *dirty = false;
-#undef R3DG_BWD
-#undef R3DG_BWD_ARGS
+    gradient_records_zeroed(rec);
+}
+
+// what a caller may hand to launch_gradient_records_scatter: one of the layouts (b) produces
+bool gradient_record_layout_valid(const GradRecordLayout& L, int S)
+{
+    if (L.nvp != 16 && L.nvp != 32 && L.nvp != 64) return false;
+    const bool lean = L.depth < 0;
+    if (lean && L.nvp != 16) return false;
+    const int v_conic = lean ? 5 : 6;
+    if (L.color[0] != 0 || L.color[1] != 1 || L.color[2] != 2 || L.sx != 3 || L.sy != 4 || (!lean && L.depth != 5) ||
+        L.sxx != v_conic || L.sxy != v_conic + 1 || L.syy != v_conic + 2 || L.opacity != v_conic + 3)
+        return false;
+    bool seen[64] = {};
+    int n = 0, top = 0;
+    for (int c = 0; c < R3DG_MAX_S_BWD; c++) {
+        const int ch = L.feature[c];
+        if (ch < 0) continue;
+        if (c >= S || ch <= L.opacity || ch >= L.nvp || seen[ch]) return false;
+        seen[ch] = true;
+        n++;
+        top = std::max(top, ch - L.opacity);
+    }
+    return n == top;                        // the channels used are V_FEAT .. V_FEAT + n - 1, each once
+}
+
+void launch_render_backward(hipStream_t s, int P, int W, int H, int S, int n_active, const int* active,
+                            const uint32_t* tile_order, const uint32_t* ranges, const uint32_t* point_list,
+                            const float* bg, const float* splat, const float* features, const float* final_Ts,
+                            const uint32_t* n_contrib, const float* dL_dpix, const float* dL_dpix_o,
+                            const float* dL_dpix_d, const float* dL_dpix_f, float* dL_dmean2D, float* dL_dconic,
+                            float* dL_dopacity, float* dL_dcolor, float* dL_dfeature, int bg_geom)
+{
+    GradRecordLayout layout;
+    float* rec = launch_render_backward_fill(s, P, W, H, S, n_active, active, tile_order, ranges, point_list, bg, splat, features,
+                                             final_Ts, n_contrib, dL_dpix, dL_dpix_o, dL_dpix_d, dL_dpix_f, bg_geom, true, &layout);
+    launch_gradient_records_scatter(s, P, S, rec, layout, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dfeature);
 }
 
 }  // namespace r3dg

@@ -127,10 +127,18 @@ s2_pack_features_kernel(int P, const float* __restrict__ xyz, const float* __res
 // light_weight * sum_c |dl_c - mean(dl)|
 // block_absmax (may be NULL): [gridDim.x] floats, max |upstream gradient| of the block's rows, +inf if any is not finite --
 // the scale of the shading backward's fixed-point texture accumulation (shading.hip), so that op needs no reduction pass
+// `rec` (UnpackRecords; rows == NULL: the [P,16] array dL_dfeatures is the source): the six columns straight from the tile backward's
+// gradient record rows -- a run-time choice of where the six loads go, uniform over the grid; everything behind them is one stream
+struct UnpackRecords {
+    const float* rows;
+    int nvp;
+    int ch[6];          // record channel of columns 2, 3, 4, 12, 13, 14; -1: the column was not carried and reads as +0.f
+};
+
 __global__ void __launch_bounds__(256)
 s2_unpack_kernel(int P, const float* __restrict__ dL_dfeatures, const float* __restrict__ shade_out, float light_weight,
                  float* __restrict__ dL_dpbr, float* __restrict__ dL_ddiffuse, float* __restrict__ block_absmax,
-                 float* __restrict__ light_l1_sum)
+                 float* __restrict__ light_l1_sum, UnpackRecords rec)
 {
     __shared__ float s_m[4];
     __shared__ float s_l1[4];
@@ -138,8 +146,20 @@ s2_unpack_kernel(int P, const float* __restrict__ dL_dfeatures, const float* __r
     float m = 0.f, l1 = 0.f;
     bool bad = false;
     if (i < P) {
-        const float4* g = reinterpret_cast<const float4*>(dL_dfeatures + 16 * (size_t)i);
-        const float4 g0 = g[0], g1 = g[1], g3 = g[3];
+        float4 g0, g1, g3;
+        if (rec.rows == nullptr) {
+            const float4* g = reinterpret_cast<const float4*>(dL_dfeatures + 16 * (size_t)i);
+            g0 = g[0]; g1 = g[1]; g3 = g[3];
+        } else {
+            const float* r = rec.rows + (size_t)i * rec.nvp;
+            g0.x = g0.y = g1.y = g1.z = g1.w = g3.w = 0.f;        // (not read)
+            g0.z = rec.ch[0] < 0 ? 0.f : r[rec.ch[0]];
+            g0.w = rec.ch[1] < 0 ? 0.f : r[rec.ch[1]];
+            g1.x = rec.ch[2] < 0 ? 0.f : r[rec.ch[2]];
+            g3.x = rec.ch[3] < 0 ? 0.f : r[rec.ch[3]];
+            g3.y = rec.ch[4] < 0 ? 0.f : r[rec.ch[4]];
+            g3.z = rec.ch[5] < 0 ? 0.f : r[rec.ch[5]];
+        }
         const size_t i3 = 3 * (size_t)i;
         dL_dpbr[i3] = g0.z; dL_dpbr[i3 + 1] = g0.w; dL_dpbr[i3 + 2] = g1.x;
         const float* so = shade_out + 19 * (size_t)i;
@@ -221,6 +241,17 @@ s2_env_backward_kernel(EnvBackward a)
     env_backward_block((int)blockIdx.x, a);
 }
 
+// `rec` (ActivateRecords; rows == NULL: the arrays dL_dfeatures [P,16] and dL_dopacity are the source): the opacity gradient and the
+// nine feature columns this kernel reads, straight from the tile backward's 16-float gradient record rows.  A run-time choice of
+// where the loads go, uniform over the grid.  This kernel is the LAST reader of the rows (the unpack kernel ran in front of it on
+// the same stream, the per-Gaussian geometry backward has been joined): behind its loads each thread writes its row back as
+// zeros, which is the state the tile backward expects to find.
+struct ActivateRecords {
+    float* rows;
+    int opacity;
+    int col[12];        // record channel of feature column c (0, 1, 5..11 are read); -1: not carried, reads as +0.f
+};
+
 __global__ void __launch_bounds__(256)
 s2_activate_backward_kernel(int P, const float* __restrict__ xyz, const float* __restrict__ scaling_raw,
                             const float* __restrict__ rotation_raw, const float* __restrict__ opacity_raw,
@@ -233,7 +264,7 @@ s2_activate_backward_kernel(int P, const float* __restrict__ xyz, const float* _
                             const float* __restrict__ dL_dmeans3D, float* __restrict__ g_xyz,
                             float* __restrict__ g_scaling, float* __restrict__ g_rotation,
                             float* __restrict__ g_opacity, float* __restrict__ g_normal, float* __restrict__ g_base,
-                            float* __restrict__ g_rough, int nb_main, EnvBackward env_job)
+                            float* __restrict__ g_rough, int nb_main, EnvBackward env_job, ActivateRecords rec)
 {
     if ((int)blockIdx.x >= nb_main) {             // side job: the environment texture's chain rule (EnvBackward)
         env_backward_block((int)blockIdx.x - nb_main, env_job);
@@ -242,8 +273,22 @@ s2_activate_backward_kernel(int P, const float* __restrict__ xyz, const float* _
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= P) return;
     const size_t i3 = 3 * (size_t)i, i4 = 4 * (size_t)i;
-    const float4* gf = reinterpret_cast<const float4*>(dL_dfeatures + 16 * (size_t)i);
-    const float4 f0 = gf[0], f1 = gf[1], f2 = gf[2];
+    float4 f0, f1, f2;
+    float g_op_rec = 0.f;
+    if (rec.rows == nullptr) {
+        const float4* gf = reinterpret_cast<const float4*>(dL_dfeatures + 16 * (size_t)i);
+        f0 = gf[0]; f1 = gf[1]; f2 = gf[2];
+    } else {
+        float* r = rec.rows + 16 * (size_t)i;
+        auto column = [&](int c) { return rec.col[c] < 0 ? 0.f : r[rec.col[c]]; };
+        f0.x = column(0); f0.y = column(1);
+        f0.z = f0.w = f1.x = 0.f;                                  // (not read)
+        f1.y = column(5); f1.z = column(6); f1.w = column(7);
+        f2.x = column(8); f2.y = column(9); f2.z = column(10); f2.w = column(11);
+        g_op_rec = r[rec.opacity];
+        float4* z = reinterpret_cast<float4*>(r);
+        z[0] = z[1] = z[2] = z[3] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     // base_color = 0.03 + 0.77 sigmoid(raw), roughness = 0.09 + 0.9 sigmoid(raw): feature row + shading op
     {
         const float gfeat[3] = {f2.x, f2.y, f2.z};
@@ -282,7 +327,7 @@ s2_activate_backward_kernel(int P, const float* __restrict__ xyz, const float* _
     // opacity = sigmoid(raw)
     {
         const float s = sigmoidf_(opacity_raw[i]);
-        g_opacity[i] = dL_dopacity[i] * s * (1.f - s);
+        g_opacity[i] = (rec.rows == nullptr ? dL_dopacity[i] : g_op_rec) * s * (1.f - s);
     }
     // normal = raw / max(|raw|, 1e-3); only the feature row carries its gradient (the shading op sees normal.detach())
     {
@@ -450,10 +495,18 @@ void launch_s2_pack(hipStream_t s, int P, const float* xyz, const float* viewmat
 }
 
 void launch_s2_unpack(hipStream_t s, int P, const float* dL_dfeatures, const float* shade_out, float light_weight,
-                      float* dL_dpbr, float* dL_ddiffuse, float* block_absmax, float* light_l1_sum)
+                      float* dL_dpbr, float* dL_ddiffuse, float* block_absmax, float* light_l1_sum, const float* records,
+                      const GradRecordLayout* layout)
 {
+    UnpackRecords rec = {nullptr, 0, {-1, -1, -1, -1, -1, -1}};
+    if (records != nullptr && layout != nullptr) {
+        const int cols[6] = {2, 3, 4, 12, 13, 14};
+        rec.rows = records;
+        rec.nvp = layout->nvp;
+        for (int k = 0; k < 6; k++) rec.ch[k] = layout->feature[cols[k]];
+    }
     s2_unpack_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, dL_dfeatures, shade_out, light_weight, dL_dpbr, dL_ddiffuse,
-                                                    block_absmax, light_l1_sum);
+                                                    block_absmax, light_l1_sum, rec);
     check_launch(s, false, "s2_unpack_kernel");
 }
 
@@ -465,8 +518,15 @@ void launch_s2_activate_backward(hipStream_t s, int P, const float* xyz, const f
                                  const float* dL_drot, const float* dL_dopacity, const float* dL_dmeans3D, float* g_xyz,
                                  float* g_scaling, float* g_rotation, float* g_opacity, float* g_normal, float* g_base,
                                  float* g_rough, int He, int We, const float* env_raw, const float* env, float* dL_denv,
-                                 float w_tv, float* g_env_raw, float* tv_sum, int consume)
+                                 float w_tv, float* g_env_raw, float* tv_sum, int consume, float* records,
+                                 const GradRecordLayout* layout)
 {
+    ActivateRecords rec = {nullptr, 0, {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1}};
+    if (records != nullptr && layout != nullptr) {      // (the C-ABI wrapper checked: 16-float rows)
+        rec.rows = records;
+        rec.opacity = layout->opacity;
+        for (int c = 0; c < 12; c++) rec.col[c] = layout->feature[c];
+    }
     EnvBackward job;
     job.He = He; job.We = We; job.raw = env_raw; job.env = env; job.dL_denv = dL_denv; job.w_tv = w_tv; job.g_raw = g_env_raw;
     job.tv_sum = tv_sum; job.consume = consume;
@@ -475,8 +535,9 @@ void launch_s2_activate_backward(hipStream_t s, int P, const float* xyz, const f
     s2_activate_backward_kernel<<<nb_main + nb_env, 256, 0, s>>>(
         P, xyz, scaling_raw, rotation_raw, opacity_raw, normal_raw, base_raw, rough_raw, viewmatrix, campos,
         dL_dfeatures, dL_dbase_shade, dL_drough_shade, dL_dviewdirs, dL_dscales, dL_drot, dL_dopacity, dL_dmeans3D, g_xyz,
-        g_scaling, g_rotation, g_opacity, g_normal, g_base, g_rough, nb_main, job);
+        g_scaling, g_rotation, g_opacity, g_normal, g_base, g_rough, nb_main, job, rec);
     check_launch(s, false, "s2_activate_backward_kernel");
+    if (rec.rows != nullptr) gradient_records_zeroed(records);
 }
 
 void launch_s2_normals_srgb(hipStream_t s, int W, int H, const float* vm, float focal_x, float focal_y, float cx, float cy,

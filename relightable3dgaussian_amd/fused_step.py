@@ -159,6 +159,7 @@ class FusedStage2Step(FusedStepBase):
         self._early = self._b_early = self._a_late = False
         self._dp_chain = None                       # data parallel: the ray set whose chain kernel closes this iteration's bucket B
         self._env_c = self._d_env = None            # softplus(environment texture) (_front_end), its gradient accumulator
+        self._records = None                        # the tile backward's gradient records, while they are left in place
         self._adam_stream = self._geo_done = None   # the early-Adam stream, created at first use (_early_stream); the geometry backward's event
         # feature rows without a pack kernel: the activations write the columns they own, the fixed-ray-set shading kernels
         # theirs (r3dg_shade_frs_forward d_feature_rows) -- one launch and its join less between the shading integral and the
@@ -308,7 +309,7 @@ class FusedStage2Step(FusedStepBase):
 
     @_in_context
     def forward_backward(self, cam, bg, gt, early_adam=False, image_mask=None, split_geometry=None, chain_incidents=False,
-                         gt_depth=None, mvs_normal=None, sh_adam_in_backward=False):
+                         gt_depth=None, mvs_normal=None, sh_adam_in_backward=False, gradient_records=False):
         """One forward + loss + backward; gradients land in self.grads.  Returns the rasterizer's 10 public outputs.
         A bare call leaves EVERY entry of `grads` holding this view's gradient.  As part of a whole iteration (__call__) two
         entries do not: grads["shs"] and grads["incidents"] are then not written at all (see `sh_adam_in_backward` and
@@ -327,7 +328,11 @@ class FusedStage2Step(FusedStepBase):
         grads["incidents"] in the world frame, always.
         `sh_adam_in_backward` (whole iterations only, see __call__ and _fuses_sh_adam): the rasterizer's per-Gaussian geometry
         backward applies the SH colour group's Adam itself, from the gradient rows it holds on chip; there is no Adam launch for
-        the group and grads["shs"] is not written."""
+        the group and grads["shs"] is not written.
+        `gradient_records` (whole iterations only, see __call__ and _reads_gradient_records): the tile backward's per-Gaussian
+        gradient records are not scattered into arrays; the geometry backward, the gradient unpack and the activation chain rule
+        read their Gaussian's record row themselves, and the last of them zeroes it.  Same gradients, one launch and 71 MB (300k
+        Gaussians) less on the serial stretch behind the tile backward.  A bare call fills every array, as ever."""
         H, W = cam.image_height, cam.image_width
         if self._supervised and (gt_depth is None or (self.w["normal_mvs_depth"] != 0.0 and mvs_normal is None)):
             raise RuntimeError("FusedStage2Step: the depth / normal_mvs_depth terms need gt_depth%s" % (
@@ -345,7 +350,8 @@ class FusedStage2Step(FusedStepBase):
             g, active = self._image_loss(v, fw)
             fused_a = sh_adam_in_backward and self._fuses_sh_adam()
             dL_dfeatures, bw, geo_stream, handle_a = self._raster_backward(
-                v, fw, g, active, early_adam if split_geometry is None else split_geometry, fused_a)
+                v, fw, g, active, early_adam if split_geometry is None else split_geometry, fused_a,
+                gradient_records and self._reads_gradient_records())
             b_early = self._schedule_early(v, handle_a, geo_stream, use_bounded, early_adam, chain_incidents, fused_a)
             self._shade_backward(v, env_c, taps, packed, dL_dfeatures, bw, geo_stream, b_early, chain_incidents)
             self._remaining_buckets(handle_a)
@@ -537,12 +543,23 @@ class FusedStage2Step(FusedStepBase):
         return (not self.dp and bool(self._groups_a) and not self.frozen_geometry and can is not None
                 and os.environ.get("R3DG_SH_ADAM_IN_BACKWARD", "1") != "0" and can(self.M))
 
-    def _raster_backward(self, v, fw, g, active, split_geometry, fused_a=False):
+    def _reads_gradient_records(self):
+        """A whole iteration reads the tile backward's gradient records in place (r3dg_rasterize_backward_split_records; no
+        scatter pass)?  The geometry backward runs at all, the backward in use takes `gradient_records`, and
+        R3DG_GRADIENT_RECORDS is not 0 (the A/B switch: 0 restores the scatter pass).  Whether the call's kernel instance has
+        such records is the library's answer, call by call (_raster_backward)."""
+        return (not self.frozen_geometry and os.environ.get("R3DG_GRADIENT_RECORDS", "1") != "0"
+                and getattr(rasterizer_ops.rasterize_gaussians_backward, "gradient_records_supported", False))
+
+    def _raster_backward(self, v, fw, g, active, split_geometry, fused_a=False, records=False):
         """-> (dL_dfeatures, ALL outputs of the geometry backward or None with frozen geometry, the stream the geometry backward
         went to or None, the work handle of bucket A's all-reduce or None).  The caller holds every output until that stream is
         joined: the allocator would hand the memory of a dropped one to the next launch of the main stream.
-        `fused_a`: the geometry backward applies the SH group's Adam as the step _schedule_early is about to begin."""
+        `fused_a`: the geometry backward applies the SH group's Adam as the step _schedule_early is about to begin.
+        `records` (_reads_gradient_records): `_records` holds the gradient records for _shade_backward when the library left them
+        in place -- dL_dfeatures and the arrays only the scatter pass writes are then None -- and None otherwise."""
         cam, empty = v.cam, torch.Tensor([])
+        self._records = None
         R, radii, geom, binning, img = fw[0], fw[9], fw[10], fw[11], fw[12]
         geo_stream = None
         if self.frozen_geometry:
@@ -561,6 +578,9 @@ class FusedStage2Step(FusedStepBase):
             # (fused: the step count opt.begin_step() gives this iteration in _schedule_early, this iteration's own skip flag)
             fused = dict(sh_adam=self.opt.fused_step_of(self._groups_a[0], self.opt.step_count + 1, 1.0, self._skip_cur)) \
                 if fused_a else {}
+            rows = rasterizer_ops.GradientRecords() if records else None
+            if rows is not None:
+                fused["gradient_records"] = rows
             bw = rasterizer_ops.rasterize_gaussians_backward(
                 v.bg, self.xyz, self.features, radii, empty, self.a_scales, self.a_rot, 1.0, empty, v.vm,
                 # (no depth gradient: an EMPTY tensor = NULL = the caller's promise that the depth image carries no loss term)
@@ -568,6 +588,7 @@ class FusedStage2Step(FusedStepBase):
                 self.shs, 3, v.campos, geom, R, binning, img, True, False, dL_dsh_out=self.grads["shs"],
                 geometry_stream=geo_stream, active_features=sorted(active), zeroed_accumulators=self._acc, **fused)
             dL_dfeatures = bw[4]
+            self._records = rows if rows else None
             if geo_stream is not None:
                 if self._geo_done is None:
                     self._geo_done = torch.cuda.Event()
@@ -638,8 +659,12 @@ class FusedStage2Step(FusedStepBase):
         """Feature gradients -> shading backward -> activation chain rule: every gradient but the SH colour group's."""
         L = _lib.lib()
         P, gr = self.P, self.grads
-        _lib.check(L.r3dg_stage2_unpack_gradients(
-            v.raw, P, dL_dfeatures.data_ptr(), self.shade_out.data_ptr(), self.w["light"] / (3.0 * P),
+        rows = self._records
+        # (gradient records left in place: both readers of the [P,16] feature-gradient array read the record rows instead)
+        unpack, source = (L.r3dg_stage2_unpack_gradients, (dL_dfeatures.data_ptr(),)) if rows is None else \
+            (L.r3dg_stage2_unpack_gradients_records, (rows.ptr, rows.layout))
+        _lib.check(unpack(
+            v.raw, P, *source, self.shade_out.data_ptr(), self.w["light"] / (3.0 * P),
             self.d_pbr.data_ptr(), self.d_diffuse.data_ptr(), self._absmax.data_ptr(),
             # (the light-smoothness term's value, when no pack kernel added it)
             None if packed else self.sums[3].data_ptr()), "stage2_unpack_gradients")
@@ -689,6 +714,16 @@ class FusedStage2Step(FusedStepBase):
         # (frozen geometry: NULL for everything its half of the chain rule would read or write)
         geo = (lambda t: None) if self.frozen_geometry else (lambda t: t.data_ptr())
         _means2D, _dcol, dL_dopacity, dL_dmeans3D, _dfeat, _dcov, _dsh, dL_dscales, dL_drot = bw or (None,) * 9
+        if rows is not None:
+            # the last reader of the record rows (the unpack ran on this stream, the geometry backward is joined): it zeroes them
+            _lib.check(L.r3dg_stage2_activate_backward_with_records(v.raw, P, geo(self.xyz), geo(self.scaling), geo(self.rotation),
+                geo(self.opacity), geo(self.normal), self.base_color.data_ptr(), self.roughness.data_ptr(), geo(v.vm),
+                geo(v.campos), rows.ptr, rows.layout, d_base.data_ptr(), d_rough.data_ptr(), geo(d_view), geo(dL_dscales),
+                geo(dL_drot), geo(dL_dmeans3D), geo(gr["xyz"]), geo(gr["scaling"]), geo(gr["rotation"]), geo(gr["opacity"]),
+                geo(gr["normal"]), gr["base_color"].data_ptr(), gr["roughness"].data_ptr(), *env_job),
+                "stage2_activate_backward")
+            self._records = None
+            return
         _lib.check(L.r3dg_stage2_activate_backward_with(v.raw, P, geo(self.xyz), geo(self.scaling), geo(self.rotation),
             geo(self.opacity), geo(self.normal), self.base_color.data_ptr(), self.roughness.data_ptr(), geo(v.vm), geo(v.campos),
             dL_dfeatures.data_ptr(), d_base.data_ptr(), d_rough.data_ptr(), geo(d_view), geo(dL_dscales), geo(dL_drot),
@@ -851,6 +886,7 @@ class FusedStage2Step(FusedStepBase):
         # costs the latency-sensitive shading kernel nearly its whole duration (2M: 0.99 ms of Adam for +0.85 ms, 159 vs 163 it/s)
         early = os.environ.get("R3DG_EARLY_ADAM", "1" if self.P <= 1_000_000 else "0") != "0" and not self.serial_streams
         outs = self.forward_backward(cam, bg, gt, early_adam=early, image_mask=image_mask, chain_incidents=True,
-                                     gt_depth=gt_depth, mvs_normal=mvs_normal, sh_adam_in_backward=True)
+                                     gt_depth=gt_depth, mvs_normal=mvs_normal, sh_adam_in_backward=True,
+                                     gradient_records=True)
         self.optimizer_step()
         return outs

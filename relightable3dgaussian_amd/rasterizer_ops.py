@@ -10,7 +10,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _abi, _lib
 
 NUM_CHANNELS = 3
 
@@ -191,11 +191,33 @@ def rasterize_gaussians(background, means3D, features, colors, opacity, scales, 
                                      debug).finish()
 
 
+class GradientRecords:
+    """The tile backward's per-Gaussian gradient records, left in place (r3dg_rasterize_backward_split_records): `ptr` is the
+    first of P rows of 16 floats in the library's scratch of the stream the backward ran on, `layout` the
+    R3DG_GRAD_RECORD_LAYOUT_INTS ints that say which channel holds what.  Handed EMPTY to rasterize_gaussians_backward
+    (`gradient_records=`); it comes back filled -- true -- when the call's kernel instance has such rows, and then the caller
+    runs r3dg_stage2_unpack_gradients_records and r3dg_stage2_activate_backward_with_records on them (the second zeroes the
+    rows again), or r3dg_gradient_records_scatter.  Empty on return: the call was the classic one."""
+
+    def __init__(self):
+        self.ptr, self.layout, self.P, self.device = None, None, 0, None
+
+    def __bool__(self):
+        return self.ptr is not None
+
+    def tensor(self):
+        """The rows as a [P,16] float32 tensor that VIEWS the library's memory (tests, debugging)."""
+        view = type("_RecordRows", (), {"__cuda_array_interface__": {
+            "shape": (self.P, 16), "typestr": "<f4", "data": (int(self.ptr), False), "version": 2, "strides": None}})()
+        return torch.as_tensor(view, device=self.device)
+
+
 def rasterize_gaussians_backward(background, means3D, features, radii, colors, scales, rotations, scale_modifier,
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                  dL_dout_opacity, dL_dout_depth, dL_dout_feature, sh, degree, campos, geomBuffer, R,
                                  binningBuffer, imageBuffer, backward_geometry, debug, dL_dsh_out=None,
-                                 geometry_stream=None, active_features=None, zeroed_accumulators=None, sh_adam=None):
+                                 geometry_stream=None, active_features=None, zeroed_accumulators=None, sh_adam=None,
+                                 gradient_records=None):
     """`dL_dsh_out` (not in the reference signature): optional preallocated [P,M,3] buffer the SH gradient is written
     into (every element is written), e.g. a view of a flat gradient bucket.  `geometry_stream`: optional torch stream
     for the per-Gaussian geometry backward (dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations are then only
@@ -207,7 +229,12 @@ def rasterize_gaussians_backward(background, means3D, features, radii, colors, s
     `sh_adam` (FusedAdam.fused_step_of(group of `sh`, ...); r3dg_rasterize_backward_split_sh_adam): the per-Gaussian geometry
     backward applies the Adam step of the SH group itself -- `sh` and its two moment tensors are updated in place and the
     returned dL_dsh is NOT written (it keeps whatever it held).  Raises where the library has no such kernel
-    (sh_adam_supported)."""
+    (sh_adam_supported).
+    `gradient_records` (an empty GradientRecords; whole stage-2 iterations): where the call's kernel instance keeps 16-float
+    records -- up to 7 active feature channels without a depth gradient -- there is NO scatter pass: the geometry backward reads
+    the records in place, `gradient_records` comes back filled, and dL_dcolors, dL_dopacity and dL_dfeatures are returned as
+    None (dL_dmeans2D is written as ever).  The caller's kernels read the rest of the rows and zero them (GradientRecords).
+    Otherwise `gradient_records` stays empty and the call is the classic one."""
     L = _lib.lib()
     P = means3D.size(0)
     S = features.size(1)
@@ -268,6 +295,25 @@ def rasterize_gaussians_backward(background, means3D, features, radii, colors, s
                 entry, tail = L.r3dg_rasterize_backward_split_sh_adam, sh_adam
             else:
                 entry, tail = L.r3dg_rasterize_backward_split, ()
+            st = None
+            if gradient_records is not None:
+                rows, supported = C.c_void_p(), C.c_int(0)
+                layout = (C.c_int * _abi.constants["R3DG_GRAD_RECORD_LAYOUT_INTS"])()
+                st = L.r3dg_rasterize_backward_split_records(
+                    cur, gs, P, S, int(degree), M, int(R), _lib.ptr(bg_), W, H, _lib.ptr(means_),
+                    _lib.ptr(sh_), _lib.ptr(feat_), _lib.ptr(col_), _lib.ptr(sc_), float(scale_modifier), _lib.ptr(rot_),
+                    _lib.ptr(cov_), _lib.ptr(vm_), _lib.ptr(pm_), _lib.ptr(cam_), float(tan_fovx), float(tan_fovy),
+                    radii_.data_ptr(), _lib.ptr(geomBuffer), _lib.ptr(binningBuffer), _lib.ptr(imageBuffer), _lib.ptr(gC),
+                    _lib.ptr(gO), _lib.ptr(gD), _lib.ptr(gF), dL_dmeans2D.data_ptr(), dL_dmeans3D.data_ptr(),
+                    dL_dcov3D.data_ptr(), _lib.ptr(dL_dsh), dL_dscales.data_ptr(), dL_drotations.data_ptr(),
+                    int(bool(backward_geometry)), int(bool(debug)), n_act, act,
+                    *(sh_adam if sh_adam is not None else (None, 0.0, 0.0, 0.0, 1, 1.0, None)),
+                    C.byref(rows), layout, C.byref(supported))
+                _lib.check(st, "rasterize_gaussians_backward")
+                if supported.value:
+                    gradient_records.ptr, gradient_records.layout = rows.value, layout
+                    gradient_records.P, gradient_records.device = P, dev
+                    return (dL_dmeans2D, None, None, dL_dmeans3D, None, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
             st = entry(
                 cur, gs, P, S, int(degree), M, int(R), _lib.ptr(bg_), W, H, _lib.ptr(means_),
                 _lib.ptr(sh_), _lib.ptr(feat_), _lib.ptr(col_), _lib.ptr(sc_), float(scale_modifier), _lib.ptr(rot_),
@@ -291,6 +337,8 @@ def _sh_adam_supported(M):
 # (asked of the FUNCTION, so that whatever stands in its place -- a wrapper, a recorder -- answers for itself; one without the
 # attribute takes no `sh_adam`)
 rasterize_gaussians_backward.sh_adam_supported = _sh_adam_supported
+# (likewise: the function takes `gradient_records`; a stand-in without the attribute is never handed one)
+rasterize_gaussians_backward.gradient_records_supported = True
 
 
 def _image_tail_supported(W, H):
