@@ -935,6 +935,41 @@ int r3dg_training_sheet(void* stream, int width, int height, int layout, const f
                         const float* d_pseudo_normal, const float* d_background, const float* d_env, int env_rows,
                         int out_width, int out_height, uint8_t* d_bytes);
 
+/* r3dg_png_encode: the zlib stream of the PNG file of d_bytes [H,W,C] uint8 (8 bits deep, colour type 0 / 4 / 2 / 6 for C = 1 / 2 /
+ *   3 / 4, no interlace) -- the scanline filter, the deflate stream and the Adler-32 -- in three launches.  The host is left with the
+ *   chunk framing and its CRC-32 (png_device.wrap).  The stream is cut so that a row segment is an independent unit of work:
+ *   FILTER, per row, bpp = C: None, Sub, Up, Average (floor((a + b) / 2)), Paeth (standard predictor, tie order a, b, c); row 0
+ *     sees a zero row above; the score of a candidate is sum |int8(byte)| over the row, the lowest wins, a tie goes to the lowest
+ *     type.  The filtered stream is H rows of row_bytes = 1 + W * C bytes: the type, then the row.  The filter reads the pixel row
+ *     above also across a segment boundary.
+ *   SEGMENTS: rows_per_segment = max(1, min(H, 16384 / row_bytes)) rows; the last one may be shorter; at most 65535 raw bytes.
+ *   PARSE: the segment's bytes, type bytes included, in maximal runs of equal bytes.  A run of n emits one literal, then rest =
+ *     n - 1: while rest >= 261 or rest == 258 a match (258, distance 1); then rest of 259 / 260: a match of rest - 3 and one of 3;
+ *     rest >= 3: a match of rest; else `rest` literals.  Distance 1 is the only distance.
+ *   CODE: one dynamic-Huffman table for all segments, handed over as data.  d_code_table uint32[286]: bits 0..15 the canonical
+ *     code of a literal/length symbol, bit-reversed for LSB-first packing, bits 16..20 its length (1..15).  d_block_header: the
+ *     constant bits of a non-final BTYPE = 10 block header (BFINAL = 0, BTYPE, HLIT = 29, HDIST = 0, HCLEN, the code-length code,
+ *     the 286 + 1 lengths), header_bits of them, LSB-first in ceil(header_bits / 8) bytes.  The one distance code has length 1 and
+ *     code 0: a match is its length code, the extra bits, one 0 bit.  The caller vouches for the table (png_device.CodeTable.
+ *     validate: lengths in 1..15, Kraft sum 1, a complete code-length code); the kernel reads it as it is.
+ *   A CODED SEGMENT: the block header, the tokens, symbol 256, then an empty stored block (bits 000, zero bits to the byte
+ *     boundary, 00 00 FF FF).  When that exceeds raw + 5 bytes the segment is ONE stored block instead: 00, LEN, ~LEN, the raw
+ *     bytes.  The choice is made from the scanned bit total before anything is written.
+ *   STREAM: 78 01, the segments, 03 00 (a final empty fixed block), Adler-32 of the filtered stream, big-endian; so
+ *     *d_zlib_bytes <= 2 + sum(raw_seg + 5) + 6 = r3dg_png_zlib_bound.
+ *   d_scratch: r3dg_png_scratch_bytes bytes at least, 16-byte aligned (a fixed slot per segment, its byte count and Adler pair
+ *   (sum b, sum (n - i) b) mod 65521, the stream offsets); d_zlib: zlib_capacity >= the bound, any alignment, only the first
+ *   *d_zlib_bytes bytes are written; d_bytes any alignment (byte loads); d_code_table and d_zlib_bytes 4-byte aligned.
+ *   No global atomics, nothing synchronises, nothing outside the arrays is touched.  Rejected, with nothing enqueued: channels
+ *   outside 1..4, row_bytes > 65535, header_bits outside 17..2048, a capacity or scratch below its size, a misaligned scratch, a
+ *   NULL pointer, 2^31 pixels and more, a bound of 2^31 bytes and more (the length word is an int32).  The two size queries
+ *   return R3DG_EINVAL (negative) for a shape the encoder rejects. */
+long long r3dg_png_zlib_bound(int width, int height, int channels);
+long long r3dg_png_scratch_bytes(int width, int height, int channels);
+int r3dg_png_encode(void* stream, int width, int height, int channels, const uint8_t* d_bytes, const uint32_t* d_code_table,
+                    const uint8_t* d_block_header, int header_bits, uint8_t* d_scratch, long long scratch_bytes,
+                    uint8_t* d_zlib, long long zlib_capacity, int32_t* d_zlib_bytes);
+
 /* r3dg_view_unpack: one ground-truth view of the device view store, d_pixels [H,W,C] uint8 as the image file holds them (C = 4:
  *   RGBA, C = 3: RGB) -> d_image [3,H,W] float composited onto d_background (3 floats on the device) and d_mask [1,H,W] float (the
  *   alpha channel; ones for C = 3; NULL: not wanted), bit for bit what the reference's reader makes of the file

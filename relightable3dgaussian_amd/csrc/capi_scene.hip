@@ -112,6 +112,48 @@ int r3dg_training_sheet(void* stream_, int width, int height, int layout, const 
     });
 }
 
+static const char* png_shape_error(int width, int height, int channels)
+{
+    if (channels < 1 || channels > 4) return "png: 1..4 channels";
+    if (width < 1 || height < 1) return "png: bad shape";
+    if ((long long)width * channels + 1 > 65535) return "png: a filtered row (width * channels + 1 bytes) must fit 65535 bytes";
+    if ((long long)width * height >= (1ll << 31)) return "png: image too large";
+    return nullptr;
+}
+
+long long r3dg_png_zlib_bound(int width, int height, int channels)
+{
+    if (const char* e = png_shape_error(width, height, channels)) return invalid(e);
+    return png_zlib_bound(width, height, channels);
+}
+
+long long r3dg_png_scratch_bytes(int width, int height, int channels)
+{
+    if (const char* e = png_shape_error(width, height, channels)) return invalid(e);
+    return png_scratch_bytes(width, height, channels);
+}
+
+int r3dg_png_encode(void* stream_, int width, int height, int channels, const uint8_t* bytes, const uint32_t* code_table,
+                    const uint8_t* block_header, int header_bits, uint8_t* scratch, long long scratch_bytes, uint8_t* zlib,
+                    long long zlib_capacity, int32_t* zlib_bytes)
+{
+    if (const char* e = png_shape_error(width, height, channels)) return invalid(e);
+    if (header_bits < 17 || header_bits > 2048) return invalid("png_encode: a block header has 17..2048 bits");
+    if (!bytes || !code_table || !block_header || !scratch || !zlib || !zlib_bytes) return invalid("png_encode: null buffer");
+    const long long bound = png_zlib_bound(width, height, channels);
+    if (bound >= (1ll << 31)) return invalid("png_encode: a stream bound of 2^31 bytes and more");
+    if (zlib_capacity < bound) return invalid("png_encode: the stream buffer is smaller than r3dg_png_zlib_bound");
+    if (scratch_bytes < png_scratch_bytes(width, height, channels))
+        return invalid("png_encode: the scratch is smaller than r3dg_png_scratch_bytes");
+    if (((size_t)scratch & 15) || ((size_t)code_table & 3) || ((size_t)zlib_bytes & 3))
+        return invalid("png_encode: the scratch must be 16-byte aligned, the code table and the length word 4-byte aligned");
+    return guarded([&]() -> int {
+        launch_png_encode((hipStream_t)stream_, width, height, channels, bytes, code_table, block_header, header_bits, scratch, zlib,
+                          zlib_bytes);
+        return R3DG_OK;
+    });
+}
+
 int r3dg_view_unpack(void* stream_, int width, int height, int channels, const uint8_t* pixels, const float* background,
                      float* image, float* mask)
 {

@@ -307,6 +307,12 @@ void launch_relight_quantize(hipStream_t s, int W, int H, int C, const float* im
 void launch_training_sheet(hipStream_t s, int W, int H, int layout, const float* render, const float* gt, const float* opacity,
                            const int* n_contrib, const float* feature, const float* pseudo_normal, const float* background,
                            const float* env, int env_rows, int out_w, int out_h, uint8_t* bytes);
+// png_encode.hip: the zlib stream of the PNG file of bytes [H,W,C] (filter, table-driven deflate per row segment, Adler-32) in three
+// launches; scratch of png_scratch_bytes, 16-byte aligned; zlib of png_zlib_bound bytes at least; the shape is checked by the caller
+long long png_zlib_bound(int W, int H, int C);
+long long png_scratch_bytes(int W, int H, int C);
+void launch_png_encode(hipStream_t s, int W, int H, int C, const uint8_t* bytes, const uint32_t* code_table,
+                       const uint8_t* block_header, int header_bits, uint8_t* scratch, uint8_t* zlib, int32_t* zlib_bytes);
 // view_store.hip: 8-bit pixels [H,W,C] of a stored ground-truth view -> image [3,H,W] over the background + mask [1,H,W] (or NULL)
 void launch_view_unpack(hipStream_t s, int W, int H, int C, const uint8_t* pixels, const float* background, float* image,
                         float* mask);

@@ -113,7 +113,7 @@ class FusedStage2Step(FusedStepBase):
         self.a_base, self.a_rough = torch.empty(P, 3, **f), torch.empty(P, 1, **f)
         self.a_viewdirs = torch.empty(P, 3, **f)
         self.shade_out = torch.empty(P, shading_ops.NOUT, **f)
-        self.features = torch.empty(P, 16, **f)
+        self.features = torch.zeros(P, 16, **f)     # (zero-filled once: the pack kernels write the active channels only)
         # unweighted sums: l1, pbr l1, normal mse, light l1, TV(env), SSIM(image), SSIM(pbr), and the three edge-aware
         # smoothness sums (base colour, roughness, diffuse light)
         # (+ with an MVS term on: the depth L1 sum over the selected pixels, the squared MVS-normal difference sum)

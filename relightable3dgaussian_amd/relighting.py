@@ -8,11 +8,12 @@ visibility once (RelightRenderer(device_visibility=True); with --bake: visibilit
 RelightRenderer(baked_visibility=True)), walks the trajectory with the cameras of relighting.py:159-165 and each frame's light
 transform, and writes OUTPUT/<capture>/frame_<idx>.png with the background rules of relighting.py:172-181.  Frames are quantised on
 the device (r3dg_relight_quantize, the rounding of torchvision's save_image), copied asynchronously into a ring of pinned host
-buffers and encoded by PIL on worker threads while the next frame renders.  `render_trajectory` is the same loop as a generator
+buffers and encoded by PIL on worker threads while the next frame renders; with --device_png the encoder runs on the device too
+(png_device.py) and the workers only frame and write the files.  `render_trajectory` is the same loop as a generator
 of device frames, for callers that want no files.
 
 Arguments are those of relighting.py:88-101 plus --rotate-sh (compose.assemble), --fovx (the reference hard-codes
-0.6911112070083618), --envmap_scale and --bake_iterations.  --video is not offered (there is no cv2 here) and the `points`
+0.6911112070083618), --envmap_scale, --bake_iterations and --device_png.  --video is not offered (there is no cv2 here) and the `points`
 capture raises.
 
 Environment maps: `.npy` ([He,We,3] linear radiance) and Radiance `.hdr` (RGBE, flat or run-length encoded scanlines) are read
@@ -140,9 +141,15 @@ class FrameWriter:
     starts the asynchronous copy into the slot's pinned host buffer and hands the encoding (PIL) to a pool of at most 8 worker
     threads.  submit blocks only when every slot is still being encoded; `close` waits for the files and raises what a worker
     raised.  `submit_bytes(bytes [H,W,C] uint8, path)` takes a picture that is 8-bit already (training_vis) through the same ring,
-    copy, event and workers without the quantise launch."""
+    copy, event and workers without the quantise launch.
 
-    def __init__(self, workers=None, slots=None):
+    `device_png=True` (opt-in) moves the encoder onto the device: submit quantises and encodes (png_device.encode: filter, deflate
+    and Adler-32 in three launches), the slot's pinned buffer has the size of the stream's bound plus the length word, and the
+    worker reads the length, frames the stream as a PNG file (png_device.wrap: one CRC-32) and writes it; PIL is not used.  The
+    ring, the back-pressure, close() and the raising of a worker's error are the same."""
+
+    def __init__(self, workers=None, slots=None, device_png=False):
+        self.device_png = bool(device_png)
         self.workers = max(1, min(8, workers or (os.cpu_count() or 1)))
         self.pool = ThreadPoolExecutor(max_workers=self.workers)
         self.free = queue.Queue()
@@ -151,6 +158,8 @@ class FrameWriter:
         self.jobs = []
 
     def submit(self, image, path):
+        if self.device_png:
+            return self._submit_device(image, None, path)
         C, H, W = image.shape
         slot = self.free.get()
         if slot.dev is None or tuple(slot.dev.shape) != (H, W, C) or slot.dev.device != image.device:
@@ -169,6 +178,8 @@ class FrameWriter:
         if not isinstance(bytes_dev, torch.Tensor) or not bytes_dev.is_cuda or bytes_dev.dtype != torch.uint8 or \
                 bytes_dev.dim() != 3 or not 1 <= bytes_dev.shape[2] <= 4 or not bytes_dev.is_contiguous():
             raise RuntimeError("submit_bytes: the picture must be a contiguous uint8 [H,W,C] with 1 <= C <= 4 on the device")
+        if self.device_png:
+            return self._submit_device(None, bytes_dev, path)
         slot = self.free.get()
         if slot.host is None or tuple(slot.host.shape) != tuple(bytes_dev.shape):
             slot.dev = None                  # (a slot that changes size drops the device half `submit` would have to match)
@@ -184,6 +195,47 @@ class FrameWriter:
             done.synchronize()
             arr = slot.host.numpy()
             Image.fromarray(arr[..., 0] if arr.shape[-1] == 1 else arr).save(path)
+        finally:
+            self.free.put(slot)
+
+    def _submit_device(self, image, bytes_dev, path):
+        """The device encoder's half of submit (an image [C,H,W] to quantise first) and submit_bytes (a picture [H,W,C])."""
+        from . import png_device
+        if bytes_dev is None:
+            C, H, W = image.shape
+            dev = image.device
+        else:
+            H, W, C = bytes_dev.shape
+            dev = bytes_dev.device
+        slot = self.free.get()
+        try:
+            if getattr(slot, "shape", None) != (H, W, C) or slot.stream.device != dev:
+                n = 4 + png_device.zlib_bound(W, H, C)                  # the length word, then the stream
+                slot.stream = torch.empty(n, dtype=torch.uint8, device=dev)
+                slot.host = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+                slot.dev = torch.empty(H, W, C, dtype=torch.uint8, device=dev)
+                slot.shape = (H, W, C)
+            if bytes_dev is None:
+                bytes_dev = quantize(image, slot.dev)
+            png_device.encode(bytes_dev, out=(slot.stream[4:], slot.stream[:4].view(torch.int32)))
+            slot.host.copy_(slot.stream, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+        except BaseException:
+            self.free.put(slot)
+            raise
+        self.jobs.append(self.pool.submit(self._write, slot, done, path))
+
+    def _write(self, slot, done, path):
+        from . import png_device
+        try:
+            done.synchronize()
+            host = slot.host.numpy()
+            n = int(host[:4].view(np.int32)[0])
+            H, W, C = slot.shape
+            data = png_device.wrap(host[4:4 + n].tobytes(), W, H, C)
+            with open(path, "wb") as fh:
+                fh.write(data)
         finally:
             self.free.put(slot)
 
@@ -252,6 +304,8 @@ def build_parser():
     p.add_argument("--envmap_scale", type=float, default=1.0)
     p.add_argument("--bake_iterations", type=int, default=1000)
     p.add_argument("--device", default="cuda")
+    p.add_argument("--device_png", action="store_true",
+                   help="encode the PNG files on the device (filter, deflate, Adler-32) instead of on PIL worker threads")
     return p
 
 
@@ -274,7 +328,7 @@ def main(argv=None):
     lights = None if cfg.light_transforms is None else [cfg.light_transforms[idx] for idx in keys]
     for c in captures:
         os.makedirs(os.path.join(args.output, c), exist_ok=True)
-    writer = FrameWriter()
+    writer = FrameWriter(device_png=True) if args.device_png else FrameWriter()
     try:
         for i, frames in render_trajectory(composite, envmap, cameras, lights, captures, sample_num=args.sample_num, bg=bg,
                                            bake=args.bake, bake_iterations=args.bake_iterations):

@@ -308,8 +308,10 @@ class FixedRaySet:
                                                  self.valid.data_ptr()), "shade_frs_classify")
         self.invalid_list = torch.nonzero(self.valid[:self.P] == 0).to(torch.int32).reshape(-1).contiguous()
         self.n_invalid = int(self.invalid_list.numel())                   # (one read-back per visibility update)
-        self.cprime = torch.empty(self.P, 48, dtype=torch.float32, device=dev)
-        self.dcprime = torch.empty(self.P, 48, dtype=torch.float32, device=dev)
+        # (zero-filled once: the rows of the Gaussians off the rotated path are written by no rotation kernel, and a recycled
+        # allocation would hand whoever reads a whole array another tensor's old values)
+        self.cprime = torch.zeros(self.P, 48, dtype=torch.float32, device=dev)
+        self.dcprime = torch.zeros(self.P, 48, dtype=torch.float32, device=dev)
         self._taps, self._taps_size = None, None
 
     @staticmethod

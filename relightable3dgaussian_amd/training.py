@@ -115,6 +115,8 @@ def build_parser():
     p.add_argument("--save_training_vis", action="store_true",
                    help="write the contact sheet OUT/visualize/<iteration>.png of the iteration's view (training_vis)")
     p.add_argument("--save_training_vis_iteration", type=int, default=1000, help="... every N iterations, and at the first")
+    p.add_argument("--device_png", action="store_true",
+                   help="encode the contact sheets on the device (png_device) instead of on a PIL worker thread")
     p.add_argument("--device", default="cuda")
     for name, value in sorted(vars(train_loop.Schedule()).items()):              # learning rates, light_init, densification
         if name not in _NOT_SCHEDULE and not name.startswith("lambda_"):
@@ -273,6 +275,8 @@ def train(args):
         if vis.sheet is None:
             from . import training_vis
             vis.sheet = training_vis.TrainingSheet(step, args.sample_num if stage2 else None)
+            if args.device_png:
+                vis.sheet.device_png = True
         v = seen[-1]
         path = os.path.join(args.model_path, "visualize", "%06d.png" % g)
         vis.sheet.save(cameras[v], store._pair(v, background, fresh=False)[0], background, path)

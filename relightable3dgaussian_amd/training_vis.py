@@ -81,6 +81,7 @@ class TrainingSheet:
             raise RuntimeError("TrainingSheet: the sheet shades with the step's own visibility, traced at %d samples per Gaussian; "
                                "sample_num = %d is another ray set" % (step.K, sample_num))
         self.writer = None
+        self.device_png = False               # True: the writer encodes on the device (relighting.FrameWriter(device_png=True))
         self._bytes = {}                      # (out_h, out_w) -> the device sheet
         self._buffers = None                  # stage 2: P and the activation / shading / feature-row buffers of that P
         self._dirs = None                     # stage 2: (snapshot normals, refresh count, directions) of a step that holds none
@@ -166,7 +167,7 @@ class TrainingSheet:
         """The sheet as a PNG at `path`, encoded off the training thread (close() waits for the files and raises their errors)."""
         if self.writer is None:
             from .relighting import FrameWriter
-            self.writer = FrameWriter(workers=2)
+            self.writer = FrameWriter(workers=2, device_png=True) if self.device_png else FrameWriter(workers=2)
         self.writer.submit_bytes(self.sheet(cam, gt, background), path)
 
     def close(self):
