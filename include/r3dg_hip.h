@@ -84,23 +84,43 @@ int r3dg_rasterize_forward(void* stream, r3dg_alloc_fn geometry_alloc, r3dg_allo
                            float* d_out_surface_xyz, float* d_out_weights, int32_t* d_radii, int debug,
                            int* num_rendered_out);
 
-/* The forward in two halves.  _begin takes the arguments of r3dg_rasterize_forward, runs the projection and starts the
+/* ---- a rasterizer call described by structs ------------------------------------------------------------------------------------
+ * r3dg_rasterize_forward_begin[_bounded] and r3dg_rasterize_backward_split take what the two positional entries (whose lists mirror
+ * the reference's) spell out as three plain structs of int, float and pointer fields; the field names are those parameters' names.
+ * The library copies a struct before the entry point returns, so a caller's struct may be a temporary (what its pointers name must
+ * outlive the kernels, as ever).
+ *
+ * r3dg_raster_scene: what the forward and the backward of a frame both read -- P Gaussians, S feature channels, SH degree D with M
+ * coefficients, the image size, the inputs and the camera.  Optional inputs are NULL when absent, as in r3dg_rasterize_forward.
+ * d_opacities, cx and cy are read by the FORWARD only (the backward takes opacities from the geometry state and never needs the
+ * principal point).  d_campos is the camera position under the backward's name for it (r3dg_rasterize_forward: d_cam_pos). */
+typedef struct r3dg_raster_scene {
+    int P, S, D, M, width, height;
+    const float* d_background; const float* d_means3D; const float* d_shs; const float* d_colors_precomp; const float* d_features;
+    const float* d_opacities; const float* d_scales;
+    float scale_modifier;
+    const float* d_rotations; const float* d_cov3D_precomp;
+    const float* d_viewmatrix; const float* d_projmatrix; const float* d_campos;
+    float tan_fovx, tan_fovy, cx, cy;
+} r3dg_raster_scene;
+/* r3dg_raster_outputs: the forward's own arguments, with r3dg_rasterize_forward's rules (d_out_weights zero-filled by the caller or
+ * NULL, d_radii may be NULL, everything else fully written). */
+typedef struct r3dg_raster_outputs {
+    int prefiltered, compute_pseudo_normal, debug;
+    float* d_out_color; float* d_out_opacity; float* d_out_depth; float* d_out_feature; float* d_out_normal;
+    float* d_out_surface_xyz; float* d_out_weights;
+    int32_t* d_radii;
+} r3dg_raster_outputs;
+
+/* The forward in two halves.  _begin takes the arguments of r3dg_rasterize_forward as structs, runs the projection and starts the
  * asynchronous read-back of num_rendered (an event is recorded on `stream`); _finish waits for that event only, sizes the
  * binning state, orders the instances and renders.  Kernels the caller enqueues on `stream` between the two calls run
  * while the host waits for the count -- `d_features` (and every other pointer) is only dereferenced by the device, so the
  * feature rows may be produced in between.  *ticket is NULL when P == 0; _finish(NULL) is a no-op.  Every ticket must be
  * finished exactly once.  r3dg_rasterize_forward == _begin immediately followed by _finish. */
 int r3dg_rasterize_forward_begin(void* stream, r3dg_alloc_fn geometry_alloc, r3dg_alloc_fn binning_alloc,
-                                 r3dg_alloc_fn image_alloc, void* alloc_user, int P, int S, int D, int M,
-                                 const float* d_background, int width, int height, const float* d_means3D,
-                                 const float* d_shs, const float* d_colors_precomp, const float* d_features,
-                                 const float* d_opacities, const float* d_scales, float scale_modifier,
-                                 const float* d_rotations, const float* d_cov3D_precomp, const float* d_viewmatrix,
-                                 const float* d_projmatrix, const float* d_cam_pos, float tan_fovx, float tan_fovy,
-                                 float cx, float cy, int prefiltered, int compute_pseudo_normal, float* d_out_color,
-                                 float* d_out_opacity, float* d_out_depth, float* d_out_feature, float* d_out_normal,
-                                 float* d_out_surface_xyz, float* d_out_weights, int32_t* d_radii, int debug,
-                                 void** ticket);
+                                 r3dg_alloc_fn image_alloc, void* alloc_user, const r3dg_raster_scene* scene,
+                                 const r3dg_raster_outputs* outputs, void** ticket);
 int r3dg_rasterize_forward_finish(void* ticket, int* num_rendered_out);
 /* _finish with the instance ordering (key duplication, sort, tile ranges) on `ordering_stream` (NULL = the forward's
  * stream): it waits for the projection only and is joined before the tile kernel, so it can run concurrently with
@@ -124,18 +144,9 @@ int r3dg_rasterize_forward_finish_on(void* ticket, void* ordering_stream, int* n
  * -- callers take the two-phase forward otherwise (_begin_bounded returns R3DG_EINVAL from _finish_bounded if asked anyway). */
 int r3dg_bounded_forward_supported(int width, int height);
 int r3dg_rasterize_forward_begin_bounded(void* stream, r3dg_alloc_fn geometry_alloc, r3dg_alloc_fn binning_alloc,
-                                         r3dg_alloc_fn image_alloc, void* alloc_user, int P, int S, int D, int M,
-                                         const float* d_background, int width, int height, const float* d_means3D,
-                                         const float* d_shs, const float* d_colors_precomp, const float* d_features,
-                                         const float* d_opacities, const float* d_scales, float scale_modifier,
-                                         const float* d_rotations, const float* d_cov3D_precomp,
-                                         const float* d_viewmatrix, const float* d_projmatrix, const float* d_cam_pos,
-                                         float tan_fovx, float tan_fovy, float cx, float cy, int prefiltered,
-                                         int compute_pseudo_normal, float* d_out_color, float* d_out_opacity,
-                                         float* d_out_depth, float* d_out_feature, float* d_out_normal,
-                                         float* d_out_surface_xyz, float* d_out_weights, int32_t* d_radii, int debug,
-                                         void* ordering_stream, long long capacity, float* d_overflow_flag,
-                                         unsigned int* d_overflow_count, void** ticket);
+                                         r3dg_alloc_fn image_alloc, void* alloc_user, const r3dg_raster_scene* scene,
+                                         const r3dg_raster_outputs* outputs, void* ordering_stream, long long capacity,
+                                         float* d_overflow_flag, unsigned int* d_overflow_count, void** ticket);
 int r3dg_rasterize_forward_finish_bounded(void* ticket, void* main_stream);
 
 /* Backward.  d_dL_dpix_d == NULL: the depth image carries no gradient (the caller's promise; the tile kernel then takes its
@@ -158,36 +169,22 @@ int r3dg_rasterize_backward(void* stream, int P, int S, int D, int M, int R, con
                             float* d_dL_dmean3D, float* d_dL_dcov3D, float* d_dL_dsh, float* d_dL_dscale,
                             float* d_dL_drot, int backward_geometry, int debug);
 
-/* Same as r3dg_rasterize_backward, but the per-Gaussian geometry backward (K12+K13) is launched on `geometry_stream`, ordered
- * after the tile kernel by an event, so work that only needs the tile pass's FINAL outputs can follow on `stream` concurrently.
- * geometry_stream == stream is exactly r3dg_rasterize_backward.
- *   final on `stream` (behind the tile kernel + its scatter pass):  d_dL_dfeature, d_dL_dopacity, d_dL_dcolor;
- *   valid ONLY AFTER JOINING geometry_stream:  d_dL_dmean3D, d_dL_dcov3D, d_dL_dsh, d_dL_dscale, d_dL_drot -- AND d_dL_dmean2D
- *     and d_dL_dconic: since round 5 the tile pass leaves RAW MOMENTS in those two (S_x, S_y / the second moments) and the
- *     per-Gaussian geometry kernel turns them into the viewspace gradient IN PLACE (rasterizer_preprocess_bwd.hip).  A consumer on
- *     `stream` that has not joined (e.g. densification statistics reading dL_dmeans2D) would read raw moments or race with that
- *     rewrite.  r3dg_stream_wait_stream(stream, geometry_stream) is the join.
- * active_features (HOST array of n_active_features distinct channel indices, or n_active_features < 0 for "all"): the
- * caller's promise that every OTHER channel of d_dL_dpix_f is zero everywhere; those channels are then not carried
- * through the tile kernel at all and the scatter pass WRITES ZEROS into their d_dL_dfeature columns (every output is fully
- * written: no zero fill by the caller is needed or relied upon).  Same results, less work: a loss normally reads a few of
- * the S feature maps.
- * Scratch: the tile pass adds into one gradient record per Gaussian, P x (16 or, with all S = 16 channels live, 32) floats of
- * LIBRARY scratch per (device, stream) that ever ran a backward -- 64 / 128 bytes per Gaussian (2M Gaussians: 128 / 256 MB),
- * grown geometrically and kept until r3dg_release_scratch(). */
-int r3dg_rasterize_backward_split(void* stream, void* geometry_stream, int P, int S, int D, int M, int R,
-                                  const float* d_background, int width, int height, const float* d_means3D,
-                                  const float* d_shs, const float* d_features, const float* d_colors_precomp,
-                                  const float* d_scales, float scale_modifier, const float* d_rotations,
-                                  const float* d_cov3D_precomp, const float* d_viewmatrix, const float* d_projmatrix,
-                                  const float* d_campos, float tan_fovx, float tan_fovy, const int32_t* d_radii,
-                                  const void* d_geom_buffer, const void* d_binning_buffer, const void* d_img_buffer,
-                                  const float* d_dL_dpix, const float* d_dL_dpix_o, const float* d_dL_dpix_d,
-                                  const float* d_dL_dpix_f, float* d_dL_dmean2D, float* d_dL_dconic,
-                                  float* d_dL_dopacity, float* d_dL_dcolor, float* d_dL_dfeature, float* d_dL_dmean3D,
-                                  float* d_dL_dcov3D, float* d_dL_dsh, float* d_dL_dscale, float* d_dL_drot,
-                                  int backward_geometry, int debug, int n_active_features,
-                                  const int* active_features);
+/* r3dg_raster_backward: the backward's own arguments (r3dg_rasterize_backward_split, declared behind r3dg_adam_group below) -- R,
+ * d_radii, the three state buffers and the four upstream gradients of r3dg_rasterize_backward, its ten outputs, and
+ * active_features: a HOST array of n_active_features distinct channel indices (n_active_features < 0: all S), the caller's promise
+ * that every OTHER channel of d_dL_dpix_f is zero everywhere; those channels are then not carried through the tile kernel at all
+ * and the scatter pass WRITES ZEROS into their d_dL_dfeature columns (every output is fully written: no zero fill by the caller is
+ * needed or relied upon).  Same results, less work: a loss normally reads a few of the S feature maps. */
+typedef struct r3dg_raster_backward {
+    int R;
+    const int32_t* d_radii;
+    const void* d_geom_buffer; const void* d_binning_buffer; const void* d_img_buffer;
+    const float* d_dL_dpix; const float* d_dL_dpix_o; const float* d_dL_dpix_d; const float* d_dL_dpix_f;
+    float* d_dL_dmean2D; float* d_dL_dconic; float* d_dL_dopacity; float* d_dL_dcolor; float* d_dL_dfeature;
+    float* d_dL_dmean3D; float* d_dL_dcov3D; float* d_dL_dsh; float* d_dL_dscale; float* d_dL_drot;
+    int backward_geometry, debug, n_active_features;
+    const int* active_features;
+} r3dg_raster_backward;
 
 /* The backward for FROZEN GEOMETRY: only d_dL_dfeature [P,S] (ACCUMULATED with atomics: zero it first) from d_dL_dpix_f
  * [S,H,W].  The stage-2 schedules of script/run_syn4.sh:27-33 and run_dtu.sh set the learning rates of positions, normals, SH
@@ -719,78 +716,67 @@ typedef struct r3dg_adam_group {
 int r3dg_adam_step(void* stream, int n_groups, const r3dg_adam_group* groups, float beta1, float beta2, float eps,
                    int step, float grad_scale, const float* d_skip_flag);
 
-/* r3dg_rasterize_backward_split whose per-Gaussian geometry backward applies the Adam step of the SH colour group ITSELF
- * (whole single-GPU training iterations): `sh_adam` describes the group -- param == d_shs ([P,M,3], n = 3 M P), both moments,
- * lr / lr_tail / period / split as for r3dg_adam_step; its `grad` is not read -- and step, betas, eps, grad_scale and
- * d_skip_flag mean what they mean there.  The gradient rows, which that kernel holds in on-chip memory, are consumed where they
- * are: d_dL_dsh is NOT written (it may be NULL) and no r3dg_adam_step launch reads it and the parameter row again -- per Gaussian
- * 3 x 12 M bytes less through device memory and one launch less.  Parameters and moments come out bit for bit as from
- * r3dg_rasterize_backward_split followed by r3dg_adam_step on the one group (the same update statements, compiled with the
- * same flags); Gaussians outside the view take part with a zero gradient, as there; every other output is what
- * r3dg_rasterize_backward_split writes, also when *d_skip_flag != 0 (then parameters and moments are left untouched).  d_shs
- * and the moments are final only after joining geometry_stream.  Needs SH input (d_colors_precomp == NULL), 16-byte aligned
- * arrays and r3dg_rasterize_backward_sh_adam_supported(M) == 1 (M a multiple of 4 up to 16 while R3DG_OPT_STAGE_SH_ROWS is
- * on); R3DG_EINVAL otherwise -- there is no fallback. */
-int r3dg_rasterize_backward_sh_adam_supported(int M);
-int r3dg_rasterize_backward_split_sh_adam(void* stream, void* geometry_stream, int P, int S, int D, int M, int R,
-                                          const float* d_background, int width, int height, const float* d_means3D,
-                                          const float* d_shs, const float* d_features, const float* d_colors_precomp,
-                                          const float* d_scales, float scale_modifier, const float* d_rotations,
-                                          const float* d_cov3D_precomp, const float* d_viewmatrix,
-                                          const float* d_projmatrix, const float* d_campos, float tan_fovx, float tan_fovy,
-                                          const int32_t* d_radii, const void* d_geom_buffer, const void* d_binning_buffer,
-                                          const void* d_img_buffer, const float* d_dL_dpix, const float* d_dL_dpix_o,
-                                          const float* d_dL_dpix_d, const float* d_dL_dpix_f, float* d_dL_dmean2D,
-                                          float* d_dL_dconic, float* d_dL_dopacity, float* d_dL_dcolor,
-                                          float* d_dL_dfeature, float* d_dL_dmean3D, float* d_dL_dcov3D, float* d_dL_dsh,
-                                          float* d_dL_dscale, float* d_dL_drot, int backward_geometry, int debug,
-                                          int n_active_features, const int* active_features,
-                                          const r3dg_adam_group* sh_adam, float beta1, float beta2, float eps, int step,
-                                          float grad_scale, const float* d_skip_flag);
-
-/* ---- the tile backward's gradient records, read in place ------------------------------------------------------------------
- * r3dg_rasterize_backward_split runs three launches: the tile kernel adds into one record per Gaussian, a scatter pass copies the
- * records into five arrays (and zeroes them), the per-Gaussian geometry kernel reads three of the arrays.  In a whole stage-2
- * iteration the other readers of the arrays -- r3dg_stage2_unpack_gradients and r3dg_stage2_activate_backward_with -- run one
- * thread per Gaussian too, so each of the three can read its Gaussian's record row itself and the scatter pass (at 300k
- * Gaussians 71 MB through device memory, alone on the critical path) is not needed.
+/* ---- the backward, split over two streams; optionally with the SH group's Adam in it and the gradient records read in place ----
+ * r3dg_rasterize_backward_split(stream, geometry_stream, scene, call, NULL, ..., NULL, NULL, NULL) is r3dg_rasterize_backward with
+ * the per-Gaussian geometry backward (K12+K13) launched on `geometry_stream`, ordered after the tile kernel by an event, so work that
+ * only needs the tile pass's FINAL outputs can follow on `stream` concurrently.  geometry_stream == stream is exactly
+ * r3dg_rasterize_backward.
+ *   final on `stream` (behind the tile kernel + its scatter pass):  d_dL_dfeature, d_dL_dopacity, d_dL_dcolor;
+ *   valid ONLY AFTER JOINING geometry_stream:  d_dL_dmean3D, d_dL_dcov3D, d_dL_dsh, d_dL_dscale, d_dL_drot -- AND d_dL_dmean2D
+ *     and d_dL_dconic: since round 5 the tile pass leaves RAW MOMENTS in those two (S_x, S_y / the second moments) and the
+ *     per-Gaussian geometry kernel turns them into the viewspace gradient IN PLACE (rasterizer_preprocess_bwd.hip).  A consumer on
+ *     `stream` that has not joined (e.g. densification statistics reading dL_dmeans2D) would read raw moments or race with that
+ *     rewrite.  r3dg_stream_wait_stream(stream, geometry_stream) is the join.
+ * Scratch: the tile pass adds into one gradient record per Gaussian, P x (16 or, with all S = 16 channels live, 32) floats of
+ * LIBRARY scratch per (device, stream) that ever ran a backward -- 64 / 128 bytes per Gaussian (2M Gaussians: 128 / 256 MB),
+ * grown geometrically and kept until r3dg_release_scratch().
+ *
+ * sh_adam != NULL (whole single-GPU training iterations; NULL: d_dL_dsh is written and the six arguments behind sh_adam are not
+ * read): the geometry kernel applies the Adam step of the SH colour group ITSELF.  `sh_adam` describes the group -- param ==
+ * d_shs ([P,M,3], n = 3 M P), both moments, lr / lr_tail / period / split as for r3dg_adam_step; its `grad` is not read -- and
+ * step, betas, eps, grad_scale and d_skip_flag mean what they mean there.  The gradient rows, which that kernel holds in on-chip
+ * memory, are consumed where they are: d_dL_dsh is NOT written (it may be NULL) and no r3dg_adam_step launch reads it and the
+ * parameter row again -- per Gaussian 3 x 12 M bytes less through device memory and one launch less.  Parameters and moments come
+ * out bit for bit as from the call with sh_adam == NULL followed by r3dg_adam_step on the one group (the same update statements,
+ * compiled with the same flags); Gaussians outside the view take part with a zero gradient, as there; every other output is what
+ * that call writes, also when *d_skip_flag != 0 (then parameters and moments are left untouched).  d_shs and the moments are final
+ * only after joining geometry_stream.  Needs SH input (d_colors_precomp == NULL), 16-byte aligned arrays and
+ * r3dg_rasterize_backward_sh_adam_supported(M) == 1 (M a multiple of 4 up to 16 while R3DG_OPT_STAGE_SH_ROWS is on);
+ * R3DG_EINVAL otherwise -- there is no fallback.
+ *
+ * d_records_out != NULL (NULL: the three launches above, and layout_out and supported_out must be NULL too): the tile backward's
+ * gradient records are read in place.  The classic call runs three launches: the tile kernel adds into one record per Gaussian, a
+ * scatter pass copies the records into five arrays (and zeroes them), the geometry kernel reads three of the arrays.  In a whole
+ * stage-2 iteration the other readers of the arrays -- r3dg_stage2_unpack_gradients and r3dg_stage2_activate_backward_with -- run
+ * one thread per Gaussian too, so each of the three can read its Gaussian's record row itself and the scatter pass (at 300k
+ * Gaussians 71 MB through device memory, alone on the critical path) is not needed.  The three outputs are reset first; then
+ *   *supported_out = 1: the tile kernel has filled the records of `stream`, the geometry kernel has read them in place on
+ *   geometry_stream, *d_records_out is the first of P rows and layout_out (R3DG_GRAD_RECORD_LAYOUT_INTS ints) describes them.  The
+ *   four arrays only the scatter pass writes -- d_dL_dconic, d_dL_dopacity, d_dL_dcolor, d_dL_dfeature -- are neither read nor
+ *   required; d_dL_dmean2D [P,3], an output of the op (required when P > 0), is written in full by the geometry kernel (valid
+ *   after joining geometry_stream); every other output is bit for bit what the classic call writes.  The caller then OWES the rows
+ *   their zeroing: r3dg_stage2_activate_backward_with_records on `stream` (behind the join with geometry_stream) or
+ *   r3dg_gradient_records_scatter.  A backward on the same stream that finds the debt unpaid clears the whole buffer first, so an
+ *   abandoned fill costs time, not correctness.
+ *   *supported_out = 0 with R3DG_OK: nothing was enqueued -- P == 0, or the instance this call selects has no 16-float records (more
+ *   than 7 active feature channels, or a depth gradient with more than 6); call again with d_records_out == NULL.
  *
  * A LAYOUT is R3DG_GRAD_RECORD_LAYOUT_INTS host ints that say which channel of a record holds what: the record width in floats |
  * colour r g b | S_x, S_y, depth side channel | S_xx, S_xy, S_yy, opacity | the channel of each of the 36 possible feature columns.
  * A channel of -1 means "not carried": the value is +0.f (the depth side channel of an instance without a depth gradient, a
  * feature column outside active_features).
- *
- * r3dg_rasterize_backward_split_records: r3dg_rasterize_backward_split_sh_adam without the scatter pass and without the four
- *   arrays only that pass writes.  *supported_out = 1: the tile kernel has filled the records of `stream`, the geometry kernel
- *   has read them in place on geometry_stream (sh_adam may be NULL: then it writes d_dL_dsh as r3dg_rasterize_backward_split
- *   does), *d_records_out is the first of P rows and layout_out describes them.  d_dL_dmean2D [P,3], an output of the op, is
- *   written in full by the geometry kernel (valid after joining geometry_stream); every other output is bit for bit what
- *   r3dg_rasterize_backward_split writes.  The caller then OWES the rows their zeroing: r3dg_stage2_activate_backward_with_records
- *   on `stream` (behind the join with geometry_stream) or r3dg_gradient_records_scatter.  A backward on the same stream that
- *   finds the debt unpaid clears the whole buffer first, so an abandoned fill costs time, not correctness.
- *   *supported_out = 0: nothing was enqueued -- the instance this call selects has no 16-float records (more than 7 active
- *   feature channels, or a depth gradient with more than 6); call r3dg_rasterize_backward_split.
- * r3dg_gradient_records_scatter: the scatter pass alone -- P rows of `layout` -> the five arrays of r3dg_rasterize_backward_split
- *   (every element written, as there), zeros -> the rows.  d_records may be a copy of the rows in the caller's memory.
+ * r3dg_gradient_records_scatter: the scatter pass alone -- P rows of `layout` -> the five arrays of the classic call (every element
+ *   written, as there), zeros -> the rows.  d_records may be a copy of the rows in the caller's memory.
  * r3dg_stage2_unpack_gradients_records, r3dg_stage2_activate_backward_with_records: those two calls with the rows (16-float
  *   records over S = 16 feature columns) in place of d_dL_dfeatures, and of d_dL_dopacity; same arithmetic, same results.  The
  *   second is the LAST reader: each thread writes its row back as zeros behind its loads.  Frozen geometry (d_g_xyz == NULL) has
  *   no records: R3DG_EINVAL. */
 #define R3DG_GRAD_RECORD_LAYOUT_INTS 47
-int r3dg_rasterize_backward_split_records(void* stream, void* geometry_stream, int P, int S, int D, int M, int R,
-                                          const float* d_background, int width, int height, const float* d_means3D,
-                                          const float* d_shs, const float* d_features, const float* d_colors_precomp,
-                                          const float* d_scales, float scale_modifier, const float* d_rotations,
-                                          const float* d_cov3D_precomp, const float* d_viewmatrix,
-                                          const float* d_projmatrix, const float* d_campos, float tan_fovx, float tan_fovy,
-                                          const int32_t* d_radii, const void* d_geom_buffer, const void* d_binning_buffer,
-                                          const void* d_img_buffer, const float* d_dL_dpix, const float* d_dL_dpix_o,
-                                          const float* d_dL_dpix_d, const float* d_dL_dpix_f, float* d_dL_dmean2D,
-                                          float* d_dL_dmean3D, float* d_dL_dcov3D, float* d_dL_dsh, float* d_dL_dscale,
-                                          float* d_dL_drot, int backward_geometry, int debug, int n_active_features,
-                                          const int* active_features, const r3dg_adam_group* sh_adam, float beta1, float beta2,
-                                          float eps, int step, float grad_scale, const float* d_skip_flag,
-                                          void** d_records_out, int* layout_out, int* supported_out);
+int r3dg_rasterize_backward_sh_adam_supported(int M);
+int r3dg_rasterize_backward_split(void* stream, void* geometry_stream, const r3dg_raster_scene* scene,
+                                  const r3dg_raster_backward* call, const r3dg_adam_group* sh_adam, float beta1, float beta2,
+                                  float eps, int step, float grad_scale, const float* d_skip_flag, void** d_records_out,
+                                  int* layout_out, int* supported_out);
 int r3dg_gradient_records_scatter(void* stream, int P, int S, float* d_records, const int* layout, float* d_dL_dmean2D,
                                   float* d_dL_dconic, float* d_dL_dopacity, float* d_dL_dcolor, float* d_dL_dfeature);
 int r3dg_stage2_unpack_gradients_records(void* stream, int P, const float* d_records, const int* layout,

@@ -63,7 +63,7 @@ def parse(text):
             first, *more = decl.split(",")                                                  # `float lr, lr_tail;`
             for d in [first] + [declarator(m.start(), first, "field")[0] + " " + d for d in more]:
                 base, stars, name = declarator(m.start(), d, "field")
-                if base not in _SCALARS or stars > 1:
+                if stars > 1 or (base not in _SCALARS and (base, stars) != ("void", 1)):
                     fail(m.start(), "field %r: unknown type" % d.strip())
                 fields.append((name, C.c_void_p if stars else _SCALARS[base]))
         structs[m.group(1)] = type(m.group(1), (C.Structure,), {"_fields_": fields})

@@ -90,23 +90,14 @@ struct RasterView {
     }
 };
 
-// The arguments of r3dg_rasterize_forward_begin[_bounded] in the order of the parameter lists (brace-initialised from them:
-// R3DG_FORWARD_ARGS below), then the four that only the bounded forward has (capacity < 0: the exact two-phase forward).
+// The arguments of r3dg_rasterize_forward_begin[_bounded] (the two structs by value: the caller's may be temporaries), then the
+// four that only the bounded forward has (capacity < 0: the exact two-phase forward).
 struct ForwardArgs {
     void* stream;
     r3dg_alloc_fn geometry_alloc, binning_alloc, image_alloc;
     void* user;
-    int P, S, D, M;
-    const float* background;
-    int width, height;
-    const float *means3D, *shs, *colors_precomp, *features, *opacities, *scales;
-    float scale_modifier;
-    const float *rotations, *cov3D_precomp, *viewmatrix, *projmatrix, *cam_pos;
-    float tan_fovx, tan_fovy, cx, cy;
-    int prefiltered, compute_pseudo_normal;
-    float *out_color, *out_opacity, *out_depth, *out_feature, *out_normal, *out_surface_xyz, *out_weights;
-    int32_t* radii;
-    int debug;
+    r3dg_raster_scene scene;
+    r3dg_raster_outputs out;
     long long capacity;
     float* overflow_flag;
     unsigned int* overflow_count;
@@ -164,8 +155,8 @@ static int enqueue_ordering(ForwardTicket* t, hipStream_t stream, int R)
     const ForwardArgs& a = t->a;
     const GeometryLayout& G = t->v.G;
     const ImageLayout& I = t->v.I;
-    const bool debug = a.debug != 0;
-    const int P = a.P, gx = t->v.gx, gy = t->v.gy, T = (int)t->v.T;
+    const bool debug = a.out.debug != 0;
+    const int P = a.scene.P, gx = t->v.gx, gy = t->v.gy, T = (int)t->v.T;
     char *gbuf = t->gbuf, *ibuf = t->ibuf;
     int* radii_p = t->radii_p;
     float* g_depths = (float*)(gbuf + G.depths);
@@ -252,22 +243,23 @@ static int enqueue_ordering(ForwardTicket* t, hipStream_t stream, int R)
 // The tile forward (K8) over the lists enqueue_ordering made and, where asked for, the pseudo-normals (K9/K10) behind it.
 static void render_tiles(const ForwardTicket* t, hipStream_t stream)
 {
-    const ForwardArgs& a = t->a;
+    const r3dg_raster_scene& s = t->a.scene;
+    const r3dg_raster_outputs& o = t->a.out;
     const GeometryLayout& G = t->v.G;
     const ImageLayout& I = t->v.I;
-    const bool debug = a.debug != 0;
+    const bool debug = o.debug != 0;
     StageTimer t_rf(stream, ST_RENDER_FWD);
-    launch_render_forward(stream, a.width, a.height, a.S,
+    launch_render_forward(stream, s.width, s.height, s.S,
                           opt(R3DG_OPT_TILE_ORDER) ? (uint32_t*)(t->ibuf + I.tile_order) : nullptr,
-                          (uint32_t*)(t->ibuf + I.ranges), t->point_list, (const float*)(t->gbuf + G.splat), a.features,
-                          (float*)(t->ibuf + I.final_T), (uint32_t*)(t->ibuf + I.n_contrib), a.background, a.out_color,
-                          a.out_opacity, a.out_depth, a.out_feature, a.out_weights);
+                          (uint32_t*)(t->ibuf + I.ranges), t->point_list, (const float*)(t->gbuf + G.splat), s.d_features,
+                          (float*)(t->ibuf + I.final_T), (uint32_t*)(t->ibuf + I.n_contrib), s.d_background, o.d_out_color,
+                          o.d_out_opacity, o.d_out_depth, o.d_out_feature, o.d_out_weights);
     check_launch(stream, debug, "render_forward");
     t_rf.stop();
-    if (a.compute_pseudo_normal) {
+    if (o.compute_pseudo_normal) {
         StageTimer t_n(stream, ST_NORMAL);
-        launch_pseudo_normal(stream, a.width, a.height, a.viewmatrix, t->focal_x, t->focal_y, a.cx, a.cy, a.out_opacity,
-                             a.out_depth, a.out_normal, a.out_surface_xyz, debug);
+        launch_pseudo_normal(stream, s.width, s.height, s.d_viewmatrix, t->focal_x, t->focal_y, s.cx, s.cy, o.d_out_opacity,
+                             o.d_out_depth, o.d_out_normal, o.d_out_surface_xyz, debug);
         t_n.stop();
     }
 }
@@ -276,21 +268,22 @@ static int forward_begin_impl(const ForwardArgs& a, void** ticket_out)
 {
     if (!ticket_out) return invalid("rasterize_forward_begin: null ticket pointer");
     *ticket_out = nullptr;
-    if (a.P < 0 || a.width <= 0 || a.height <= 0) return invalid("rasterize_forward: bad P/width/height");
-    if (a.S < 0 || a.S > R3DG_MAX_S_FWD) return invalid("rasterize_forward: feature channels S must be in [0,36]");
+    const r3dg_raster_scene& s = a.scene;
+    if (s.P < 0 || s.width <= 0 || s.height <= 0) return invalid("rasterize_forward: bad P/width/height");
+    if (s.S < 0 || s.S > R3DG_MAX_S_FWD) return invalid("rasterize_forward: feature channels S must be in [0,36]");
     if (!a.geometry_alloc || !a.binning_alloc || !a.image_alloc) return invalid("rasterize_forward: null resize callback");
-    if (a.shs == nullptr && a.colors_precomp == nullptr)
+    if (s.d_shs == nullptr && s.d_colors_precomp == nullptr)
         return invalid("rasterize_forward: provide SHs or precomputed colours");
-    if (a.shs != nullptr && a.colors_precomp == nullptr && (a.M < (a.D + 1) * (a.D + 1) || a.D > 3 || a.D < 0))
+    if (s.d_shs != nullptr && s.d_colors_precomp == nullptr && (s.M < (s.D + 1) * (s.D + 1) || s.D > 3 || s.D < 0))
         return invalid("rasterize_forward: SH degree/coefficients mismatch");
-    if (a.cov3D_precomp == nullptr && (a.scales == nullptr || a.rotations == nullptr))
+    if (s.d_cov3D_precomp == nullptr && (s.d_scales == nullptr || s.d_rotations == nullptr))
         return invalid("rasterize_forward: provide scales+rotations or a precomputed 3D covariance");
-    if (a.P == 0) return R3DG_OK;                  // no ticket: nothing was launched (finish accepts NULL)
+    if (s.P == 0) return R3DG_OK;                  // no ticket: nothing was launched (finish accepts NULL)
 
     return guarded([&]() -> int {
         hipStream_t stream = (hipStream_t)a.stream;
-        const bool debug = a.debug != 0;
-        const RasterView v = RasterView::make(a.P, a.width, a.height);
+        const bool debug = a.out.debug != 0;
+        const RasterView v = RasterView::make(s.P, s.width, s.height);
         const GeometryLayout& G = v.G;
         char* gbuf = (char*)a.geometry_alloc(a.user, G.bytes);
         char* ibuf = (char*)a.image_alloc(a.user, v.I.bytes);
@@ -300,9 +293,9 @@ static int forward_begin_impl(const ForwardArgs& a, void** ticket_out)
         struct Release { ForwardTicket* t; ~Release() { if (t) ticket_release(t); } } on_error{t};      // (a launch check may throw)
         t->a = a;
         t->v = v;
-        t->focal_y = a.height / (2.0f * a.tan_fovy);
-        t->focal_x = a.width / (2.0f * a.tan_fovx);
-        t->radii_p = a.radii ? a.radii : (int*)(gbuf + G.radii);
+        t->focal_y = s.height / (2.0f * s.tan_fovy);
+        t->focal_x = s.width / (2.0f * s.tan_fovx);
+        t->radii_p = a.out.d_radii ? a.out.d_radii : (int*)(gbuf + G.radii);
         t->gbuf = gbuf;
         t->ibuf = ibuf;
         t->bbuf = nullptr;
@@ -328,9 +321,9 @@ static int forward_begin_impl(const ForwardArgs& a, void** ticket_out)
         }
         unsigned long long* g_total = (unsigned long long*)(gbuf + G.total);
         StageTimer t_pre(order_stream, ST_PREPROCESS);
-        launch_preprocess(order_stream, a.P, a.D, a.M, a.means3D, a.scales, a.scale_modifier, a.rotations, a.opacities, a.shs,
-                          (uint8_t*)(gbuf + G.clamped), a.cov3D_precomp, a.colors_precomp, a.viewmatrix, a.projmatrix,
-                          a.cam_pos, a.width, a.height, a.tan_fovx, a.tan_fovy, t->focal_x, t->focal_y, t->radii_p,
+        launch_preprocess(order_stream, s.P, s.D, s.M, s.d_means3D, s.d_scales, s.scale_modifier, s.d_rotations, s.d_opacities,
+                          s.d_shs, (uint8_t*)(gbuf + G.clamped), s.d_cov3D_precomp, s.d_colors_precomp, s.d_viewmatrix,
+                          s.d_projmatrix, s.d_campos, s.width, s.height, s.tan_fovx, s.tan_fovy, t->focal_x, t->focal_y, t->radii_p,
                           (float*)(gbuf + G.means2D), (float*)(gbuf + G.depths), (float*)(gbuf + G.cov3D),
                           (float*)(gbuf + G.rgb), (float*)(gbuf + G.conic_opacity), (float*)(gbuf + G.splat), v.gx, v.gy,
                           (uint32_t*)(gbuf + G.tiles_touched), (uint32_t*)(gbuf + G.block_sums), g_total, !t->fused_front,
@@ -400,41 +393,24 @@ int r3dg_binning_state_offsets(int64_t R, size_t* o)
     return R3DG_OK;
 }
 
-#define R3DG_FORWARD_ARGS                                                                                              \
-    stream_, geometry_alloc, binning_alloc, image_alloc, user, P, S, D, M, background, width, height, means3D, shs,    \
-        colors_precomp, features, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, \
-        cam_pos, tan_fovx, tan_fovy, cx, cy, prefiltered, compute_pseudo_normal, out_color, out_opacity, out_depth,    \
-        out_feature, out_normal, out_surface_xyz, out_weights, radii, debug_
-
 int r3dg_rasterize_forward_begin(void* stream_, r3dg_alloc_fn geometry_alloc, r3dg_alloc_fn binning_alloc,
-                           r3dg_alloc_fn image_alloc, void* user, int P, int S, int D, int M,
-                           const float* background, int width, int height, const float* means3D, const float* shs,
-                           const float* colors_precomp, const float* features, const float* opacities,
-                           const float* scales, float scale_modifier, const float* rotations,
-                           const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                           const float* cam_pos, float tan_fovx, float tan_fovy, float cx, float cy, int prefiltered,
-                           int compute_pseudo_normal, float* out_color, float* out_opacity, float* out_depth,
-                           float* out_feature, float* out_normal, float* out_surface_xyz, float* out_weights,
-                           int32_t* radii, int debug_, void** ticket_out)
+                                 r3dg_alloc_fn image_alloc, void* user, const r3dg_raster_scene* scene,
+                                 const r3dg_raster_outputs* outputs, void** ticket_out)
 {
-    return forward_begin_impl(ForwardArgs{R3DG_FORWARD_ARGS, -1, nullptr, nullptr, nullptr}, ticket_out);
+    if (!scene || !outputs) return invalid("rasterize_forward_begin: null scene or outputs");
+    return forward_begin_impl(ForwardArgs{stream_, geometry_alloc, binning_alloc, image_alloc, user, *scene, *outputs, -1, nullptr,
+                                          nullptr, nullptr}, ticket_out);
 }
 
 int r3dg_rasterize_forward_begin_bounded(void* stream_, r3dg_alloc_fn geometry_alloc, r3dg_alloc_fn binning_alloc,
-                           r3dg_alloc_fn image_alloc, void* user, int P, int S, int D, int M,
-                           const float* background, int width, int height, const float* means3D, const float* shs,
-                           const float* colors_precomp, const float* features, const float* opacities,
-                           const float* scales, float scale_modifier, const float* rotations,
-                           const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                           const float* cam_pos, float tan_fovx, float tan_fovy, float cx, float cy, int prefiltered,
-                           int compute_pseudo_normal, float* out_color, float* out_opacity, float* out_depth,
-                           float* out_feature, float* out_normal, float* out_surface_xyz, float* out_weights,
-                           int32_t* radii, int debug_, void* ordering_stream, long long capacity,
-                           float* overflow_flag, unsigned int* overflow_count, void** ticket_out)
+                                         r3dg_alloc_fn image_alloc, void* user, const r3dg_raster_scene* scene,
+                                         const r3dg_raster_outputs* outputs, void* ordering_stream, long long capacity,
+                                         float* overflow_flag, unsigned int* overflow_count, void** ticket_out)
 {
+    if (!scene || !outputs) return invalid("rasterize_forward_begin: null scene or outputs");
     if (capacity < 0 || capacity > 0x7fffffffll) return invalid("rasterize_forward (bounded): capacity must be in [0, 2^31)");
-    return forward_begin_impl(ForwardArgs{R3DG_FORWARD_ARGS, capacity, overflow_flag, overflow_count, ordering_stream},
-                              ticket_out);
+    return forward_begin_impl(ForwardArgs{stream_, geometry_alloc, binning_alloc, image_alloc, user, *scene, *outputs, capacity,
+                                          overflow_flag, overflow_count, ordering_stream}, ticket_out);
 }
 int r3dg_rasterize_forward_finish_bounded(void* ticket_, void* main_stream_)
 {
@@ -486,44 +462,30 @@ int r3dg_rasterize_forward_finish_on(void* ticket_, void* ordering_stream_, int*
     return st;
 }
 
+// (the reference's list; parameters carry the names of the struct fields they fill, in the structs' order of declaration)
 int r3dg_rasterize_forward(void* stream_, r3dg_alloc_fn geometry_alloc, r3dg_alloc_fn binning_alloc,
                            r3dg_alloc_fn image_alloc, void* user, int P, int S, int D, int M,
-                           const float* background, int width, int height, const float* means3D, const float* shs,
-                           const float* colors_precomp, const float* features, const float* opacities,
-                           const float* scales, float scale_modifier, const float* rotations,
-                           const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                           const float* cam_pos, float tan_fovx, float tan_fovy, float cx, float cy, int prefiltered,
-                           int compute_pseudo_normal, float* out_color, float* out_opacity, float* out_depth,
-                           float* out_feature, float* out_normal, float* out_surface_xyz, float* out_weights,
-                           int32_t* radii, int debug_, int* num_rendered_out)
+                           const float* d_background, int width, int height, const float* d_means3D, const float* d_shs,
+                           const float* d_colors_precomp, const float* d_features, const float* d_opacities,
+                           const float* d_scales, float scale_modifier, const float* d_rotations,
+                           const float* d_cov3D_precomp, const float* d_viewmatrix, const float* d_projmatrix,
+                           const float* d_campos, float tan_fovx, float tan_fovy, float cx, float cy, int prefiltered,
+                           int compute_pseudo_normal, float* d_out_color, float* d_out_opacity, float* d_out_depth,
+                           float* d_out_feature, float* d_out_normal, float* d_out_surface_xyz, float* d_out_weights,
+                           int32_t* d_radii, int debug, int* num_rendered_out)
 {
     if (num_rendered_out) *num_rendered_out = 0;
+    const r3dg_raster_scene scene = {P, S, D, M, width, height,
+                                     d_background, d_means3D, d_shs, d_colors_precomp, d_features, d_opacities, d_scales,
+                                     scale_modifier, d_rotations, d_cov3D_precomp, d_viewmatrix, d_projmatrix, d_campos,
+                                     tan_fovx, tan_fovy, cx, cy};
+    const r3dg_raster_outputs outputs = {prefiltered, compute_pseudo_normal, debug,
+                                         d_out_color, d_out_opacity, d_out_depth, d_out_feature, d_out_normal, d_out_surface_xyz,
+                                         d_out_weights, d_radii};
     void* ticket = nullptr;
-    const int st = forward_begin_impl(ForwardArgs{R3DG_FORWARD_ARGS, -1, nullptr, nullptr, nullptr}, &ticket);
+    const int st = r3dg_rasterize_forward_begin(stream_, geometry_alloc, binning_alloc, image_alloc, user, &scene, &outputs, &ticket);
     if (st != R3DG_OK) return st;
     return r3dg_rasterize_forward_finish(ticket, num_rendered_out);
-}
-#undef R3DG_FORWARD_ARGS
-
-// (defined below)
-int r3dg_rasterize_backward(void* stream_, int P, int S, int D, int M, int R, const float* background, int width,
-                            int height, const float* means3D, const float* shs, const float* features,
-                            const float* colors_precomp, const float* scales, float scale_modifier,
-                            const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                            const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                            const int32_t* radii, const void* geom_buffer, const void* binning_buffer,
-                            const void* img_buffer, const float* dL_dpix, const float* dL_dpix_o,
-                            const float* dL_dpix_d, const float* dL_dpix_f, float* dL_dmean2D, float* dL_dconic,
-                            float* dL_dopacity, float* dL_dcolor, float* dL_dfeature, float* dL_dmean3D,
-                            float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                            int backward_geometry, int debug_)
-{
-    return r3dg_rasterize_backward_split(stream_, stream_, P, S, D, M, R, background, width, height, means3D, shs,
-                                         features, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
-                                         viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer,
-                                         binning_buffer, img_buffer, dL_dpix, dL_dpix_o, dL_dpix_d, dL_dpix_f, dL_dmean2D,
-                                         dL_dconic, dL_dopacity, dL_dcolor, dL_dfeature, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                         dL_dscale, dL_drot, backward_geometry, debug_, -1, nullptr);
 }
 
 // the optional list of feature channels whose gradients the caller wants (n < 0: all S of them)
@@ -536,204 +498,158 @@ static int check_active_features(const char* name, int n, const int* list, int S
     return R3DG_OK;
 }
 
-// the backward behind r3dg_rasterize_backward_split, _split_sh_adam (`adam` != nullptr: the geometry kernel applies the SH
-// colour group's Adam and does not write dL_dsh) and _split_records (`records_out` != nullptr: no scatter pass -- the geometry
-// kernel reads the gradient record rows in place, the rows and their layout are handed to the caller, whose kernels read the rest;
-// *supported_out = 0 and nothing enqueued where the instance has no 16-float rows)
-static int backward_split_impl(void* stream_, void* geometry_stream_, int P, int S, int D, int M, int R,
-                                  const float* background, int width, int height, const float* means3D,
-                                  const float* shs, const float* features, const float* colors_precomp,
-                                  const float* scales, float scale_modifier, const float* rotations,
-                                  const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                                  const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
-                                  const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
-                                  const float* dL_dpix, const float* dL_dpix_o, const float* dL_dpix_d,
-                                  const float* dL_dpix_f, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
-                                  float* dL_dcolor, float* dL_dfeature, float* dL_dmean3D, float* dL_dcov3D,
-                                  float* dL_dsh, float* dL_dscale, float* dL_drot, int backward_geometry, int debug_,
-                                  int n_active_features, const int* active_features,
-                                  const ShAdamArgs* adam, void** records_out = nullptr, int* layout_out = nullptr,
-                                  int* supported_out = nullptr)
+// the backward behind r3dg_rasterize_backward[_split]: `adam` != nullptr: the geometry kernel applies the SH colour group's Adam
+// and does not write dL_dsh; `records_out` != nullptr: no scatter pass -- the geometry kernel reads the gradient record rows in
+// place, the rows and their layout are handed to the caller, whose kernels read the rest; *supported_out = 0 and nothing enqueued
+// where the instance has no 16-float rows (the entry point has reset the three outputs)
+static int backward_split_impl(void* stream_, void* geometry_stream_, const r3dg_raster_scene& s, const r3dg_raster_backward& c,
+                               const ShAdamArgs* adam, void** records_out, int* layout_out, int* supported_out)
 {
-    if (records_out) *records_out = nullptr;
-    if (supported_out) *supported_out = 0;
-    if (P < 0 || width <= 0 || height <= 0 || R < 0) return invalid("rasterize_backward: bad P/R/width/height");
-    if (S < 0 || S > R3DG_MAX_S_BWD) return invalid("rasterize_backward: feature channels S must be in [0,36]");
-    if (P == 0) return R3DG_OK;
-    if (!geom_buffer || !img_buffer || (R > 0 && !binning_buffer)) return invalid("rasterize_backward: null state buffer");
-    if (!dL_dpix || !dL_dpix_o || (S > 0 && !dL_dpix_f)) return invalid("rasterize_backward: null upstream gradient");
-    if (int e = check_active_features("rasterize_backward", n_active_features, active_features, S)) return e;
+    if (s.P < 0 || s.width <= 0 || s.height <= 0 || c.R < 0) return invalid("rasterize_backward: bad P/R/width/height");
+    if (s.S < 0 || s.S > R3DG_MAX_S_BWD) return invalid("rasterize_backward: feature channels S must be in [0,36]");
+    if (s.P == 0) return R3DG_OK;
+    if (!c.d_geom_buffer || !c.d_img_buffer || (c.R > 0 && !c.d_binning_buffer)) return invalid("rasterize_backward: null state buffer");
+    if (!c.d_dL_dpix || !c.d_dL_dpix_o || (s.S > 0 && !c.d_dL_dpix_f)) return invalid("rasterize_backward: null upstream gradient");
+    if (int e = check_active_features("rasterize_backward", c.n_active_features, c.active_features, s.S)) return e;
     const bool in_place = records_out != nullptr;
     if (in_place) {
-        if (!layout_out || !supported_out) return invalid("rasterize_backward_split_records: null output");
-        const GradRecordLayout L = render_backward_layout(S, n_active_features, active_features, dL_dpix_d != nullptr,
-                                                          backward_geometry);
-        if (L.nvp != 16) return R3DG_OK;                 // (not an error: the caller takes r3dg_rasterize_backward_split)
+        const GradRecordLayout L = render_backward_layout(s.S, c.n_active_features, c.active_features, c.d_dL_dpix_d != nullptr,
+                                                          c.backward_geometry);
+        if (L.nvp != 16) return R3DG_OK;                 // (not an error: the caller calls again without record outputs)
         *supported_out = 1;
     }
 
     return guarded([&]() -> int {
         hipStream_t stream = (hipStream_t)stream_;
-        const bool debug = debug_ != 0;
-        const float focal_y = height / (2.0f * tan_fovy);
-        const float focal_x = width / (2.0f * tan_fovx);
+        const bool debug = c.debug != 0;
+        const int P = s.P, S = s.S, width = s.width, height = s.height;
+        const float focal_y = height / (2.0f * s.tan_fovy);
+        const float focal_x = width / (2.0f * s.tan_fovx);
         const RasterView v = RasterView::make(P, width, height);
         const GeometryLayout& G = v.G;
         const ImageLayout& I = v.I;
-        BinningLayout B = BinningLayout::make((size_t)R);
-        const char* gbuf = (const char*)geom_buffer;
-        const char* ibuf = (const char*)img_buffer;
-        const char* bbuf = (const char*)binning_buffer;
-        const int* radii_p = radii ? radii : (const int*)(gbuf + G.radii);
+        BinningLayout B = BinningLayout::make((size_t)c.R);
+        const char* gbuf = (const char*)c.d_geom_buffer;
+        const char* ibuf = (const char*)c.d_img_buffer;
+        const char* bbuf = (const char*)c.d_binning_buffer;
+        const int* radii_p = c.d_radii ? c.d_radii : (const int*)(gbuf + G.radii);
 
         float* rec = nullptr;
         GradRecordLayout layout;
         if (in_place) {
             StageTimer t_rb(stream, ST_RENDER_BWD);
-            rec = launch_render_backward_fill(stream, P, width, height, S, n_active_features, active_features,
+            rec = launch_render_backward_fill(stream, P, width, height, S, c.n_active_features, c.active_features,
                                               opt(R3DG_OPT_TILE_ORDER) ? (const uint32_t*)(ibuf + I.tile_order) : nullptr,
-                                              (const uint32_t*)(ibuf + I.ranges), (const uint32_t*)(bbuf + B.vals), background,
-                                              (const float*)(gbuf + G.splat), features, (const float*)(ibuf + I.final_T),
-                                              (const uint32_t*)(ibuf + I.n_contrib), dL_dpix, dL_dpix_o, dL_dpix_d, dL_dpix_f,
-                                              backward_geometry, R > 0, &layout);
+                                              (const uint32_t*)(ibuf + I.ranges), (const uint32_t*)(bbuf + B.vals), s.d_background,
+                                              (const float*)(gbuf + G.splat), s.d_features, (const float*)(ibuf + I.final_T),
+                                              (const uint32_t*)(ibuf + I.n_contrib), c.d_dL_dpix, c.d_dL_dpix_o, c.d_dL_dpix_d,
+                                              c.d_dL_dpix_f, c.backward_geometry, c.R > 0, &layout);
             check_launch(stream, debug, "render_backward");
             t_rb.stop();
             *records_out = rec;
             std::memcpy(layout_out, &layout, sizeof(layout));
-        } else if (R > 0) {
+        } else if (c.R > 0) {
             StageTimer t_rb(stream, ST_RENDER_BWD);
-            launch_render_backward(stream, P, width, height, S, n_active_features, active_features,
+            launch_render_backward(stream, P, width, height, S, c.n_active_features, c.active_features,
                                    opt(R3DG_OPT_TILE_ORDER) ? (const uint32_t*)(ibuf + I.tile_order) : nullptr,
                                    (const uint32_t*)(ibuf + I.ranges),
-                                   (const uint32_t*)(bbuf + B.vals), background, (const float*)(gbuf + G.splat),
-                                   features, (const float*)(ibuf + I.final_T), (const uint32_t*)(ibuf + I.n_contrib),
-                                   dL_dpix, dL_dpix_o, dL_dpix_d, dL_dpix_f, dL_dmean2D, dL_dconic, dL_dopacity,
-                                   dL_dcolor, dL_dfeature, backward_geometry);
+                                   (const uint32_t*)(bbuf + B.vals), s.d_background, (const float*)(gbuf + G.splat),
+                                   s.d_features, (const float*)(ibuf + I.final_T), (const uint32_t*)(ibuf + I.n_contrib),
+                                   c.d_dL_dpix, c.d_dL_dpix_o, c.d_dL_dpix_d, c.d_dL_dpix_f, c.d_dL_dmean2D, c.d_dL_dconic,
+                                   c.d_dL_dopacity, c.d_dL_dcolor, c.d_dL_dfeature, c.backward_geometry);
             check_launch(stream, debug, "render_backward");
             t_rb.stop();
         } else {
             // nothing was rendered: the five per-Gaussian outputs the tile pass writes are zero
-            R3DG_HIP(hipMemsetAsync(dL_dmean2D, 0, (size_t)P * 3 * sizeof(float), stream));
-            R3DG_HIP(hipMemsetAsync(dL_dconic, 0, (size_t)P * 4 * sizeof(float), stream));
-            R3DG_HIP(hipMemsetAsync(dL_dopacity, 0, (size_t)P * sizeof(float), stream));
-            R3DG_HIP(hipMemsetAsync(dL_dcolor, 0, (size_t)P * 3 * sizeof(float), stream));
-            if (S > 0 && dL_dfeature != nullptr) R3DG_HIP(hipMemsetAsync(dL_dfeature, 0, (size_t)P * S * sizeof(float), stream));
+            R3DG_HIP(hipMemsetAsync(c.d_dL_dmean2D, 0, (size_t)P * 3 * sizeof(float), stream));
+            R3DG_HIP(hipMemsetAsync(c.d_dL_dconic, 0, (size_t)P * 4 * sizeof(float), stream));
+            R3DG_HIP(hipMemsetAsync(c.d_dL_dopacity, 0, (size_t)P * sizeof(float), stream));
+            R3DG_HIP(hipMemsetAsync(c.d_dL_dcolor, 0, (size_t)P * 3 * sizeof(float), stream));
+            if (S > 0 && c.d_dL_dfeature != nullptr)
+                R3DG_HIP(hipMemsetAsync(c.d_dL_dfeature, 0, (size_t)P * S * sizeof(float), stream));
         }
-        const float* cov3D_ptr = cov3D_precomp != nullptr ? cov3D_precomp : (const float*)(gbuf + G.cov3D);
+        const float* cov3D_ptr = s.d_cov3D_precomp != nullptr ? s.d_cov3D_precomp : (const float*)(gbuf + G.cov3D);
         // the per-Gaussian geometry backward may run on a second stream, ordered after the tile kernel by an event
         hipStream_t gstream = (hipStream_t)geometry_stream_;
         stream_wait_stream(gstream, stream);
         stream = gstream;
         StageTimer t_pb(stream, ST_PREPROCESS_BWD);
-        launch_preprocess_backward(stream, P, D, M, means3D, radii_p, colors_precomp == nullptr ? shs : nullptr,
-                                   (const uint8_t*)(gbuf + G.clamped), cov3D_precomp == nullptr ? scales : nullptr,
-                                   rotations, scale_modifier, cov3D_ptr, viewmatrix, projmatrix, focal_x, focal_y,
-                                   tan_fovx, tan_fovy, campos, dL_dmean2D, dL_dconic, (const float*)(gbuf + G.conic_opacity),
-                                   width, height, dL_dmean3D, dL_dcolor, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, adam, rec,
-                                   in_place ? &layout : nullptr);
+        launch_preprocess_backward(stream, P, s.D, s.M, s.d_means3D, radii_p, s.d_colors_precomp == nullptr ? s.d_shs : nullptr,
+                                   (const uint8_t*)(gbuf + G.clamped), s.d_cov3D_precomp == nullptr ? s.d_scales : nullptr,
+                                   s.d_rotations, s.scale_modifier, cov3D_ptr, s.d_viewmatrix, s.d_projmatrix, focal_x, focal_y,
+                                   s.tan_fovx, s.tan_fovy, s.d_campos, c.d_dL_dmean2D, c.d_dL_dconic,
+                                   (const float*)(gbuf + G.conic_opacity), width, height, c.d_dL_dmean3D, c.d_dL_dcolor,
+                                   c.d_dL_dcov3D, c.d_dL_dsh, c.d_dL_dscale, c.d_dL_drot, adam, rec, in_place ? &layout : nullptr);
         check_launch(stream, debug, "preprocess_backward");
         t_pb.stop();
         return R3DG_OK;
     });
 }
 
-#define R3DG_BACKWARD_SPLIT_ARGS                                                                                              \
-    stream_, geometry_stream_, P, S, D, M, R, background, width, height, means3D, shs, features, colors_precomp, scales,        \
-        scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer,       \
-        binning_buffer, img_buffer, dL_dpix, dL_dpix_o, dL_dpix_d, dL_dpix_f, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,    \
-        dL_dfeature, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, backward_geometry, debug_, n_active_features,           \
-        active_features
-
-int r3dg_rasterize_backward_split(void* stream_, void* geometry_stream_, int P, int S, int D, int M, int R,
-                                  const float* background, int width, int height, const float* means3D,
-                                  const float* shs, const float* features, const float* colors_precomp,
-                                  const float* scales, float scale_modifier, const float* rotations,
-                                  const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                                  const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
-                                  const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
-                                  const float* dL_dpix, const float* dL_dpix_o, const float* dL_dpix_d,
-                                  const float* dL_dpix_f, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
-                                  float* dL_dcolor, float* dL_dfeature, float* dL_dmean3D, float* dL_dcov3D,
-                                  float* dL_dsh, float* dL_dscale, float* dL_drot, int backward_geometry, int debug_,
-                                  int n_active_features, const int* active_features)
+// (the reference's list, as r3dg_rasterize_forward above)
+int r3dg_rasterize_backward(void* stream_, int P, int S, int D, int M, int R, const float* d_background, int width,
+                            int height, const float* d_means3D, const float* d_shs, const float* d_features,
+                            const float* d_colors_precomp, const float* d_scales, float scale_modifier,
+                            const float* d_rotations, const float* d_cov3D_precomp, const float* d_viewmatrix,
+                            const float* d_projmatrix, const float* d_campos, float tan_fovx, float tan_fovy,
+                            const int32_t* d_radii, const void* d_geom_buffer, const void* d_binning_buffer,
+                            const void* d_img_buffer, const float* d_dL_dpix, const float* d_dL_dpix_o,
+                            const float* d_dL_dpix_d, const float* d_dL_dpix_f, float* d_dL_dmean2D, float* d_dL_dconic,
+                            float* d_dL_dopacity, float* d_dL_dcolor, float* d_dL_dfeature, float* d_dL_dmean3D,
+                            float* d_dL_dcov3D, float* d_dL_dsh, float* d_dL_dscale, float* d_dL_drot,
+                            int backward_geometry, int debug)
 {
-    return backward_split_impl(R3DG_BACKWARD_SPLIT_ARGS, nullptr);
+    const r3dg_raster_scene scene = {P, S, D, M, width, height,
+                                     d_background, d_means3D, d_shs, d_colors_precomp, d_features, /*d_opacities=*/nullptr, d_scales,
+                                     scale_modifier, d_rotations, d_cov3D_precomp, d_viewmatrix, d_projmatrix, d_campos,
+                                     tan_fovx, tan_fovy, /*cx, cy=*/0.0f, 0.0f};
+    const r3dg_raster_backward call = {R, d_radii, d_geom_buffer, d_binning_buffer, d_img_buffer,
+                                       d_dL_dpix, d_dL_dpix_o, d_dL_dpix_d, d_dL_dpix_f,
+                                       d_dL_dmean2D, d_dL_dconic, d_dL_dopacity, d_dL_dcolor, d_dL_dfeature,
+                                       d_dL_dmean3D, d_dL_dcov3D, d_dL_dsh, d_dL_dscale, d_dL_drot,
+                                       backward_geometry, debug, /*n_active_features=*/-1, /*active_features=*/nullptr};
+    return backward_split_impl(stream_, stream_, scene, call, nullptr, nullptr, nullptr, nullptr);
 }
 
 int r3dg_rasterize_backward_sh_adam_supported(int M) { return preprocess_backward_applies_adam(M) ? 1 : 0; }
 
-int r3dg_rasterize_backward_split_sh_adam(void* stream_, void* geometry_stream_, int P, int S, int D, int M, int R,
-                                  const float* background, int width, int height, const float* means3D,
-                                  const float* shs, const float* features, const float* colors_precomp,
-                                  const float* scales, float scale_modifier, const float* rotations,
-                                  const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                                  const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
-                                  const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
-                                  const float* dL_dpix, const float* dL_dpix_o, const float* dL_dpix_d,
-                                  const float* dL_dpix_f, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
-                                  float* dL_dcolor, float* dL_dfeature, float* dL_dmean3D, float* dL_dcov3D,
-                                  float* dL_dsh, float* dL_dscale, float* dL_drot, int backward_geometry, int debug_,
-                                  int n_active_features, const int* active_features,
-                                  const r3dg_adam_group* sh_adam, float beta1, float beta2, float eps, int step,
-                                  float grad_scale, const float* skip_flag)
+// r3dg_rasterize_backward_split's arguments behind `sh_adam`, checked and made into what the geometry kernel takes
+static int make_sh_adam(const r3dg_raster_scene& s, const r3dg_adam_group& g, float beta1, float beta2, float eps, int step,
+                        float grad_scale, const float* skip_flag, ShAdamArgs* adam)
 {
-    const char* me = "rasterize_backward_split_sh_adam: ";
-    if (P < 0 || M < 0) return invalid(std::string(me) + "bad P/M");
-    if (!sh_adam) return invalid(std::string(me) + "null group");
-    if (step < 1) return invalid(std::string(me) + "step counts from 1");
-    if (!preprocess_backward_applies_adam(M)) return invalid(std::string(me) + "no such kernel for this M / with STAGE_SH_ROWS off");
-    if (!shs || colors_precomp) return invalid(std::string(me) + "needs SH input");
-    const r3dg_adam_group& g = *sh_adam;
-    if (g.param != shs || g.n != (uint64_t)P * 3 * (uint64_t)M || g.n >= (1ull << 32))
-        return invalid(std::string(me) + "the group must be the [P,M,3] SH tensor itself (below 2^32 elements)");
-    if (P > 0 && (!g.exp_avg || !g.exp_avg_sq || (((uintptr_t)g.param | (uintptr_t)g.exp_avg | (uintptr_t)g.exp_avg_sq) & 15)))
-        return invalid(std::string(me) + "null or unaligned buffer in group");
+    const std::string me = "rasterize_backward_split (sh_adam): ";
+    if (s.P < 0 || s.M < 0) return invalid(me + "bad P/M");
+    if (step < 1) return invalid(me + "step counts from 1");
+    if (!preprocess_backward_applies_adam(s.M)) return invalid(me + "no such kernel for this M / with STAGE_SH_ROWS off");
+    if (!s.d_shs || s.d_colors_precomp) return invalid(me + "needs SH input");
+    if (g.param != s.d_shs || g.n != (uint64_t)s.P * 3 * (uint64_t)s.M || g.n >= (1ull << 32))
+        return invalid(me + "the group must be the [P,M,3] SH tensor itself (below 2^32 elements)");
+    if (s.P > 0 && (!g.exp_avg || !g.exp_avg_sq || (((uintptr_t)g.param | (uintptr_t)g.exp_avg | (uintptr_t)g.exp_avg_sq) & 15)))
+        return invalid(me + "null or unaligned buffer in group");
     const AdamBias b = adam_bias(beta1, beta2, step);
-    const ShAdamArgs adam = {g, beta1, beta2, eps, b.bias1, b.inv_sqrt_bias2, grad_scale, skip_flag};
-    return backward_split_impl(R3DG_BACKWARD_SPLIT_ARGS, &adam);
+    *adam = ShAdamArgs{g, beta1, beta2, eps, b.bias1, b.inv_sqrt_bias2, grad_scale, skip_flag};
+    return R3DG_OK;
 }
-#undef R3DG_BACKWARD_SPLIT_ARGS
 
-int r3dg_rasterize_backward_split_records(void* stream_, void* geometry_stream_, int P, int S, int D, int M, int R,
-                                  const float* background, int width, int height, const float* means3D,
-                                  const float* shs, const float* features, const float* colors_precomp,
-                                  const float* scales, float scale_modifier, const float* rotations,
-                                  const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                                  const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
-                                  const void* geom_buffer, const void* binning_buffer, const void* img_buffer,
-                                  const float* dL_dpix, const float* dL_dpix_o, const float* dL_dpix_d,
-                                  const float* dL_dpix_f, float* dL_dmean2D, float* dL_dmean3D, float* dL_dcov3D,
-                                  float* dL_dsh, float* dL_dscale, float* dL_drot, int backward_geometry, int debug_,
-                                  int n_active_features, const int* active_features,
-                                  const r3dg_adam_group* sh_adam, float beta1, float beta2, float eps, int step,
-                                  float grad_scale, const float* skip_flag, void** records_out, int* layout_out,
-                                  int* supported_out)
+int r3dg_rasterize_backward_split(void* stream_, void* geometry_stream_, const r3dg_raster_scene* scene,
+                                  const r3dg_raster_backward* call, const r3dg_adam_group* sh_adam, float beta1, float beta2,
+                                  float eps, int step, float grad_scale, const float* skip_flag, void** records_out,
+                                  int* layout_out, int* supported_out)
 {
-    const char* me = "rasterize_backward_split_records: ";
-    if (!records_out || !layout_out || !supported_out) return invalid(std::string(me) + "null output");
-    *records_out = nullptr;
-    *supported_out = 0;
-    if (P > 0 && !dL_dmean2D) return invalid(std::string(me) + "null dL_dmean2D");
-    ShAdamArgs adam = {};
-    if (sh_adam) {
-        if (P < 0 || M < 0) return invalid(std::string(me) + "bad P/M");
-        if (step < 1) return invalid(std::string(me) + "step counts from 1");
-        if (!preprocess_backward_applies_adam(M)) return invalid(std::string(me) + "no such kernel for this M / with STAGE_SH_ROWS off");
-        if (!shs || colors_precomp) return invalid(std::string(me) + "needs SH input");
-        const r3dg_adam_group& g = *sh_adam;
-        if (g.param != shs || g.n != (uint64_t)P * 3 * (uint64_t)M || g.n >= (1ull << 32))
-            return invalid(std::string(me) + "the group must be the [P,M,3] SH tensor itself (below 2^32 elements)");
-        if (P > 0 && (!g.exp_avg || !g.exp_avg_sq || (((uintptr_t)g.param | (uintptr_t)g.exp_avg | (uintptr_t)g.exp_avg_sq) & 15)))
-            return invalid(std::string(me) + "null or unaligned buffer in group");
-        const AdamBias b = adam_bias(beta1, beta2, step);
-        adam = ShAdamArgs{g, beta1, beta2, eps, b.bias1, b.inv_sqrt_bias2, grad_scale, skip_flag};
+    const std::string me = "rasterize_backward_split: ";
+    if (records_out ? !layout_out || !supported_out : layout_out || supported_out)
+        return invalid(me + "records, layout and supported outputs go together");
+    if (records_out) {
+        *records_out = nullptr;
+        *supported_out = 0;
     }
-    return backward_split_impl(stream_, geometry_stream_, P, S, D, M, R, background, width, height, means3D, shs, features,
-                               colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
-                               tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dpix_o, dL_dpix_d,
-                               dL_dpix_f, dL_dmean2D, nullptr, nullptr, nullptr, nullptr, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
-                               dL_drot, backward_geometry, debug_, n_active_features, active_features,
-                               sh_adam ? &adam : nullptr, records_out, layout_out, supported_out);
+    if (!scene || !call) return invalid(me + "null scene or call");
+    if (records_out && scene->P > 0 && !call->d_dL_dmean2D) return invalid(me + "null dL_dmean2D");
+    ShAdamArgs adam = {};
+    if (sh_adam)
+        if (int e = make_sh_adam(*scene, *sh_adam, beta1, beta2, eps, step, grad_scale, skip_flag, &adam)) return e;
+    return backward_split_impl(stream_, geometry_stream_, *scene, *call, sh_adam ? &adam : nullptr, records_out, layout_out,
+                               supported_out);
 }
 
 int r3dg_gradient_records_scatter(void* stream_, int P, int S, float* records, const int* layout_, float* dL_dmean2D,

@@ -40,7 +40,7 @@ class FusedAdam:
 
     def fused_step_of(self, i, step, grad_scale=1.0, skip_flag=None):
         """The trailing arguments of an entry point whose kernel applies group i's update as step `step` itself, where the
-        gradient is produced (r3dg_rasterize_backward_split_sh_adam): (group descriptor, betas, eps, step, grad_scale, skip flag).
+        gradient is produced (r3dg_rasterize_backward_split's sh_adam): (group descriptor, betas, eps, step, grad_scale, skip flag).
         The descriptor names no gradient buffer; it lives until the next call."""
         g = self.groups[i]
         p = g["param"]

@@ -534,7 +534,7 @@ class FusedStage2Step(FusedStepBase):
         return count
 
     def _fuses_sh_adam(self):
-        """A whole iteration lets the geometry backward apply the SH colour group's Adam (r3dg_rasterize_backward_split_sh_adam:
+        """A whole iteration lets the geometry backward apply the SH colour group's Adam (r3dg_rasterize_backward_split's sh_adam:
         the gradient rows never reach device memory, the group gets no Adam launch)?  Single GPU (under data parallelism the
         gradient has to travel in bucket A, and replicas must stay bit-identical through ONE kernel), the group trains, the
         geometry backward runs at all, the backward in use has the kernel for this SH size (asked every iteration: it depends on
@@ -544,7 +544,7 @@ class FusedStage2Step(FusedStepBase):
                 and os.environ.get("R3DG_SH_ADAM_IN_BACKWARD", "1") != "0" and can(self.M))
 
     def _reads_gradient_records(self):
-        """A whole iteration reads the tile backward's gradient records in place (r3dg_rasterize_backward_split_records; no
+        """A whole iteration reads the tile backward's gradient records in place (r3dg_rasterize_backward_split with record outputs; no
         scatter pass)?  The geometry backward runs at all, the backward in use takes `gradient_records`, and
         R3DG_GRADIENT_RECORDS is not 0 (the A/B switch: 0 restores the scatter pass).  Whether the call's kernel instance has
         such records is the library's answer, call by call (_raster_backward)."""

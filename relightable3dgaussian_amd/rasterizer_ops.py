@@ -13,6 +13,7 @@ import torch
 from . import _abi, _lib
 
 NUM_CHANNELS = 3
+RasterScene, RasterOutputs, RasterBackward = (_abi.structs["r3dg_raster_" + n] for n in ("scene", "outputs", "backward"))
 
 
 def _f32c(t):
@@ -50,6 +51,15 @@ class _Resizer:
             except Exception:          # surfaces as R3DG_EALLOC -> RuntimeError
                 return 0
         return cb
+
+
+def _scene(P, S, degree, M, W, H, scale_modifier, tan_fovx, tan_fovy, cx=0.0, cy=0.0, **inputs):
+    """The r3dg_raster_scene of a call, and {field name without d_: contiguous fp32 tensor or None} of the `inputs` its pointers
+    name: the caller keeps those referenced for as long as kernels of the call may still be enqueued."""
+    kept = {k: _f32c(v) for k, v in inputs.items()}
+    return RasterScene(P=P, S=S, D=int(degree), M=M, width=W, height=H, scale_modifier=float(scale_modifier),
+                       tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), cx=float(cx), cy=float(cy),
+                       **{"d_" + k: _lib.ptr(v) for k, v in kept.items()}), kept
 
 
 def _offsets(fn, n, *args):
@@ -147,20 +157,19 @@ def rasterize_gaussians_begin(background, means3D, features, colors, opacity, sc
     ticket = C.c_void_p(None)
     if P != 0:
         M = sh.size(1) if sh.size(0) != 0 else 0
-        t = [_f32c(x) for x in (background, means3D, sh, colors, features, opacity, scales, rotations, cov3D_precomp,
-                                viewmatrix, projmatrix, campos)]
-        bg_, means_, sh_, col_, feat_, op_, sc_, rot_, cov_, vm_, pm_, cam_ = t
-        if feat_ is not None and feat_.data_ptr() != features.data_ptr():
+        scene, kept = _scene(P, S, degree, M, W, H, scale_modifier, tan_fovx, tan_fovy, cx, cy, background=background,
+                             means3D=means3D, shs=sh, colors_precomp=colors, features=features, opacities=opacity, scales=scales,
+                             rotations=rotations, cov3D_precomp=cov3D_precomp, viewmatrix=viewmatrix, projmatrix=projmatrix,
+                             campos=campos)
+        if kept["features"] is not None and kept["features"].data_ptr() != features.data_ptr():
             raise RuntimeError("rasterize_gaussians_begin needs contiguous features (their contents are read later)")
-        rs.keep = t                                   # inputs stay alive until finish()
-        common = (rs.callbacks[0], rs.callbacks[1], rs.callbacks[2], None, P, S, int(degree), M,
-                  _lib.ptr(bg_), W, H, _lib.ptr(means_), _lib.ptr(sh_), _lib.ptr(col_), _lib.ptr(feat_), _lib.ptr(op_),
-                  _lib.ptr(sc_), float(scale_modifier), _lib.ptr(rot_), _lib.ptr(cov_), _lib.ptr(vm_), _lib.ptr(pm_),
-                  _lib.ptr(cam_), float(tan_fovx), float(tan_fovy), float(cx), float(cy), int(bool(prefiltered)),
-                  int(bool(computer_pseudo_normal)), out_color.data_ptr(), out_opacity.data_ptr(), out_depth.data_ptr(),
-                  _lib.ptr(out_feature), out_normal.data_ptr(), out_surface_xyz.data_ptr(),
-                  out_weights.data_ptr() if out_weights is not None else None,
-                  radii.data_ptr(), int(bool(debug)))
+        rs.keep = list(kept.values())                 # inputs stay alive until finish()
+        outputs = RasterOutputs(
+            prefiltered=int(bool(prefiltered)), compute_pseudo_normal=int(bool(computer_pseudo_normal)), debug=int(bool(debug)),
+            d_out_color=out_color.data_ptr(), d_out_opacity=out_opacity.data_ptr(), d_out_depth=out_depth.data_ptr(),
+            d_out_feature=_lib.ptr(out_feature), d_out_normal=out_normal.data_ptr(), d_out_surface_xyz=out_surface_xyz.data_ptr(),
+            d_out_weights=_lib.ptr(out_weights), d_radii=radii.data_ptr())
+        common = (rs.callbacks[0], rs.callbacks[1], rs.callbacks[2], None, C.byref(scene), C.byref(outputs))
         with torch.cuda.device(dev):
             if capacity is None:
                 st = L.r3dg_rasterize_forward_begin(_lib.current_stream(), *common, C.byref(ticket))
@@ -192,8 +201,8 @@ def rasterize_gaussians(background, means3D, features, colors, opacity, scales, 
 
 
 class GradientRecords:
-    """The tile backward's per-Gaussian gradient records, left in place (r3dg_rasterize_backward_split_records): `ptr` is the
-    first of P rows of 16 floats in the library's scratch of the stream the backward ran on, `layout` the
+    """The tile backward's per-Gaussian gradient records, left in place (r3dg_rasterize_backward_split with record outputs): `ptr`
+    is the first of P rows of 16 floats in the library's scratch of the stream the backward ran on, `layout` the
     R3DG_GRAD_RECORD_LAYOUT_INTS ints that say which channel holds what.  Handed EMPTY to rasterize_gaussians_backward
     (`gradient_records=`); it comes back filled -- true -- when the call's kernel instance has such rows, and then the caller
     runs r3dg_stage2_unpack_gradients_records and r3dg_stage2_activate_backward_with_records on them (the second zeroes the
@@ -226,7 +235,7 @@ def rasterize_gaussians_backward(background, means3D, features, radii, colors, s
     dL_dout_feature are zero; they are then skipped by the tile kernel (same results).  `zeroed_accumulators`: optional float32
     tensor of (11 + S) * P floats (any contents since round 5 -- the name is from when it had to be zeros) that takes the place
     of the slab allocated here; dL_dmeans2D, dL_dconic, dL_dopacity, dL_dcolors and dL_dfeatures are views of it.
-    `sh_adam` (FusedAdam.fused_step_of(group of `sh`, ...); r3dg_rasterize_backward_split_sh_adam): the per-Gaussian geometry
+    `sh_adam` (FusedAdam.fused_step_of(group of `sh`, ...); r3dg_rasterize_backward_split's sh_adam): the per-Gaussian geometry
     backward applies the Adam step of the SH group itself -- `sh` and its two moment tensors are updated in place and the
     returned dL_dsh is NOT written (it keeps whatever it held).  Raises where the library has no such kernel
     (sh_adam_supported).
@@ -277,52 +286,42 @@ def rasterize_gaussians_backward(background, means3D, features, radii, colors, s
     dL_drotations = (torch.empty if have_scale else torch.zeros)((P, 4), **fopt)
 
     if P != 0:
-        t = [_f32c(x) for x in (background, means3D, sh, features, colors, scales, rotations, cov3D_precomp, viewmatrix,
-                                projmatrix, campos, dL_dout_color, dL_dout_opacity, dL_dout_depth, dL_dout_feature)]
-        bg_, means_, sh_, feat_, col_, sc_, rot_, cov_, vm_, pm_, cam_, gC, gO, gD, gF = t
+        scene, kept = _scene(P, S, degree, M, W, H, scale_modifier, tan_fovx, tan_fovy, background=background, means3D=means3D,
+                             shs=sh, features=features, colors_precomp=colors, scales=scales, rotations=rotations,
+                             cov3D_precomp=cov3D_precomp, viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos)
+        gC, gO, gD, gF = [_f32c(x) for x in (dL_dout_color, dL_dout_opacity, dL_dout_depth, dL_dout_feature)]
         radii_ = radii.contiguous()
+        if sh_adam is not None and (kept["shs"] is not sh or not have_sh):
+            raise RuntimeError("sh_adam: needs the contiguous float32 SH tensor itself as `sh`")
+        if active_features is None:
+            n_act, act = -1, None
+        else:
+            n_act = len(active_features)
+            act = (C.c_int * max(1, n_act))(*[int(a) for a in active_features])
+        # (`kept`, the four gradients, radii_ and `act` are locals: referenced until both calls below have returned)
+        call = RasterBackward(
+            R=int(R), d_radii=radii_.data_ptr(), d_geom_buffer=_lib.ptr(geomBuffer), d_binning_buffer=_lib.ptr(binningBuffer),
+            d_img_buffer=_lib.ptr(imageBuffer), d_dL_dpix=_lib.ptr(gC), d_dL_dpix_o=_lib.ptr(gO), d_dL_dpix_d=_lib.ptr(gD),
+            d_dL_dpix_f=_lib.ptr(gF), d_dL_dmean2D=dL_dmeans2D.data_ptr(), d_dL_dconic=dL_dconic.data_ptr(),
+            d_dL_dopacity=dL_dopacity.data_ptr(), d_dL_dcolor=dL_dcolors.data_ptr(), d_dL_dfeature=_lib.ptr(dL_dfeatures),
+            d_dL_dmean3D=dL_dmeans3D.data_ptr(), d_dL_dcov3D=dL_dcov3D.data_ptr(), d_dL_dsh=_lib.ptr(dL_dsh),
+            d_dL_dscale=dL_dscales.data_ptr(), d_dL_drot=dL_drotations.data_ptr(), backward_geometry=int(bool(backward_geometry)),
+            debug=int(bool(debug)), n_active_features=n_act, active_features=C.addressof(act) if act is not None else None)
         with torch.cuda.device(dev):
             cur = _lib.current_stream()
             gs = cur if geometry_stream is None else C.c_void_p(geometry_stream.cuda_stream)
-            if active_features is None:
-                n_act, act = -1, None
-            else:
-                n_act = len(active_features)
-                act = (C.c_int * max(1, n_act))(*[int(a) for a in active_features])
-            if sh_adam is not None:
-                if sh_ is not sh or not have_sh:
-                    raise RuntimeError("sh_adam: needs the contiguous float32 SH tensor itself as `sh`")
-                entry, tail = L.r3dg_rasterize_backward_split_sh_adam, sh_adam
-            else:
-                entry, tail = L.r3dg_rasterize_backward_split, ()
-            st = None
+            head = (cur, gs, C.byref(scene), C.byref(call)) + \
+                (tuple(sh_adam) if sh_adam is not None else (None, 0.0, 0.0, 0.0, 1, 1.0, None))
             if gradient_records is not None:
                 rows, supported = C.c_void_p(), C.c_int(0)
                 layout = (C.c_int * _abi.constants["R3DG_GRAD_RECORD_LAYOUT_INTS"])()
-                st = L.r3dg_rasterize_backward_split_records(
-                    cur, gs, P, S, int(degree), M, int(R), _lib.ptr(bg_), W, H, _lib.ptr(means_),
-                    _lib.ptr(sh_), _lib.ptr(feat_), _lib.ptr(col_), _lib.ptr(sc_), float(scale_modifier), _lib.ptr(rot_),
-                    _lib.ptr(cov_), _lib.ptr(vm_), _lib.ptr(pm_), _lib.ptr(cam_), float(tan_fovx), float(tan_fovy),
-                    radii_.data_ptr(), _lib.ptr(geomBuffer), _lib.ptr(binningBuffer), _lib.ptr(imageBuffer), _lib.ptr(gC),
-                    _lib.ptr(gO), _lib.ptr(gD), _lib.ptr(gF), dL_dmeans2D.data_ptr(), dL_dmeans3D.data_ptr(),
-                    dL_dcov3D.data_ptr(), _lib.ptr(dL_dsh), dL_dscales.data_ptr(), dL_drotations.data_ptr(),
-                    int(bool(backward_geometry)), int(bool(debug)), n_act, act,
-                    *(sh_adam if sh_adam is not None else (None, 0.0, 0.0, 0.0, 1, 1.0, None)),
-                    C.byref(rows), layout, C.byref(supported))
+                st = L.r3dg_rasterize_backward_split(*head, C.byref(rows), layout, C.byref(supported))
                 _lib.check(st, "rasterize_gaussians_backward")
                 if supported.value:
                     gradient_records.ptr, gradient_records.layout = rows.value, layout
                     gradient_records.P, gradient_records.device = P, dev
                     return (dL_dmeans2D, None, None, dL_dmeans3D, None, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
-            st = entry(
-                cur, gs, P, S, int(degree), M, int(R), _lib.ptr(bg_), W, H, _lib.ptr(means_),
-                _lib.ptr(sh_), _lib.ptr(feat_), _lib.ptr(col_), _lib.ptr(sc_), float(scale_modifier), _lib.ptr(rot_),
-                _lib.ptr(cov_), _lib.ptr(vm_), _lib.ptr(pm_), _lib.ptr(cam_), float(tan_fovx), float(tan_fovy),
-                radii_.data_ptr(), _lib.ptr(geomBuffer), _lib.ptr(binningBuffer), _lib.ptr(imageBuffer), _lib.ptr(gC),
-                _lib.ptr(gO), _lib.ptr(gD), _lib.ptr(gF), dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(),
-                dL_dopacity.data_ptr(), dL_dcolors.data_ptr(), _lib.ptr(dL_dfeatures), dL_dmeans3D.data_ptr(),
-                dL_dcov3D.data_ptr(), _lib.ptr(dL_dsh), dL_dscales.data_ptr(), dL_drotations.data_ptr(),
-                int(bool(backward_geometry)), int(bool(debug)), n_act, act, *tail)
+            st = L.r3dg_rasterize_backward_split(*head, None, None, None)
         _lib.check(st, "rasterize_gaussians_backward")
     return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dfeatures, dL_dcov3D, dL_dsh, dL_dscales,
             dL_drotations)

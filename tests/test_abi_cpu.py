@@ -11,9 +11,11 @@ _i, _f, _p, _A = C.c_int, C.c_float, C.c_void_p, _abi.ALLOC_FN
 
 def test_c_compiler_agrees_on_structs_constants_and_options(tmp_path):
     """A C program generated from the reader's own name lists (a name the compiler rejects fails too) prints the size, and per
-    field the offset, size and type, of the three structs, every integer #define and every R3DG_OPT_* enumerator."""
-    assert set(_abi.structs) == {"r3dg_adam_group", "r3dg_densify_config", "r3dg_densify_group"}
-    assert (fused_adam.AdamGroup, densify.DensifyConfig, densify.DensifyGroup) == tuple(_abi.structs.values())
+    field the offset, size and type, of the six structs, every integer #define and every R3DG_OPT_* enumerator."""
+    assert set(_abi.structs) == {"r3dg_adam_group", "r3dg_densify_config", "r3dg_densify_group", "r3dg_raster_scene",
+                                 "r3dg_raster_outputs", "r3dg_raster_backward"}
+    assert (fused_adam.AdamGroup, densify.DensifyConfig, densify.DensifyGroup) == tuple(
+        _abi.structs[n] for n in ("r3dg_adam_group", "r3dg_densify_config", "r3dg_densify_group"))
     assert len(_abi.constants) >= 15 and len(_abi.options) == 13
     kind = "_Generic(%s, float: 'f', int: 'i', unsigned int: 'I', unsigned long: 'L', default: 'P')"   # ctypes' own type codes
     rows = []                                                       # (what, C expression, the reader's value)
@@ -46,6 +48,8 @@ def test_type_rule_on_one_prototype_of_each_kind():
     assert P["r3dg_binning_state_bytes"] == (C.c_size_t, [C.c_int64])
     assert P["r3dg_rasterize_forward"] == (_i, [_p, _A, _A, _A, _p, _i, _i, _i, _i, _p, _i, _i] + [_p] * 6 + [_f] + [_p] * 5 +
                                            [_f] * 4 + [_i, _i] + [_p] * 8 + [_i, C.POINTER(_i)])
+    assert P["r3dg_rasterize_backward_split"] == (_i, [_p] * 5 + [_f] * 3 + [_i, _f, _p, C.POINTER(_p), C.POINTER(_i),
+                                                         C.POINTER(_i)])
     assert P["r3dg_context_make_current"] == (_i, [_p, C.POINTER(_p)])
     assert P["r3dg_adam_step"] == (_i, [_p, _i, _p, _f, _f, _f, _i, _f, _p])
     assert P["r3dg_profile_read"] == (_i, [C.POINTER(C.c_double), C.POINTER(_i)])
@@ -62,6 +66,7 @@ def test_type_rule_on_one_prototype_of_each_kind():
     "int r3dg_t(float* out);",                              # a pointer that is neither device memory nor a known host out-pointer
     "short r3dg_s(void);",                                  # an unknown return type
     "static inline int r3dg_r(void) { return 0; }",         # r3dg_*( outside a prototype
+    "typedef struct r3dg_q { const r3dg_adam_group* g; } r3dg_q;",      # a struct field that points to another struct
 ])
 def test_reader_fails_loudly_naming_the_line(line):
     header = open(_abi.HEADER).read()

@@ -1,6 +1,6 @@
-"""The tile backward's gradient records read in place (r3dg_rasterize_backward_split_records, r3dg_stage2_unpack_gradients_records,
+"""The tile backward's gradient records read in place (r3dg_rasterize_backward_split with record outputs, r3dg_stage2_unpack_gradients_records,
 r3dg_stage2_activate_backward_with_records) against the scatter pass and the three kernels that read its arrays
-(r3dg_gradient_records_scatter / r3dg_rasterize_backward_split[_sh_adam], r3dg_stage2_unpack_gradients,
+(r3dg_gradient_records_scatter / r3dg_rasterize_backward_split without them, r3dg_stage2_unpack_gradients,
 r3dg_stage2_activate_backward_with).  Given the same record contents each reader runs the same arithmetic on the same values
 whichever place it loads them from, so every output is compared BIT FOR BIT.
 

@@ -342,12 +342,62 @@ def _oracle_variant(case, ref, ups):
                                             want_bounds=True)
 
 
+def _reference_shaped(case, out, ups):
+    """r3dg_rasterize_forward and r3dg_rasterize_backward, the two entries with the reference's positional lists, called through
+    ctypes with this test's own resize callbacks: the forward against the cached rasterize_gaussians result `out`; returns the
+    backward's 9-tuple in the op's order and its dL_dconic [P,4]."""
+    import ctypes as C
+    from relightable3dgaussian_amd import _lib, rasterizer_ops as ro
+    L = _lib.lib()
+    H, W, S, P = case["H"], case["W"], case["S"], case["P"]
+    a = fwd_args(case, DEV)
+    bg, means, feats, colors, opac, scales, rots, cov, vm, pm, sh, campos = [
+        _lib.ptr(ro._f32c(x)) for x in (a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[8], a[9], a[10], a[17], a[19])]
+    M = a[17].size(1) if a[17].numel() else 0
+    new = lambda *shape, **kw: torch.empty(shape, device=DEV, **kw)
+    state = [None, None, None]
+
+    def resizer(i):
+        def cb(_user, nbytes):
+            state[i] = new(int(nbytes), dtype=torch.uint8)
+            return state[i].data_ptr()
+        return _lib.ALLOC_FN(cb)
+    cbs = [resizer(i) for i in range(3)]
+    color, opacity, depth, feature, normal, xyz = new(3, H, W), new(1, H, W), new(1, H, W), new(S, H, W), new(3, H, W), new(3, H, W)
+    weights, radii, n = torch.zeros(P, 1, device=DEV), new(P, dtype=torch.int32), C.c_int(-1)
+    _lib.check(L.r3dg_rasterize_forward(
+        _lib.current_stream(), cbs[0], cbs[1], cbs[2], None, P, S, a[18], M, bg, W, H, means, sh, colors, feats, opac, scales,
+        a[7], rots, cov, vm, pm, campos, a[11], a[12], a[13], a[14], 0, 1, color.data_ptr(), opacity.data_ptr(), depth.data_ptr(),
+        _lib.ptr(feature), normal.data_ptr(), xyz.data_ptr(), weights.data_ptr(), radii.data_ptr(), 0, C.byref(n)),
+        "r3dg_rasterize_forward")
+    torch.cuda.synchronize()
+    off = ro._offsets(L.r3dg_image_state_offsets, 3, W, H)[1]
+    n_contrib = state[2][off:off + 4 * H * W].view(torch.int32).view(H, W)
+    assert n.value == out[0]
+    for i, got in enumerate((n_contrib, color, opacity, depth, feature), 1):
+        assert torch.equal(got, out[i]), "forward output %d" % i
+    assert torch.allclose(weights, out[8], rtol=1e-5, atol=1e-6)        # (float atomics: order)
+    g2, gconic, gop, gcol, gfeat = new(P, 3), new(P, 4), new(P, 1), new(P, 3), new(P, S)
+    g3, gcov, gsh, gsc, grot = new(P, 3), new(P, 6), new(P, M, 3), new(P, 3), new(P, 4)
+    _lib.check(L.r3dg_rasterize_backward(
+        _lib.current_stream(), P, S, a[18], M, n.value, bg, W, H, means, sh, feats, colors, scales, a[7], rots, cov, vm, pm,
+        campos, a[11], a[12], radii.data_ptr(), state[0].data_ptr(), _lib.ptr(state[1]), state[2].data_ptr(),
+        ups[0].data_ptr(), ups[1].data_ptr(), ups[2].data_ptr(), _lib.ptr(ups[3]), g2.data_ptr(), gconic.data_ptr(),
+        gop.data_ptr(), gcol.data_ptr(), _lib.ptr(gfeat), g3.data_ptr(), gcov.data_ptr(), _lib.ptr(gsh), gsc.data_ptr(),
+        grot.data_ptr(), 1, 0), "r3dg_rasterize_backward")
+    torch.cuda.synchronize()
+    return (g2, gcol, gop, g3, gfeat, gcov, gsh, gsc, grot), -0.5 * gconic
+
+
 @pytest.mark.parametrize("name", list(VARIANT_CASES))
-@pytest.mark.parametrize("variant", ["split_active_subset", "lean", "lean_off", "features_only", "bounded_forward"])
+@pytest.mark.parametrize("variant", ["split_active_subset", "lean", "lean_off", "features_only", "bounded_forward",
+                                     "reference_shaped"])
 def test_variant_entry_points_against_the_oracle_elementwise(name, variant):
     """Every other way into the tile backward -- r3dg_rasterize_backward_split with an active feature subset, the lean
-    instances (no depth gradient) with BWD_LEAN on and off, r3dg_rasterize_backward_features, and the backward behind
-    r3dg_rasterize_forward_begin_bounded -- against the ORACLE (not against each other) under the element-wise bounds."""
+    instances (no depth gradient) with BWD_LEAN on and off, r3dg_rasterize_backward_features, the backward behind
+    r3dg_rasterize_forward_begin_bounded, and the two positional entries (r3dg_rasterize_forward, r3dg_rasterize_backward:
+    the only code that fills the call structs from a list) -- against the ORACLE (not against each other) under the
+    element-wise bounds."""
     from relightable3dgaussian_amd import _lib, rasterizer_ops as ro
     case, out, ref, ups = _variant_setup(name)
     H, W, S, P = case["H"], case["W"], case["S"], case["P"]
@@ -370,6 +420,9 @@ def test_variant_entry_points_against_the_oracle_elementwise(name, variant):
         torch.cuda.synchronize()
         ok, msgs = _elementwise(label, case, ref, (None, None, None, None, only, None, None, None, None), None, oref,
                                 tile_only=("feature",))
+    elif variant == "reference_shaped":
+        grads, conic = _reference_shaped(case, out, dev)
+        ok, msgs = _elementwise(label, case, ref, grads, conic, oref)
     else:
         state, R = out, out[0]
         if variant == "bounded_forward":

@@ -1,6 +1,6 @@
-"""r3dg_rasterize_backward_split_sh_adam: the per-Gaussian geometry backward that applies the SH colour group's Adam itself
+"""r3dg_rasterize_backward_split with sh_adam: the per-Gaussian geometry backward that applies the SH colour group's Adam itself
 (csrc/rasterizer_preprocess_bwd.hip, preprocess_backward_kernel<true, true>) against the two launches it replaces in a whole
-single-GPU iteration -- r3dg_rasterize_backward_split, then r3dg_adam_step on the one group.  Both kernels compile the same update
+single-GPU iteration -- the same entry without it, then r3dg_adam_step on the one group.  Both kernels compile the same update
 statements (csrc/adam_update.hpp) with the same flags, so parameters and moments are compared BIT FOR BIT, and so is every other
 output of the backward.
 
